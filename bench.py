@@ -11,7 +11,11 @@ Part-presence patterns (valid_id) are synthetic and already resident in HBM when
 no per-step collective; the frozen weights are broadcast from rank 0 once (RCCL), outside the timed
 region (reported as weights_bcast_ms).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline`.  A plain run times the headline and nothing
+else; `--full` adds the secondary measurements and checks after the timed region (clock / power samples and the box's bare-MFMA
+calibration, parity vs the CPU oracle, T=100 / f32 / sweep / small-batch lines, `cpu_baseline`, training iteration).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32; inputs are seeded, so two builds
+can be compared output for output).
 """
 import argparse
 import json
@@ -596,6 +600,23 @@ def small_batch_line(params, names, sampler, N, precision, dev, T):
         return {"error": repr(e)[:200]}
 
 
+def dump_outputs(out_dir, arrays, budget_bytes=64 * 2 ** 20):
+    """`--dump-outputs`: every array of `arrays` (first axis = shape index) as float32 out_dir/<name>.npy.  Beyond `budget_bytes` in all,
+    the same fixed, seeded sample of shapes is taken from every array and its indices are written as shape_index.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = next(iter(host.values())).shape[0]
+    assert all(a.shape[0] == total for a in host.values()), {k: a.shape for k, a in host.items()}
+    per_shape = sum(a[:1].nbytes for a in host.values())
+    if per_shape * total > budget_bytes:
+        keep = max(1, (budget_bytes - 4096) // (per_shape + 8))
+        idx = np.sort(np.random.default_rng(0).choice(total, size=keep, replace=False))
+        host = {k: a[idx] for k, a in host.items()}
+        host["shape_index"] = idx.astype(np.float64)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -615,7 +636,13 @@ def main():
     ap.add_argument("--no-parity", action="store_true",
                     help="skip the secondary blocks: parity (HIP vs PyTorch-CPU oracle, T=100, 2 shapes), t100, f32, sweep, small_batch")
     ap.add_argument("--dump-clouds", default=None, help="rank 0 writes the last step's gathered clouds (shapes, N, 3) to this .npy")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed step's outputs to DIR/<name>.npy (float32, at most 64 MB: a fixed sample of shapes beyond)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements and checks after the timed region (box samples + calibration, parity, t100, "
+                         "f32, sweep, small_batch, cpu_baseline, train_iteration; the --no-* switches still drop single blocks)")
     args = ap.parse_args()
+    assert args.steps >= 1 and args.warmup >= 0, (args.steps, args.warmup)
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -691,12 +718,14 @@ def main():
     gen = torch.Generator(device=dev)
 
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    last_lat = {}
 
     def one_step(i, timed):
         gen.manual_seed(1234 + i)                                        # the whole job's draws, then this rank's block
         w = torch.randn(total, 256, 4, device=dev, generator=gen)[lo:hi]    # part_encoders.py:1054
         an = torch.randn(total, 32, device=dev, generator=gen)[lo:hi]       # :1065 (K = 1 noise per shape)
         lat = sampler.sample_latents(w, an, valid, K=1, npoints=N)
+        last_lat["lat"] = lat
         ctx = eng.prepare_shapes(lat["part_code"], lat["params"][:, :3], lat["params"][:, 3:], lat["valid_id"])
         if timed:
             ev[i][0].record()
@@ -717,7 +746,7 @@ def main():
             torch.cuda.synchronize()
 
     fence()
-    box = BoxSampler(torch.cuda.current_device()).start() if rank == 0 else None
+    box = BoxSampler(torch.cuda.current_device()).start() if rank == 0 and args.full else None
     t0 = time.perf_counter()
     out = None
     for i in range(args.steps):
@@ -726,10 +755,16 @@ def main():
     t1 = time.perf_counter()
     dt = t1 - t0
     calib = None
-    if rank == 0:
+    if box is not None:
         box.stop()
         if world == 1 and args.precision == "bf16":
             calib = box_calibration()      # right behind the timed region: same box, same thermal state
+    dumped = None
+    if args.dump_outputs:                  # the last timed step's per-point labels and part parameters, gathered like its clouds
+        lat = last_lat["lat"]
+        dumped = {"seg_mask": lat["seg_mask"].float(), "part_params": lat["params"].float()}
+        if dist is not None:
+            dumped = {k: gather_clouds(v.contiguous(), dst=0, sizes=sizes) for k, v in dumped.items()}
     if dist is not None:
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -747,6 +782,8 @@ def main():
         assert out.shape[0] == total, (out.shape, total)
         if args.dump_clouds:
             np.save(args.dump_clouds, out.cpu().numpy())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"clouds": out, **dumped})
         value = total * args.steps / dt
         F = flops_per_step(N) * T * B                      # algorithmic FLOPs per launch (one rank)
         traffic, traffic_src = measured_traffic(T, B, N) if args.precision == "bf16" else (None, None)
@@ -767,7 +804,8 @@ def main():
                          "kernel": variant + " (persistent T-step chain)", "kernel_variant": variant, "kernel_ms": kern_ms,
                          "flops_per_launch": F},
         }
-        res["roofline"]["box"] = box.summary(t0, t1)   # clock / power / temperature samples taken DURING the timed region
+        if box is not None:
+            res["roofline"]["box"] = box.summary(t0, t1)   # clock / power / temperature samples taken DURING the timed region
         if args.precision == "bf16":
             res["roofline"]["power_limited_ceiling"] = power_limited_ceiling()
             if calib is not None and "bare_mfma_tflops" in calib:
@@ -777,7 +815,8 @@ def main():
                 res["roofline"]["executed_tflops"] = executed
                 res["roofline"]["frac_of_box"] = executed / calib["bare_mfma_tflops"]
                 res["roofline"]["frac_of_box_algorithmic"] = achieved / calib["bare_mfma_tflops"]
-            res["roofline"]["box_calibration"] = calib
+            if args.full:
+                res["roofline"]["box_calibration"] = calib
         res["config"]["shapes_gathered"] = int(out.shape[0])
         if world_seen is not None:   # what the process group itself reports: the SCALE record shows the collective library saw N ranks
             res["config"].update({"backend": world_seen["backend"], "world_size_seen": world_seen["world_size"],
@@ -785,16 +824,16 @@ def main():
                                   "gather": gather_info["gather"], "gather_fallback": gather_info["fallback"], "shapes_per_rank": sizes,
                                   "collective_library": collective_library(), "transport": rccl_transport_summary(),
                                   "rank_kernel_ms": [r[0] for r in rank_ms], "rank_wall_ms_per_step": [r[1] for r in rank_ms]})
-        if world == 1 and not args.no_parity:
+        if args.full and world == 1 and not args.no_parity:
             res["parity"] = parity_block(Wnp, N)
             res["t100"] = t100_line(params, names, B, N, args.precision, dev)
             if args.precision == "bf16":
                 res["f32"] = f32_line(params, names, B, N, T, dev)
             res["sweep"] = sweep_block(params, names, args.precision, dev, T)
             res["small_batch"] = small_batch_line(params, names, sampler, N, args.precision, dev, T)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(Wnp, N)
-        if world == 1 and not args.no_train_line and args.precision == "bf16":
+        if args.full and world == 1 and not args.no_train_line and args.precision == "bf16":
             res["train_iteration"] = train_iteration(Wnp, B, N)
         print(json.dumps(res), flush=True)
     if dist is not None:

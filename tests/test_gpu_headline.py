@@ -201,14 +201,14 @@ def test_bench_two_ranks_rccl():
 
 
 def test_bench_line_contract_single_gpu(tmp_path):
-    """The N = 1 JSON line of bench.py (driver contract + the tier's `roofline` / `cpu_baseline` objects + round 2's `parity` and
+    """The N = 1 JSON line of bench.py --full (driver contract + the tier's `roofline` / `cpu_baseline` objects + round 2's `parity` and
     `t100` blocks) on a reduced run: every key present, numbers finite, the workload named."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     env = dict(os.environ)
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--timesteps", "20", "--batch", "32",
-                        "--no-train-line"], env=env, capture_output=True, text=True, timeout=900)
+                        "--no-train-line", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
@@ -227,6 +227,38 @@ def test_bench_line_contract_single_gpu(tmp_path):
     assert ow["kernel_variant"] == "k_denoise_pipe<8>" and ow["w1_fold"]["folded"] and ow["w1_fold"]["channel"] not in (127, -1), ow
     assert all("error" not in v and v["finite"] and v["shapes_per_s"] > 0 for v in d["sweep"].values()) and d["sweep"]["gen_car"]["npoints"] == 8192
     assert "error" not in d["small_batch"] and d["small_batch"]["B1"]["ms_per_chain"] > 0 and d["small_batch"]["B4"]["shapes_per_s"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """A plain bench.py run (no --full) times the headline only: --steps timed steps, `ms_per_step`, none of the secondary blocks.
+    --dump-outputs writes the last timed step's clouds, per-point part labels and part parameters as float32 .npy files, the clouds
+    equal to --dump-clouds, and a second run with the same arguments writes the same bits."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    env = dict(os.environ)
+    env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"out{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--timesteps", "20",
+                            "--batch", "8", "--dump-outputs", str(out), "--dump-clouds", str(tmp_path / f"clouds{k}.npy")],
+                           env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "shapes/s"
+        assert d["dtype"] == "bf16" and d["higher_is_better"] is True and abs(d["value"] - 8 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+        for k2 in ("cpu_baseline", "parity", "t100", "f32", "sweep", "small_batch", "train_iteration"):
+            assert k2 not in d, k2
+        assert "box" not in d["roofline"] and "box_calibration" not in d["roofline"]
+        files = {p.name: np.load(p) for p in sorted(out.iterdir())}
+        assert sorted(files) == ["clouds.npy", "part_params.npy", "seg_mask.npy"]
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+        assert files["clouds.npy"].shape == (8, 2048, 3) and files["seg_mask.npy"].shape == (8, 2048) and files["part_params.npy"].shape == (8, 6, 4)
+        assert np.array_equal(files["clouds.npy"], np.load(tmp_path / f"clouds{k}.npy"))
+        assert set(np.unique(files["seg_mask.npy"]).tolist()) <= {0.0, 1.0, 2.0, 3.0}
+        runs.append(files)
+    for name in runs[0]:
+        assert np.array_equal(runs[0][name], runs[1][name]), name
 
 
 def test_data_parallel_training_example_two_ranks_on_one_gpu():

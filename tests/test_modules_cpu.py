@@ -1,5 +1,5 @@
-"""CPU: the drop-in modules keep the reference's constructor arguments and state_dict layout; when the reference
-tree is present (dev container) compare key-for-key and check registry installation."""
+"""CPU: the drop-in modules keep the reference's constructor arguments and state_dict layout; compared key-for-key with what the
+reference built from its shipped configs (recorded in tests/golden/reference_modules.npz), and registry installation checked."""
 import os
 import sys
 
@@ -53,30 +53,81 @@ def test_cpu_forward_is_rejected():
             valid_id=torch.ones(1, 4), anchor_assignment=torch.zeros(1, 32, dtype=torch.int32))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/python/difffacto"), reason="reference tree not present")
-def test_keys_and_registry_against_reference():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import ref_import
-    model, cfg = ref_import.build_reference_model(num_timesteps=10)
-    ref_sd = model.diffusion.state_dict()
+def _reference_facts():
+    """tests/golden/reference_modules.npz (tests/golden/make_golden_modules.py): what the reference's own config loader and registry
+    built from the shipped configs — cfg.model, state_dict layouts, parameter counts, the attributes encoders.attach() reads and the
+    keyword arguments its decode passes to p_sample_loop_progressive."""
+    import json
+    import numpy as np
+    with np.load(os.path.join(ROOT, "tests", "golden", "reference_modules.npz")) as z:
+        return json.loads(z["json"].tobytes())
+
+
+def _checkpoint(layout, seed=0):
+    """A checkpoint with the recorded layout (keys in order, shapes, dtypes) and seeded values."""
+    g = torch.Generator().manual_seed(seed)
+    out = {}
+    for k, shape, dtype in layout:
+        dt = getattr(torch, dtype)
+        out[k] = torch.randn(shape, generator=g).to(dt) if dt.is_floating_point else torch.randint(0, 100, shape, generator=g).to(dt)
+    return out
+
+
+@pytest.fixture
+def reference_registry():
+    """The reference's registry protocol (utils/registry.py:1-46: Registry._modules / get; build_from_cfg copies the dict, pops 'type'
+    and calls the registered class with the rest) as the module `difffacto.utils.registry`, its entries standing for the reference's
+    classes, so that difffacto_amd.install() has a registry to register into.  sys.modules is restored afterwards."""
+    import types
+
+    class Registry:
+        def __init__(self, names):
+            self._modules = {n: type(n, (), {"__module__": "difffacto.models"}) for n in names}
+
+        def get(self, name):
+            assert name in self._modules, f"{name} is not registered."
+            return self._modules[name]
+
+    def build_from_cfg(cfg, registry, **kwargs):
+        args = dict(cfg, **kwargs)
+        return registry.get(args.pop("type"))(**args)
+
+    reg = types.ModuleType("difffacto.utils.registry")
+    reg.build_from_cfg = build_from_cfg
+    reg.NETS, reg.DIFFUSIONS, reg.MODELS = Registry(["TransformerNet"]), Registry(["AnchoredDiffusion"]), Registry(["AnchorDiffAE"])
+    reg.ENCODERS = Registry(["PartEncoderForTransformerDecoder", "PointNetV2", "PartAlignerTransformer", "PointNet2SSG", "PointNet2MSG"])
+    reg.SAMPLERS = Registry(["Uniform"])
+    pkg, utils = types.ModuleType("difffacto"), types.ModuleType("difffacto.utils")
+    pkg.utils, utils.registry = utils, reg
+    names = ("difffacto", "difffacto.utils", "difffacto.utils.registry", "pointnet2_ops", "pointnet2_ops.pointnet2_utils",
+             "pointnet2_ops.pointnet2_modules")
+    saved = {k: sys.modules.get(k) for k in names}
+    sys.modules.update({"difffacto": pkg, "difffacto.utils": utils, "difffacto.utils.registry": reg})
+    try:
+        yield reg
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                sys.modules.pop(k, None)
+            else:
+                sys.modules[k] = v
+
+
+def test_keys_and_registry_against_reference(reference_registry):
+    facts = _reference_facts()
+    ref_sd = {k: tuple(shape) for k, shape, _ in facts["gen_chair_T10_diffusion_state_dict"]}
     mine = AnchoredDiffusion(num_timesteps=10, **DIFF_CFG).state_dict()
     assert set(ref_sd) == set(mine)
     for k in ref_sd:
-        assert tuple(ref_sd[k].shape) == tuple(mine[k].shape), k
+        assert ref_sd[k] == tuple(mine[k].shape), k
     # registry installation: the reference's build_from_cfg now yields the libdfx-backed classes
     import difffacto_amd
-    from difffacto.utils.registry import NETS, DIFFUSIONS, build_from_cfg
-    saved = (NETS._modules["TransformerNet"], DIFFUSIONS._modules["AnchoredDiffusion"], dict(sys.modules))
-    try:
-        assert difffacto_amd.install() is True
-        built = build_from_cfg(dict(cfg.model["diffusion"], num_timesteps=10), DIFFUSIONS)
-        assert isinstance(built, AnchoredDiffusion) and isinstance(built.model, TransformerNet)
-        import pointnet2_ops
-        assert pointnet2_ops.pointnet2_utils.gather_operation.__self__.__module__.startswith("difffacto_amd")
-    finally:
-        NETS._modules["TransformerNet"], DIFFUSIONS._modules["AnchoredDiffusion"] = saved[0], saved[1]
-        for k in ("pointnet2_ops", "pointnet2_ops.pointnet2_utils", "pointnet2_ops.pointnet2_modules"):
-            sys.modules[k] = saved[2][k]
+    from difffacto.utils.registry import DIFFUSIONS, build_from_cfg
+    assert difffacto_amd.install() is True
+    built = build_from_cfg(dict(facts["configs"]["gen_chair.py"]["model_cfg"]["diffusion"], num_timesteps=10), DIFFUSIONS)
+    assert isinstance(built, AnchoredDiffusion) and isinstance(built.model, TransformerNet)
+    import pointnet2_ops
+    assert pointnet2_ops.pointnet2_utils.gather_operation.__self__.__module__.startswith("difffacto_amd")
 
 
 ENC_CFG = dict(
@@ -123,25 +174,31 @@ def test_encoder_mirror_state_dict_keys_and_unsupported_options():
         PartEncoderForTransformerDecoder(**{**ENC_CFG, "selective_noise_sampling": True})
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/python/difffacto"), reason="dev container only")
 def test_encoder_mirror_matches_reference_state_dict():
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tools"))
-    import ref_import
-    import contextlib
-    import io
-    with contextlib.redirect_stdout(io.StringIO()):
-        model, _ = ref_import.build_reference_model("gen_chair.py", 10)
+    import types
+    facts = _reference_facts()
+    layout = facts["gen_chair_encoder_state_dict"]
+    ref = {k: tuple(shape) for k, shape, _ in layout}
     from difffacto_amd.encoders import PartEncoderForTransformerDecoder
     enc = PartEncoderForTransformerDecoder(**ENC_CFG)
-    ref = {k: tuple(v.shape) for k, v in model.encoder.state_dict().items()}
     assert ref == {k: tuple(v.shape) for k, v in enc.state_dict().items()}       # incl. encoder.* (PointNetV2): strict loading
-    enc.load_state_dict(model.encoder.state_dict(), strict=True)
+    enc.load_state_dict(_checkpoint(layout), strict=True)
+    # attach() on an object carrying the recorded attributes of the reference's built encoder (construction only: the first
+    # sample_latents call needs the GPU)
     from difffacto_amd.encoders import attach
-    mirror = attach(model.encoder)           # construction only (the first sample_latents call needs the GPU)
+    a = facts["gen_chair_encoder_attrs"]
+    al = a["part_aligner"]
+    ns = types.SimpleNamespace
+    block = ns(attn2=ns(heads=al["heads"]), single_attn=al["single_attn"])
+    part_aligner = ns(transformer_blocks=[block] * al["depth"], proj_out=ns(out_features=al["proj_out_features"]),
+                      **{k: v for k, v in al.items() if k not in ("heads", "single_attn", "depth", "proj_out_features")})
+    flow = [ns(chain=[ns(net_s_t=[ns(out_features=a["flow"]["hidden"])])] * a["flow"]["depth"])] * a["flow"]["count"]
+    built = type("BuiltEncoder", (), {})()          # (attach keeps a weak reference to it)
+    built.__dict__.update(part_aligner=part_aligner, flow=flow, **a["encoder"])
+    mirror = attach(built)
     assert {k for k in mirror.state_dict() if not k.startswith("encoder.")} == {k for k in ref if not k.startswith("encoder.")}
     assert mirror.part_aligner.noise_scale == 100
-    assert model.encoder.sample_latents.__name__ == "sample_latents"
+    assert built.sample_latents.__name__ == "sample_latents"
 
 
 def test_point_padding_helpers_of_the_engine():
@@ -227,102 +284,64 @@ def test_bench_evidence_helpers_read_the_newest_committed_profiles():
     assert abs(b.flops_per_step(2048) - 4.733899e9) < 1e4
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/python/difffacto"), reason="dev container only")
-def test_reference_forward_through_install_and_attach_dry_run(monkeypatch):
-    """The drop-in protocol end to end WITHOUT a GPU: the reference's OWN AnchorDiffAE (built by its registry after
-    difffacto_amd.install(), encoder accelerated with encoders.attach()) runs its gen branch (anchor_gen.py:1034-1084); the two libdfx
-    handles are replaced by numpy-oracle stand-ins (tests/_oracle_backend.py, test-only).  Checks:
-      * the kwargs the reference passes (decode -> p_sample_loop_progressive(shape, anchors=, variance=, ctx=, noise=None,
-        anchor_assignment=, valid_id=, device=, progress=) -> p_sample) are accepted, and the dict it builds equals the golden the
-        unmodified reference produced (forward_gen_B2_K2_T10.npz) when the recorded draws are replayed at the same sites;
-      * seed-less sampling is FRESH per decode() call — ONE key per loop, a new one per call — and replays under torch.manual_seed."""
-    import contextlib
-    import io
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
+def test_reference_decode_protocol_through_install_on_oracle_backend(reference_registry, monkeypatch):
+    """The drop-in protocol WITHOUT a GPU: the reference's AnchorDiffAE.decode (anchor_gen.py:145-169) is one call of the registered
+    diffusion's p_sample_loop_progressive, iterated down to t = 0, with the keyword arguments recorded from the reference in
+    tests/golden/reference_modules.npz (shape positional; anchors=, ctx=, variance=, noise=None, anchor_assignment=, valid_id=, device=,
+    progress=).  The diffusion comes from the registry after difffacto_amd.install(), its libdfx handle replaced by the numpy-oracle
+    stand-in (tests/_oracle_backend.py, test-only).  Checks: those arguments are accepted and the chain runs T steps to a finite cloud;
+    seed-less sampling is FRESH per decode() call — ONE key per loop, a new one per call — and replays under torch.manual_seed.
+    (The forward dict of the reference's gen branch against its golden: test_anchor_diff_ae_mirror_bookkeeping_on_oracle_backends.)"""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import numpy as np
-    import ref_import
-    from _oracle_backend import OracleEngine, OracleLatentSampler
-    from _replay import load_forward_fixture, replay_draws
+    from _oracle_backend import OracleEngine
     import difffacto_amd
-    from difffacto_amd import encoders, modules
-    ref_import.import_reference()
-    from difffacto.config.config import init_cfg, get_cfg
-    from difffacto.utils.registry import NETS, DIFFUSIONS, MODELS, build_from_cfg
+    from difffacto_amd import modules
+    facts = _reference_facts()
+    call = facts["decode_call"]
+    T, B, N = 10, 2, 32
+    assert difffacto_amd.install() is True
+    from difffacto.utils.registry import DIFFUSIONS, build_from_cfg
+    diffusion = build_from_cfg(dict(facts["configs"]["gen_chair.py"]["model_cfg"]["diffusion"], num_timesteps=T), DIFFUSIONS)
+    assert isinstance(diffusion, modules.AnchoredDiffusion)
+    diffusion.model.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_denoiser_weights(0).items()})
+    diffusion.eval()
+    engines = {}
+    monkeypatch.setattr(modules.TransformerNet, "engine", lambda net: engines.setdefault(id(net), OracleEngine(
+        {k: v.detach() for k, v in net.named_parameters()}, net._dfx_T, *net._dfx_betas)))
 
-    batch, draws, expect, meta = load_forward_fixture(os.path.join(ROOT, "tests", "golden", "forward_gen_B2_K2_T10.npz"))
-    T, K, N = int(meta["T"]), int(meta["K"]), batch["ref"].shape[1]
-    saved = (NETS._modules["TransformerNet"], DIFFUSIONS._modules["AnchoredDiffusion"], dict(sys.modules))
+    pc, mean, logvar, valid = synth.make_latents(B, seed=5)
+    t_ = torch.from_numpy
+    ctx = [t_(pc), torch.cat([t_(mean), torch.exp(t_(logvar))], 1)]
+    seg = t_(synth.make_seg_mask(valid, N))
+    idx = seg.long()[:, None, :].expand(-1, 3, -1)
+    anchors, variance = torch.gather(ctx[1][:, :3], 2, idx), torch.gather(ctx[1][:, 3:], 2, idx)
+    kw = dict(anchors=anchors, ctx=ctx, variance=variance, noise=None, anchor_assignment=seg.to(torch.int32), valid_id=t_(valid),
+              device="cpu", progress=False)
+    assert call["args"] == 1 and sorted(kw) == call["kwargs"]
+
+    def decode():   # what the reference's decode does with the diffusion (anchor_gen.py:149-158)
+        steps, final = [], None
+        for t, sample in diffusion.p_sample_loop_progressive([B, 3, N], **kw):
+            steps.append(t)
+            if t == 0:
+                final = sample["sample"].transpose(2, 1)
+        assert steps == list(range(T, -1, -1)) and final.shape == (B, N, 3) and bool(torch.isfinite(final).all())
+        return final
+
+    OracleEngine.seeds_seen = []
     try:
-        assert difffacto_amd.install() is True
-        init_cfg(os.path.join(ref_import.REF_ROOT, "configs", "gen_chair.py"))
-        cfg = get_cfg()
-        cfg.model["num_timesteps"] = T
-        with contextlib.redirect_stdout(io.StringIO()):
-            model = build_from_cfg(cfg.model, MODELS).eval()
-        assert type(model).__module__.startswith("difffacto.") and isinstance(model.diffusion, modules.AnchoredDiffusion)
-        model.npoints, model.cimle_sample_num, model.ret_traj, model.ret_interval = N, K, True, int(meta["ret_interval"])
-        model.diffusion.model.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_denoiser_weights(0).items()})
-        sd = model.encoder.state_dict()
-        for k, v in synth.make_latent_weights(0).items():
-            sd[k] = torch.from_numpy(v.copy())
-        for k, v in synth.make_pointnet_v2_weights(0).items():
-            sd["encoder." + k] = torch.from_numpy(v.copy())
-        model.encoder.load_state_dict(sd)
-        encoders.attach(model.encoder)
-
-        engines = {}
-
-        def fake_engine(net):
-            key = id(net)
-            if key not in engines:
-                engines[key] = OracleEngine({k: v.detach() for k, v in net.named_parameters()}, net._dfx_T, *net._dfx_betas)
-            return engines[key]
-
-        monkeypatch.setattr(modules.TransformerNet, "engine", fake_engine)
-        monkeypatch.setattr(encoders, "LatentSampler", OracleLatentSampler)
-        monkeypatch.setattr(torch.Tensor, "cuda", lambda t, *a, **k: t, raising=False)    # hard-coded .cuda() in the reference's prior loss
-
-        chain_at = 3
-        OracleEngine.replay_steps = list(draws[chain_at + 1:chain_at + T + 1])
-        with replay_draws(draws[:chain_at + 1] + draws[chain_at + T + 1:]) as queue, torch.no_grad(), contextlib.redirect_stdout(io.StringIO()):
-            out = model(batch, device="cpu", epoch=0)
-        assert not queue and not OracleEngine.replay_steps
-        OracleEngine.replay_steps = None
-        pred, name = out[0]
-        assert name == str(meta["name"]) and set(map(str, pred)) == set(expect)
-        for k, v in pred.items():
-            ref, got = expect[str(k)], v.numpy()
-            assert got.shape == ref.shape, k
-            if ref.dtype.kind in "iub":
-                assert np.array_equal(got, ref), k
-            else:
-                assert float(np.abs(got - ref).max()) <= 2e-5 * max(1.0, float(np.abs(ref).max())), k
-
-        # ---- fresh noise per decode() call of the REFERENCE (it passes no seed: anchor_gen.py:149-158) ----
-        pc, mean, logvar, valid = synth.make_latents(2, seed=5)
-        t_ = torch.from_numpy
-        ctx = [t_(pc), torch.cat([t_(mean), torch.exp(t_(logvar))], 1)]
-        seg = t_(synth.make_seg_mask(valid, 32))
-        idx = seg.long()[:, None, :].expand(-1, 3, -1)
-        anchors, variance = torch.gather(ctx[1][:, :3], 2, idx), torch.gather(ctx[1][:, 3:], 2, idx)
-        kw = dict(ctx=ctx, variance=variance, anchor_assignments=seg.to(torch.int32), valid_id=t_(valid), device="cpu")
-        OracleEngine.seeds_seen = []
         torch.manual_seed(11)
         with torch.no_grad():
-            a, b = model.decode(anchors, **kw)["pred"], model.decode(anchors, **kw)["pred"]
+            a, b = decode(), decode()
         seeds = list(OracleEngine.seeds_seen)
         assert len(seeds) == 2 * T and len(set(seeds[:T])) == 1 and len(set(seeds[T:])) == 1 and seeds[0] != seeds[T]   # one key per loop
         assert not torch.equal(a, b)
         torch.manual_seed(11)
         with torch.no_grad():
-            a2 = model.decode(anchors, **kw)["pred"]
+            a2 = decode()
         assert torch.equal(a, a2)
     finally:
-        OracleEngine.replay_steps = None
-        NETS._modules["TransformerNet"], DIFFUSIONS._modules["AnchoredDiffusion"] = saved[0], saved[1]
-        for k in ("pointnet2_ops", "pointnet2_ops.pointnet2_utils", "pointnet2_ops.pointnet2_modules"):
-            sys.modules[k] = saved[2][k]
+        OracleEngine.seeds_seen = []
 
 
 @pytest.mark.parametrize("tag,chain_at", [("gen_B2_K2_T10", 3), ("sample_B2_K2_T10", 4)])
@@ -377,69 +396,56 @@ def test_anchor_diff_ae_mirror_bookkeeping_on_oracle_backends(tag, chain_at, mon
             assert float(np.abs(got - ref).max()) <= 2e-5 * max(1.0, float(np.abs(ref).max())), k
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/python/difffacto"), reason="dev container only")
 @pytest.mark.parametrize("cfg_name", ["gen_chair.py", "gen_airplane.py", "gen_car.py", "gen_lamp.py", "train_chair_stage1.py", "train_chair_stage2.py"])
-def test_install_full_builds_the_mirror_from_the_unmodified_configs(cfg_name):
-    """INTEGRATION.md §2's "take the whole model" binding: after `install(full=True)` the REFERENCE's own `init_cfg` +
-    `build_from_cfg(cfg.model, MODELS)` (utils/registry.py:24-46) on an unmodified shipped config yields `networks.AnchorDiffAE` whose `state_dict`
-    has the reference model's keys and shapes, and a reference-made checkpoint loads `strict=True` — also through the shape-checking,
-    `strict=False` protocol of `Runner.load` (runner.py:505-520), with nothing dropped and nothing left unloaded."""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import contextlib
-    import io
-    import ref_import
+def test_install_full_builds_the_mirror_from_the_unmodified_configs(cfg_name, reference_registry):
+    """INTEGRATION.md §2's "take the whole model" binding: after `install(full=True)` the registry's
+    `build_from_cfg(cfg.model, MODELS)` (utils/registry.py:24-46) on the `cfg.model` of an unmodified shipped config (as the reference's
+    own `init_cfg` loads it, tests/golden/reference_modules.npz) yields `networks.AnchorDiffAE` whose `state_dict` has the reference
+    model's keys, shapes and dtypes, and a checkpoint of that layout loads `strict=True` — also through the shape-checking, `strict=False`
+    protocol of `Runner.load` (runner.py:505-520), with nothing dropped and nothing left unloaded."""
+    import copy
     import difffacto_amd
     from difffacto_amd import networks, encoders, modules
+    facts = _reference_facts()["configs"][cfg_name]
+    model_cfg_ref = facts["model_cfg"]
+    ref_sd = _checkpoint(facts["state_dict"])
+    from difffacto.utils.registry import MODELS, ENCODERS, build_from_cfg
+    import contextlib
+    import io
+    assert difffacto_amd.install(full=True) is True
     with contextlib.redirect_stdout(io.StringIO()):
-        ref_model, cfg = ref_import.build_reference_model(cfg_name)
-    assert type(ref_model).__module__.startswith("difffacto.")
-    ref_sd = ref_model.state_dict()
-    from difffacto.utils.registry import NETS, DIFFUSIONS, MODELS, ENCODERS, SAMPLERS, build_from_cfg
-    regs = (NETS, DIFFUSIONS, MODELS, ENCODERS, SAMPLERS)
-    saved = [dict(r._modules) for r in regs]
-    saved_mods = {k: sys.modules.get(k) for k in ("pointnet2_ops", "pointnet2_ops.pointnet2_utils", "pointnet2_ops.pointnet2_modules")}
-    try:
-        assert difffacto_amd.install(full=True) is True
-        with contextlib.redirect_stdout(io.StringIO()):
-            mine = build_from_cfg(cfg.model, MODELS)
-        assert type(mine) is networks.AnchorDiffAE
-        if cfg_name == "gen_chair.py":       # the dict the -m gpu composition tests build the mirror from IS this config's cfg.model
-            assert _plain(cfg.model) == {"type": "AnchorDiffAE", **model_cfg()}
-        if cfg_name == "train_chair_stage2.py":   # stage 2 = gen_chair's model up to these keys (the stage2_step golden was made on gen_chair's)
-            got, base = _plain(cfg.model), {"type": "AnchorDiffAE", **model_cfg()}
-            assert got.pop("save_dir") and got.pop("ret_interval") == 1 and "cimle_sample_num" not in got
-            assert got["encoder"]["part_aligner"].pop("noise_scale") == 50
-            base.pop("ret_interval"), base.pop("cimle_sample_num"), base["encoder"]["part_aligner"].pop("noise_scale")
-            assert got == base
-        assert type(mine.encoder) is encoders.PartEncoderForTransformerDecoder and type(mine.encoder.encoder) is encoders.PointNetV2
-        assert ENCODERS.get("PointNet2SSG") is encoders.PointNet2SSG and ENCODERS.get("PointNet2MSG") is encoders.PointNet2MSG   # (registered, unused by the configs)
-        assert type(mine.diffusion) is modules.AnchoredDiffusion and type(mine.diffusion.model) is modules.TransformerNet
-        my_sd = mine.state_dict()
-        assert list(my_sd) == list(ref_sd) or set(my_sd) == set(ref_sd)
-        assert len(ref_sd) == (473 if cfg_name == "train_chair_stage1.py" else 547)   # stage 1 has no part aligner (train_chair_stage1.py)
-        for k, v in ref_sd.items():
-            assert tuple(my_sd[k].shape) == tuple(v.shape) and my_sd[k].dtype == v.dtype, k
-        assert sum(p.numel() for p in mine.parameters()) == sum(p.numel() for p in ref_model.parameters())
-        mine.load_state_dict(ref_sd, strict=True)
-        for k, v in mine.state_dict().items():
-            assert torch.equal(v, ref_sd[k]), k
-        # Runner.load's protocol on a checkpoint written by DataParallel-wrapped training ("module." prefix stripped by the caller, runner.py:503)
-        with contextlib.redirect_stdout(io.StringIO()):
-            again = build_from_cfg(cfg.model, MODELS)
-        ckpt = {"module." + k: v.clone() for k, v in ref_sd.items()}
-        state = {k.replace("module.", ""): v for k, v in ckpt.items()}
-        target = again.state_dict()
-        dropped = [k for k in state if k not in target]
-        reshaped = [k for k in state if k in target and state[k].shape != target[k].shape]
-        missing = [k for k in target if k not in state]
-        assert not dropped and not reshaped and not missing
-        res = again.load_state_dict(state, strict=False)
-        assert not res.missing_keys and not res.unexpected_keys
-        assert all(torch.equal(v, ref_sd[k]) for k, v in again.state_dict().items())
-    finally:
-        for r, s in zip(regs, saved):
-            r._modules.clear()
-            r._modules.update(s)
-        for k, v in saved_mods.items():
-            if v is not None:
-                sys.modules[k] = v
+        mine = build_from_cfg(copy.deepcopy(model_cfg_ref), MODELS)
+    assert type(mine) is networks.AnchorDiffAE
+    if cfg_name == "gen_chair.py":       # the dict the -m gpu composition tests build the mirror from IS this config's cfg.model
+        assert _plain(model_cfg_ref) == {"type": "AnchorDiffAE", **model_cfg()}
+    if cfg_name == "train_chair_stage2.py":   # stage 2 = gen_chair's model up to these keys (the stage2_step golden was made on gen_chair's)
+        got, base = copy.deepcopy(model_cfg_ref), {"type": "AnchorDiffAE", **model_cfg()}
+        assert got.pop("save_dir") and got.pop("ret_interval") == 1 and "cimle_sample_num" not in got
+        assert got["encoder"]["part_aligner"].pop("noise_scale") == 50
+        base.pop("ret_interval"), base.pop("cimle_sample_num"), base["encoder"]["part_aligner"].pop("noise_scale")
+        assert got == base
+    assert type(mine.encoder) is encoders.PartEncoderForTransformerDecoder and type(mine.encoder.encoder) is encoders.PointNetV2
+    assert ENCODERS.get("PointNet2SSG") is encoders.PointNet2SSG and ENCODERS.get("PointNet2MSG") is encoders.PointNet2MSG   # (registered, unused by the configs)
+    assert type(mine.diffusion) is modules.AnchoredDiffusion and type(mine.diffusion.model) is modules.TransformerNet
+    my_sd = mine.state_dict()
+    assert list(my_sd) == list(ref_sd) or set(my_sd) == set(ref_sd)
+    assert len(ref_sd) == (473 if cfg_name == "train_chair_stage1.py" else 547)   # stage 1 has no part aligner (train_chair_stage1.py)
+    for k, v in ref_sd.items():
+        assert tuple(my_sd[k].shape) == tuple(v.shape) and my_sd[k].dtype == v.dtype, k
+    assert sum(p.numel() for p in mine.parameters()) == facts["n_params"]
+    mine.load_state_dict(ref_sd, strict=True)
+    for k, v in mine.state_dict().items():
+        assert torch.equal(v, ref_sd[k]), k
+    # Runner.load's protocol on a checkpoint written by DataParallel-wrapped training ("module." prefix stripped by the caller, runner.py:503)
+    with contextlib.redirect_stdout(io.StringIO()):
+        again = build_from_cfg(copy.deepcopy(model_cfg_ref), MODELS)
+    ckpt = {"module." + k: v.clone() for k, v in ref_sd.items()}
+    state = {k.replace("module.", ""): v for k, v in ckpt.items()}
+    target = again.state_dict()
+    dropped = [k for k in state if k not in target]
+    reshaped = [k for k in state if k in target and state[k].shape != target[k].shape]
+    missing = [k for k in target if k not in state]
+    assert not dropped and not reshaped and not missing
+    res = again.load_state_dict(state, strict=False)
+    assert not res.missing_keys and not res.unexpected_keys
+    assert all(torch.equal(v, ref_sd[k]) for k, v in again.state_dict().items())

@@ -4,7 +4,7 @@
 # Everything lands in gpurun_out/r05b; copy to profiles/ by hand (names r05b_*).
 O=gpurun_out/r05b
 mkdir -p $O
-python bench.py > $O/bench_T1000.json 2> $O/bench_T1000.err
+python bench.py --full > $O/bench_T1000.json 2> $O/bench_T1000.err
 python tools/bench_train.py --long > $O/bench_train.txt 2>&1
 python tools/bench_train.py --long --dropout 0.2 >> $O/bench_train.txt 2>&1
 tools/prof_train_dropout.sh $O/train_dropout > $O/kernel_stats_train_p0_p02.txt 2>&1

@@ -22,7 +22,7 @@ run --batch 128 --precision f32 --timesteps 100
 echo "# exact fp32, direct kernel (r02's path), T = 100"
 run --batch 128 --precision f32 --timesteps 100 --force-direct
 echo "# configs[2]: gen_airplane / gen_car / gen_lamp at T = 1000 (bench.py's sweep block: latents with the config's noise_scale)"
-python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-train-line 2>/dev/null | tail -1 | python -c '
+python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-train-line 2>/dev/null | tail -1 | python -c '
 import json, sys
 r = json.loads(sys.stdin.readline())
 for k, v in r["sweep"].items():
