@@ -110,6 +110,9 @@ SIGNATURES = {
     "dfx_part_aligner": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
     "dfx_sample_latents": (_I, [_P, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_int32), _I, _I, _I,
                                 _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dfx_compose_latents": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _I,
+                                 _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dfx_debug_latents_stub": (_I, [ctypes.POINTER(_P), _I, _I, _I, _I]),
     "dfx_aligner_train_workspace_bytes": (_SZ, [_I] * 7),
     "dfx_aligner_train_forward": (_I, [ctypes.POINTER(LatentWeights), _P, _SZ, _P, _P, _P, _P, _P, _I, _P]),
     "dfx_aligner_train_backward": (_I, [ctypes.POINTER(LatentWeights), _P, _SZ, _P, _P, _P, ctypes.POINTER(LatentWeights), _P, _I, _P]),

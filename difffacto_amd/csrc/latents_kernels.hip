@@ -164,6 +164,96 @@ __global__ void k_finish(const float *__restrict__ valid, const float *__restric
   }
 }
 
+// ---- editing front end (dfx_compose_latents): an explicit recipe instead of a sampling rule ----
+//
+// Part codes: code[r,:,j] = src[a] + (src[b] - src[a]) * alpha[r,j] in exactly that order (anchor_gen.py:244), or a plain copy
+// of src[a] when b < 0 (no arithmetic: -0 stays -0); then the aligner noise rows noise_o[r] = noise_src[nrow[r]] (nrow NULL =
+// identity).  amap / bmap / nrow are device copies of host-validated maps, so every index is in range.
+__global__ void k_compose(const float *__restrict__ src, const int32_t *__restrict__ amap, const int32_t *__restrict__ bmap,
+                          const float *__restrict__ alpha, const float *__restrict__ noise, const int32_t *__restrict__ nrow,
+                          float *__restrict__ code_o, float *__restrict__ noise_o, int R, int Z, int J, int ND) {
+#pragma clang fp contract(off)
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long nc = (long long)R * Z * J, nn = (long long)R * ND;
+  if (t < nc) {
+    const int j = t % J, c = (t / J) % Z, r = t / ((long long)J * Z);
+    const int a = amap[(size_t)r * J + j], b = bmap ? bmap[(size_t)r * J + j] : -1;
+    const float va = src[((size_t)a * Z + c) * J + j];
+    if (b < 0) {
+      code_o[t] = va;
+    } else {
+      const float vb = src[((size_t)b * Z + c) * J + j];
+      const float d = vb - va;
+      const float e = d * alpha[(size_t)r * J + j];
+      code_o[t] = va + e;
+    }
+  } else if (t < nc + nn) {
+    const long long u = t - nc;
+    const int d = u % ND, r = u / ND;
+    noise_o[u] = noise[(size_t)(nrow ? nrow[r] : r) * ND + d];
+  }
+}
+
+// Anchor edit after the aligner (interpolate_params, anchor_gen.py:369-370): mean <- mean * s, logvar <- logvar + l (either
+// factor may be NULL), then params = [mean | exp(logvar + lsv)] from the edited values, like k_split.
+__global__ void k_anchor_edit(float *__restrict__ mean, float *__restrict__ logvar, const float *__restrict__ ms,
+                              const float *__restrict__ ls, float *__restrict__ params, int R, int J, float lsv) {
+#pragma clang fp contract(off)
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= R * 6 * J) return;
+  const int j = t % J, c = (t / J) % 6, r = t / (6 * J);
+  if (c < 3) {
+    const size_t i = ((size_t)r * 3 + c) * J + j;
+    float m = mean[i];
+    if (ms) m = m * ms[i];
+    mean[i] = m;
+    if (params) params[t] = m;
+  } else {
+    const size_t i = ((size_t)r * 3 + (c - 3)) * J + j;
+    float l = logvar[i];
+    if (ls) l = l + ls[i];
+    logvar[i] = l;
+    if (params) params[t] = expf(l + lsv);
+  }
+}
+
+// k_finish with a choice of segment rule:
+//   0: ids = arange * valid + argmax(valid) * (1 - valid)    (part_encoders.py:1105-1108, the current rule)
+//   1: ids = arange * valid                                   (combine_latent_specific, anchor_gen.py:437)
+//   2: seg[r] = seg_src[srow[r]]                              (a segmentation taken from the batch)
+// The per-point gathers are k_finish's; the gather index is clamped to [0, J) so that a bad id in seg_src cannot read out
+// of bounds (the host layer rejects such ids before the call).
+__global__ void k_finish_mode(const float *__restrict__ valid, const float *__restrict__ mean,
+                              const float *__restrict__ logvar, int mode, const int32_t *__restrict__ seg_src,
+                              const int32_t *__restrict__ srow, int32_t *__restrict__ seg, float *__restrict__ mpp,
+                              float *__restrict__ lpp, int R, int J, int npoints, float lsv) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int per = npoints / J, n_eff = per * J;
+  if (t >= (long long)R * n_eff) return;
+  const int p = t % n_eff, r = t / n_eff, j = p / per;
+  int id;
+  if (mode == 2) {
+    id = seg_src[(size_t)srow[r] * npoints + p];
+  } else {
+    const float vj = valid[(size_t)r * J + j];
+    if (mode == 1) {
+      id = (int)((float)j * vj);
+    } else {
+      int first = 0;
+      float best = valid[(size_t)r * J];
+      for (int jj = 1; jj < J; ++jj)
+        if (valid[(size_t)r * J + jj] > best) best = valid[(size_t)r * J + jj], first = jj;
+      id = (int)((float)j * vj + (float)first * (1.f - vj));
+    }
+  }
+  if (seg) seg[(size_t)r * n_eff + p] = id;
+  const int g = id < 0 ? 0 : (id >= J ? J - 1 : id);
+  for (int c = 0; c < 3; ++c) {
+    if (mpp) mpp[((size_t)r * 3 + c) * n_eff + p] = mean[((size_t)r * 3 + c) * J + g];
+    if (lpp) lpp[((size_t)r * 3 + c) * n_eff + p] = logvar[((size_t)r * 3 + c) * J + g] + lsv;
+  }
+}
+
 inline int nblk(long long n, int bs = 256) { return (int)((n + bs - 1) / bs); }
 
 }  // namespace
@@ -444,6 +534,89 @@ int dfx_sample_latents(dfx_latents *h, const float *w_noise, const float *part_c
     k_finish<<<nblk((long long)R * npoints), 256, 0, st>>>(valid_out, mean, logvar, seg, mean_per_point, logvar_per_point, R,
                                                           J, npoints, h->lsv);
   return dfx::check_launch("sample_latents");
+}
+
+int dfx_compose_latents(dfx_latents *h, const float *code_src, int S, const int32_t *code_a, const int32_t *code_b,
+                        const float *alpha, const float *valid, const float *noise_src, int Sn, const int32_t *noise_row,
+                        const float *mean_scale, const float *logvar_shift, int seg_mode, const int32_t *seg_src, int Ss,
+                        const int32_t *seg_row, int R, int npoints, float *part_code, float *noise_out, float *mean,
+                        float *logvar, float *params, int32_t *seg, float *mean_per_point, float *logvar_per_point,
+                        dfx_stream_t stream) {
+  // every check runs on the host before the first HIP call (the index maps are host arrays)
+  DFX_REQUIRE(h && R >= 0 && S >= 0 && npoints >= 0, "compose_latents: bad sizes");
+  if (R == 0) return DFX_OK;
+  const int J = h->J, Z = h->Z;
+  DFX_REQUIRE(S >= 1 && code_src && code_a, "compose_latents: code_src / code_a required (S = %d)", S);
+  DFX_REQUIRE(valid && part_code && mean && logvar, "compose_latents: null pointer");
+  DFX_REQUIRE((code_b != nullptr) == (alpha != nullptr), "compose_latents: code_b and alpha are given together");
+  DFX_REQUIRE(npoints % J == 0, "compose_latents: npoints %d must be a multiple of n_class %d", npoints, J);
+  DFX_REQUIRE(seg_mode >= 0 && seg_mode <= 2, "compose_latents: seg_mode %d not in {0,1,2}", seg_mode);
+  for (long long i = 0; i < (long long)R * J; ++i) {
+    DFX_REQUIRE(code_a[i] >= 0 && code_a[i] < S, "compose_latents: code_a[%lld] = %d outside [0,%d)", i, code_a[i], S);
+    DFX_REQUIRE(!code_b || (code_b[i] >= -1 && code_b[i] < S), "compose_latents: code_b[%lld] = %d outside [-1,%d)", i,
+                code_b[i], S);
+  }
+  if (h->cimle) {
+    DFX_REQUIRE(noise_src && noise_out, "compose_latents: noise_src and noise_out required with cimle");
+    DFX_REQUIRE(Sn >= 1, "compose_latents: Sn = %d", Sn);
+    if (noise_row) {
+      for (int r = 0; r < R; ++r)
+        DFX_REQUIRE(noise_row[r] >= 0 && noise_row[r] < Sn, "compose_latents: noise_row[%d] = %d outside [0,%d)", r,
+                    noise_row[r], Sn);
+    } else {
+      DFX_REQUIRE(Sn >= R, "compose_latents: identity noise rows need Sn >= R (Sn = %d, R = %d)", Sn, R);
+    }
+  } else {
+    DFX_REQUIRE(!noise_src && !noise_row, "compose_latents: noise given but the aligner was built without cimle");
+  }
+  if (seg_mode == 2) {
+    DFX_REQUIRE(seg_src && seg_row && Ss >= 1, "compose_latents: seg_mode 2 needs seg_src and seg_row");
+    for (int r = 0; r < R; ++r)
+      DFX_REQUIRE(seg_row[r] >= 0 && seg_row[r] < Ss, "compose_latents: seg_row[%d] = %d outside [0,%d)", r, seg_row[r], Ss);
+  } else {
+    DFX_REQUIRE(!seg_src && !seg_row, "compose_latents: seg_src / seg_row are for seg_mode 2 only");
+  }
+  DFX_REQUIRE(h->wbuf, "compose_latents: the handle holds no weights");
+
+  hipStream_t st = dfx::as_stream(stream);
+  const size_t n_map = (size_t)R * J * 2 + 2 * (size_t)R;
+  const size_t map_floats = (n_map + 3) & ~(size_t)3;
+  if (int e = h->reserve(map_floats + aligner_ws_floats(h, R))) return e;
+  int32_t *amap = reinterpret_cast<int32_t *>(h->ws), *bmap = amap + (size_t)R * J, *nmap = bmap + (size_t)R * J,
+          *smap = nmap + R;
+  float *scratch = h->ws + map_floats;
+  // pageable host -> device: the call returns once the host arrays are staged, so the caller may free them afterwards
+  const size_t nb = (size_t)R * J * sizeof(int32_t);
+  hipError_t ce = hipMemcpyAsync(amap, code_a, nb, hipMemcpyHostToDevice, st);
+  if (ce == hipSuccess && code_b) ce = hipMemcpyAsync(bmap, code_b, nb, hipMemcpyHostToDevice, st);
+  if (ce == hipSuccess && noise_row) ce = hipMemcpyAsync(nmap, noise_row, R * sizeof(int32_t), hipMemcpyHostToDevice, st);
+  if (ce == hipSuccess && seg_row) ce = hipMemcpyAsync(smap, seg_row, R * sizeof(int32_t), hipMemcpyHostToDevice, st);
+  if (ce != hipSuccess) return dfx::set_error(DFX_ERR_HIP, "compose_latents: map copy: %s", hipGetErrorString(ce));
+
+  const int ND = h->cimle ? h->nd : 0;
+  const long long ncomp = (long long)R * Z * J + (long long)R * ND;
+  k_compose<<<nblk(ncomp), 256, 0, st>>>(code_src, amap, code_b ? bmap : nullptr, alpha, noise_src, noise_row ? nmap : nullptr,
+                                         part_code, noise_out, R, Z, J, ND);
+  const bool edit = mean_scale || logvar_shift;
+  if (int e = run_aligner(h, part_code, valid, h->cimle ? noise_out : nullptr, mean, logvar, edit ? nullptr : params, R,
+                          scratch, st))
+    return e;
+  if (edit)
+    k_anchor_edit<<<nblk((long long)R * 6 * J), 256, 0, st>>>(mean, logvar, mean_scale, logvar_shift, params, R, J, h->lsv);
+  if (npoints > 0 && (seg || mean_per_point || logvar_per_point))
+    k_finish_mode<<<nblk((long long)R * npoints), 256, 0, st>>>(valid, mean, logvar, seg_mode, seg_src, seg_row ? smap : nullptr,
+                                                               seg, mean_per_point, logvar_per_point, R, J, npoints, h->lsv);
+  return dfx::check_launch("compose_latents");
+}
+
+// A handle with the sizes of a real one and no device memory: lets the argument checks of dfx_compose_latents run on a
+// machine without a GPU.  Free it with dfx_latents_destroy.
+int dfx_debug_latents_stub(dfx_latents **out, int n_class, int zdim, int cimle, int noise_dim) {
+  DFX_REQUIRE(out && n_class >= 1 && n_class <= 8 && zdim > 0, "latents_stub: bad argument");
+  dfx_latents *h = new dfx_latents();
+  h->J = n_class, h->Z = zdim, h->cimle = cimle ? 1 : 0, h->nd = noise_dim;
+  *out = h;
+  return DFX_OK;
 }
 
 }  // extern "C"

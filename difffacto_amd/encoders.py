@@ -547,6 +547,16 @@ class PartEncoderForTransformerDecoder(nn.Module):
         return (ctx, out["mean_per_point"], out["logvar_per_point"], out["seg_mask"], out["valid_id"],
                 [out["part_code"], out["mean"], out["logvar"], out["noise"]])
 
+    @torch.no_grad()
+    def compose_latents(self, code_src, code_a, valid, sample_points, **recipe):
+        """The editing counterpart of ``sample_latents``: rows built from an explicit recipe over the source codes (one
+        ``dfx_compose_latents`` call: code lerp / swap, aligner, anchor edit, seg ids, per-point gathers; the keyword arguments
+        are ``LatentSampler.compose_latents``').  Returns the same 6-tuple, so ``decode`` takes it unchanged."""
+        out = self.sampler().compose_latents(code_src, code_a, valid, npoints=sample_points, **recipe)
+        ctx = [out["part_code"], out["params"]]
+        return (ctx, out["mean_per_point"], out["logvar_per_point"], out["seg_mask"], out["valid_id"],
+                [out["part_code"], out["mean"], out["logvar"], out["noise"]])
+
 
 @torch.no_grad()
 def generate(encoder, diffusion, sample_num, npoints, valid_id=None, fixed_id=None, K=10, epoch=0, seed=None,

@@ -154,3 +154,48 @@ class LatentSampler:
                 _ffi.ptr(out["mean_per_point"]), _ffi.ptr(out["logvar_per_point"]), _ffi.current_stream())
         _ffi.check(rc, "dfx_sample_latents")
         return out
+
+    def compose_latents(self, code_src, code_a, valid, code_b=None, alpha=None, noise_src=None, noise_row=None, mean_scale=None,
+                        logvar_shift=None, seg_mode=0, seg_src=None, seg_row=None, npoints=2048):
+        """The editing front end (``dfx_compose_latents``): ``sample_latents``' dict from an explicit recipe over S source codes.
+
+        code_src (S,zdim,J); code_a / code_b (R,J) source rows per output row and part (host ints; code_b -1 or None = copy code_a)
+        with alpha (R,J) the lerp weights; valid (R,J) the final key mask; noise_src (Sn,noise_dim) + noise_row (R,) (None =
+        identity); mean_scale / logvar_shift (R,3,J) anchor edits after the aligner; seg_mode 0 / 1 / 2 (seg_src (Ss,npoints)
+        ids + seg_row (R,) for mode 2).  Returns the keys of ``sample_latents``; ``valid_id`` is ``valid``."""
+        host = lambda a: None if a is None else np.ascontiguousarray(
+            (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(np.int32))
+        code_a, code_b, noise_row, seg_row = map(host, (code_a, code_b, noise_row, seg_row))
+        code_src, valid, alpha, noise_src, mean_scale, logvar_shift = map(
+            self._f, (code_src, valid, alpha, noise_src, mean_scale, logvar_shift))
+        J, Z = self.n_class, self.zdim
+        S, R = code_src.shape[0], code_a.shape[0]
+        assert tuple(code_src.shape) == (S, Z, J) and code_a.shape == (R, J) and tuple(valid.shape) == (R, J)
+        for t, shape in ((code_b, (R, J)), (noise_row, (R,)), (seg_row, (R,))):
+            assert t is None or t.shape == shape
+        for t in (alpha, mean_scale, logvar_shift):
+            assert t is None or t.numel() == R * J * (1 if t is alpha else 3)
+        Sn = 0 if noise_src is None else noise_src.shape[0]
+        if noise_src is not None:
+            assert tuple(noise_src.shape) == (Sn, self.noise_dim)
+        Ss = 0
+        if seg_src is not None:
+            seg_src = seg_src.detach().to(device=self.device, dtype=torch.int32).contiguous()
+            Ss = seg_src.shape[0]
+            assert tuple(seg_src.shape) == (Ss, npoints)
+            if bool(((seg_src < 0) | (seg_src >= J)).any()):
+                raise ValueError(f"compose_latents: segment ids outside [0, {J})")
+        e = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=self.device)
+        out = {"part_code": e(R, Z, J), "valid_id": valid, "noise": e(R, self.noise_dim) if self.cimle else None,
+               "mean": e(R, 3, J), "logvar": e(R, 3, J), "params": e(R, 6, J), "seg_mask": e(R, npoints, dtype=torch.int32),
+               "mean_per_point": e(R, 3, npoints), "logvar_per_point": e(R, 3, npoints)}
+        hp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        with torch.cuda.device(self.device):
+            rc = _ffi.lib().dfx_compose_latents(
+                self._h, _ffi.ptr(code_src), S, hp(code_a), hp(code_b), _ffi.ptr(alpha), _ffi.ptr(valid), _ffi.ptr(noise_src), Sn,
+                hp(noise_row), _ffi.ptr(mean_scale), _ffi.ptr(logvar_shift), int(seg_mode), _ffi.ptr(seg_src), Ss, hp(seg_row), R,
+                int(npoints), _ffi.ptr(out["part_code"]), _ffi.ptr(out["noise"]), _ffi.ptr(out["mean"]), _ffi.ptr(out["logvar"]),
+                _ffi.ptr(out["params"]), _ffi.ptr(out["seg_mask"]), _ffi.ptr(out["mean_per_point"]),
+                _ffi.ptr(out["logvar_per_point"]), _ffi.current_stream())
+        _ffi.check(rc, "dfx_compose_latents")
+        return out

@@ -6,6 +6,9 @@ dicts from ``forward``:
 * eval + ``gen``            -> ``[(dict, "gen_fixed0000")]``  (anchor_gen.py:1034-1084: encoder pass, sample_latents, decode, K-fold
                                ``"{k}_sample {i}"`` / ``"sample prior {i}"`` keys under cIMLE)
 * eval, not ``gen`` (cIMLE) -> ``[(dict, "sample")]``         (:1085-1134: sample_noise, encode, decode — the reconstruction mode)
+* eval + ``interpolate`` / ``combine`` / ``drift_anchors`` -> ``[(dict, "interpolate" / "mixing" / "interpolate_params")]`` (:1027-1032:
+                               the editing modes, ``interpolate_latent`` / ``combine_latent`` / ``interpolate_params``; ``combine_latent_specific``
+                               is the mixing runner's entry, runner/mixing_runner.py:89)
 * train()                   -> loss dict                      (:1002-1021: prior_loss / fit_loss / mse_loss; stage 1 natively, see
                                ``training.stage1_losses``)
 
@@ -15,6 +18,8 @@ K-fold regrouping, which random draw happens where).  Random draws happen at the
 that is drawn from torch's generator at the point where the reference draws x_T (``engine.resolve_seed``).
 Options outside the shipped ``configs/gen_*.py`` / ``train_*.py`` raise ``NotImplementedError``.
 """
+import math
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -59,9 +64,8 @@ class AnchorDiffAE(nn.Module):
                  reg_loss_weight=1.0, pretrain_prior=False, train_language=False, language_encoder=None, clip_weight=1.0,
                  triplet_weight=1.0, triplet_thresh=0.1, precision="bf16"):
         super().__init__()
-        for name, val in (("zero_anchors", zero_anchors), ("use_input", use_input), ("interpolate", interpolate), ("combine", combine),
-                          ("drift_anchors", drift_anchors), ("save_weights", save_weights), ("pretrain_prior", pretrain_prior),
-                          ("train_language", train_language), ("forward_sample", forward_sample)):
+        for name, val in (("zero_anchors", zero_anchors), ("use_input", use_input), ("save_weights", save_weights),
+                          ("pretrain_prior", pretrain_prior), ("train_language", train_language), ("forward_sample", forward_sample)):
             if val:
                 _unsupported(f"{name}=True")
         if isinstance(encoder, nn.Module):
@@ -86,6 +90,7 @@ class AnchorDiffAE(nn.Module):
         self.diffusion_loss_weight, self.sample_noise_num, self.cimle, self.cimle_sample_num = \
             diffusion_loss_weight, sample_noise_num, cimle, cimle_sample_num
         self.fix_part_ids, self.gen = fix_part_ids, gen
+        self.interpolate, self.interpolate_part_id, self.combine, self.drift_anchors = interpolate, interpolate_part_id, combine, drift_anchors
         self.num_timesteps, self.num_anchors, self.npoints = int(num_timesteps), num_anchors, npoints
         # detach_anchor=False raises in the training forward (stage1_losses); detach_variance detaches a tensor the reference no longer reads
         # (anchor_gen.py:1013-1014 vs :1002), and learn_var / global_shift / global_scale / vertical_only are stored and never read by the
@@ -145,6 +150,12 @@ class AnchorDiffAE(nn.Module):
         with torch.no_grad():
             # the reference runs the encoder on every val batch, gen branch included (:995): its reparameterisation draw comes first
             ctx, mean_pp, logvar_pp, _flag, _losses, _latents = self.encoder(pcds, device, epoch=epoch)
+            if self.interpolate:                                                               # :1027-1032, in this order
+                return [(self.interpolate_latent(device, pcds), "interpolate")]
+            if self.combine:
+                return [(self.combine_latent(pcds, device), "mixing")]
+            if self.drift_anchors:
+                return [(self.interpolate_params(device, pcds), "interpolate_params")]
             h = self.cimle_sample_num
             if self.gen:
                 fixed_id = [0] * self.num_anchors
@@ -210,3 +221,186 @@ class AnchorDiffAE(nn.Module):
                          "token": pcds["token"], "present": valid_id, "shift": pcds["shift"], "scale": pcds["scale"]})
             pred = {k: v.detach().cpu() if isinstance(v, torch.Tensor) else v for k, v in pred.items()}
             return [(pred, "sample")]
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # Editing modes (anchor_gen.py:206-532).  Each is ONE dfx_compose_latents call (the latent rows of every edit: code lerp /
+    # part swap, aligner, anchor edit, seg ids, per-point gathers) and ONE persistent chain launch over all B*K rows (the
+    # reference decodes in chunks of 50 rows; the chunking changes nothing but the launch count).  Random draws happen at the
+    # reference's sites in its order, torch.randperm included.  The caller's batch is never written to: the reference's
+    # in-place writes into pcds["present"] (:231, :494, which reach the caller only when the batch already lives on `device`)
+    # are made on a copy, and its permutation of pcds["part_shift"] (:495; the aligner never reads it) is left out — the
+    # returned values are the same.
+    def _edit_batch(self, pcds, device):
+        if not self.cimle:
+            # the reference crashes here without cIMLE (noise = None, then None.repeat_interleave: :250, :366)
+            _unsupported("the interpolate / drift_anchors editing modes without cimle (the reference's own methods fail there)")
+        ref = pcds["ref"].to(device)
+        inp = pcds["input"].to(device)
+        ref_seg_mask = pcds["ref_seg_mask"].to(device)
+        seg_flag = pcds["attn_map"].to(device)
+        valid_id = pcds["present"].to(device).to(torch.float32).clone()
+        return ref, inp, ref_seg_mask, seg_flag, valid_id
+
+    def _part_code(self, inp, seg_flag):
+        m, lv = self.encoder.get_part_code(inp, seg_flag)
+        return self.encoder._reparameterize(m, lv) if self.encoder.gen else m.transpose(1, 2)
+
+    def _decode_rows(self, ctx, seg, valid, device):
+        return self.decode(None, ctx=ctx, device=device, variance=None, anchor_assignments=seg, valid_id=valid)
+
+    @torch.no_grad()
+    def interpolate_latent(self, device, pcds):
+        """anchor_gen.py:206-305: part ``interpolate_part_id`` of every shape lerped towards that of a random partner
+        (``torch.randperm``) in K = 10 steps, ``dx = linspace(0, 1)`` (both hard-coded in the reference, mirrored).  ``gen``:
+        fresh part codes from the flows, the interpolated part marked present, seg ids by rule 0; else the encoded codes
+        (reparameterised) and the batch's ``ref_seg_mask`` (seg rule 2).  The ``priors`` draw (:265) is made and dropped like
+        the reference's.  Keys: "interpolate sample {i}" (on the CPU, like the reference's chunked outputs), "pred",
+        "pred_seg_mask", "ref_seg_mask", "input_ref", "permuted_ref", "permuted_ref_seg_mask", "shift", "scale".  The
+        per-point log-variances carry ``log_scale_var`` (0 in every shipped config; the reference leaves it out here, :255) —
+        they only feed the dropped priors."""
+        from . import editing
+        ref, inp, ref_seg_mask, seg_flag, valid_id = self._edit_batch(pcds, device)
+        B, J, pid = inp.shape[0], self.num_anchors, self.interpolate_part_id
+        noise, _ = self.encoder.sample_noise(pcds, device, 1)
+        noise = noise.squeeze(1)
+        seg_kw = {}
+        if self.gen:
+            w = torch.randn(B, self.encoder.zdim, J).to(device)                              # :224 (scaled by sqrt(prior_var) in-kernel)
+            if self.encoder.use_flow:
+                part_code = self.encoder.sampler().flow_reverse(w)
+            else:
+                part_code = w * math.sqrt(self.encoder.prior_var)
+            valid_id[..., pid] = 1.                                                          # :231
+        else:
+            part_code = self._part_code(inp, seg_flag)
+            Nr = ref_seg_mask.shape[1]
+            pred_seg_mask = ref_seg_mask.reshape(-1, Nr, 1).expand(-1, -1, self.npoints // Nr).reshape(-1, self.npoints)   # :237
+        K = 10
+        dx = torch.linspace(0, 1, steps=K)
+        perm = torch.randperm(B)
+        rows = editing.repeat_rows(B, K)
+        code_a, code_b = editing.interpolation_recipe(B, K, J, pid, perm.numpy())
+        if not self.gen:
+            seg_kw = {"seg_mode": 2, "seg_src": pred_seg_mask, "seg_row": rows}
+        ctx, mean_pp, logvar_pp, seg, valid, _lat = self.encoder.compose_latents(
+            part_code, code_a, valid_id.repeat_interleave(K, dim=0), self.npoints, code_b=code_b,
+            alpha=editing.interpolation_alpha(B, K, J, pid, dx).to(device), noise_src=noise, noise_row=rows, **seg_kw)
+        if self.gen:
+            pred_seg_mask = seg.reshape(B, K, -1)[:, 0].to(torch.float32)                   # :232-233 (float ids, like the reference)
+        torch.randn_like(logvar_pp)                                                          # :265 priors, never returned
+        _pred = self._decode_rows(ctx, seg, valid, device)
+        pred = _pred["pred"].cpu().reshape(B, K, self.npoints, 3)
+        out = {f"interpolate sample {i}": pred[:, i] for i in range(K)}
+        out.update({"pred_seg_mask": pred_seg_mask[:B], "ref_seg_mask": ref_seg_mask, "pred": out["interpolate sample 0"], "input_ref": ref,
+                    "permuted_ref": ref[perm.to(ref.device)], "permuted_ref_seg_mask": ref_seg_mask[perm.to(ref.device)],
+                    "shift": pcds["shift"], "scale": pcds["scale"]})
+        return out
+
+    @torch.no_grad()
+    def interpolate_params(self, device, pcds):
+        """anchor_gen.py:338-410 (``drift_anchors=True``): every shape K = ``cimle_sample_num`` times with the y anchors of parts 0
+        and 2 scaled by sqrt(dx) and their log-variances shifted by log(dx), dx = linspace(1, 5, K) (the reference's constants,
+        mirrored); seg ids from the batch (rule 2, so ``ref`` must have ``npoints`` points).  The priors keep the reference's
+        formula, noise times the VARIANCE (not the standard deviation, :385).  Keys: "interpolate sample {i}",
+        "interpolate sample prior {i}", "pred", "pred_seg_mask", "ref_seg_mask", "seg_mask", "input_ref", "shift", "scale"."""
+        from . import editing
+        ref, inp, ref_seg_mask, seg_flag, valid_id = self._edit_batch(pcds, device)
+        B, J = inp.shape[0], self.num_anchors
+        if ref_seg_mask.shape[1] != self.npoints:
+            _unsupported("interpolate_params with a reference cloud of other than npoints points (the reference's reshape fails, :395)")
+        noise, _ = self.encoder.sample_noise(pcds, device, 1)
+        noise = noise.squeeze(1)
+        part_code = self._part_code(inp, seg_flag)
+        K = self.cimle_sample_num
+        scale, shift = editing.drift_factors(B, K, J, torch.linspace(1, 5, steps=K))
+        rows = editing.repeat_rows(B, K)
+        ctx, mean_pp, logvar_pp, seg, valid, _lat = self.encoder.compose_latents(
+            part_code, np.repeat(rows[:, None], J, 1), valid_id.repeat_interleave(K, dim=0), self.npoints, noise_src=noise, noise_row=rows,
+            mean_scale=scale.to(device), logvar_shift=shift.to(device), seg_mode=2, seg_src=ref_seg_mask, seg_row=rows)
+        var_pp = torch.exp(logvar_pp)
+        priors = torch.randn(B * K, self.npoints, 3).to(device) * var_pp.transpose(1, 2) + mean_pp.transpose(1, 2)   # :385
+        _pred = self._decode_rows(ctx, seg, valid, device)
+        pred = _pred["pred"].reshape(B, K, self.npoints, 3)
+        priors = priors.reshape(B, K, self.npoints, 3)
+        out = {f"interpolate sample {i}": pred[:, i] for i in range(K)}
+        out.update({f"interpolate sample prior {i}": priors[:, i] for i in range(K)})
+        out.update({"pred_seg_mask": ref_seg_mask, "ref_seg_mask": ref_seg_mask, "seg_mask": ref_seg_mask, "pred": out["interpolate sample 0"],
+                    "input_ref": ref, "shift": pcds["shift"], "scale": pcds["scale"]})
+        return out
+
+    @torch.no_grad()
+    def combine_latent(self, pcds, device):
+        """anchor_gen.py:457-532 (``combine=True``): part i of every shape taken from shape ``perm_i[b]`` (one ``torch.randperm``
+        per part), present when both shapes have it (:494), K = ``cimle_sample_num`` aligner noises per shape from
+        ``sample_noise``, seg ids by rule 0.  Keys: "{k}_sample_{i}" for every key of decode's dict, "pred", "pred_seg_mask",
+        "input_ref", "ref_seg_mask", "input_ref{i}", "ref_seg_mask{i}", "shift", "scale"."""
+        from . import editing
+        ref = pcds["ref"].to(device)
+        inp = pcds["input"].to(device)
+        seg_flag = pcds["attn_map"].to(device)
+        valid_id = pcds["present"].to(device).to(torch.float32).clone()
+        B, J = inp.shape[0], self.num_anchors
+        part_code = self._part_code(inp, seg_flag)
+        if self.cimle:
+            K = self.cimle_sample_num
+            noise, _ = self.encoder.sample_noise(pcds, device, K)
+            noise = noise.reshape(B * K, -1)
+        else:
+            K, noise = 1, None
+        perms = [torch.randperm(B) for _ in range(J)]                                         # :489-496
+        valid = editing.mixing_valid(valid_id, [p.to(device) for p in perms])
+        ctx, mean_pp, logvar_pp, seg, valid, _lat = self.encoder.compose_latents(
+            part_code, editing.mixing_recipe([p.numpy() for p in perms], K), valid.repeat_interleave(K, dim=0), self.npoints, noise_src=noise)
+        _pred = self._decode_rows(ctx, seg, valid, device)
+        pred = {}
+        for k, v in _pred.items():
+            v = _fold(v, K)
+            for i in range(K):
+                pred[f"{k}_sample_{i}"] = v[:, i]
+        pred["pred"] = pred["pred_sample_0"]
+        pred["pred_seg_mask"] = seg.reshape(B, K, -1)[:, 0]
+        pred["input_ref"] = ref
+        pred["ref_seg_mask"] = pcds["ref_seg_mask"]
+        for i in range(J):
+            pred[f"input_ref{i}"] = ref[perms[i].to(ref.device)]
+            pred[f"ref_seg_mask{i}"] = pcds["ref_seg_mask"][perms[i]]
+        pred["shift"], pred["scale"] = pcds["shift"], pcds["scale"]
+        return pred
+
+    @torch.no_grad()
+    def combine_latent_specific(self, inputs, device):
+        """anchor_gen.py:412-455, the mixing runner's entry (runner/mixing_runner.py:89): ``inputs`` = one (n_i, 3) point set per
+        part, an all-zero set = the part is absent.  The present sets are encoded as ONE shape (PointNetV2 means, no
+        reparameterisation), K = ``cimle_sample_num`` aligner noises, seg ids by rule 1 (arange * valid: absent parts map to
+        part 0).  Keys: "{k}_sample_{i}", "pred", "input", "pred_seg_mask", "seg_mask", "shift", "scale"."""
+        assert len(inputs) == self.num_anchors
+        J = self.num_anchors
+        present = [bool(torch.any(inp != 0)) for inp in inputs]
+        valid_id = torch.tensor([1 if p else 0 for p in present]).to(device).unsqueeze(0)
+        eye = torch.eye(J)
+        seg_flag = torch.cat([eye[i].reshape(1, J).repeat_interleave(inp.shape[0], dim=0) for i, inp in enumerate(inputs) if present[i]],
+                             dim=0).unsqueeze(0).to(device)
+        inp = torch.cat([x for x, p in zip(inputs, present) if p], dim=0).unsqueeze(0).to(device)
+        m, _lv = self.encoder.get_part_code(inp, seg_flag)
+        part_code = m.transpose(1, 2)
+        if self.cimle:
+            K = self.cimle_sample_num
+            noise = torch.randn(K, self.encoder.part_aligner.noise_dim).to(device)            # :426
+        else:
+            K, noise = 1, None
+        ctx, mean_pp, logvar_pp, seg, valid, _lat = self.encoder.compose_latents(
+            part_code, np.zeros((K, J), np.int32), valid_id.repeat_interleave(K, dim=0).to(torch.float32), self.npoints, noise_src=noise,
+            seg_mode=1)
+        _pred = self._decode_rows(ctx, seg, valid, device)
+        pred = {}
+        for k, v in _pred.items():
+            v = _fold(v, K)
+            for i in range(K):
+                pred[f"{k}_sample_{i}"] = v[:, i]
+        pred["pred"] = pred["pred_sample_0"]
+        pred["input"] = inp
+        pred["pred_seg_mask"] = seg
+        pred["seg_mask"] = torch.argmax(seg_flag, dim=2)
+        pred["shift"] = torch.zeros(1, 1, 3, device=device)
+        pred["scale"] = torch.ones(1, 1, 1, device=device)
+        return pred

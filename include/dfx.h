@@ -302,6 +302,29 @@ int dfx_sample_latents(dfx_latents *h, const float *w_noise, const float *part_c
                        float *valid_out, float *noise_out, float *mean, float *logvar, float *params, int32_t *seg,
                        float *mean_per_point, float *logvar_per_point, dfx_stream_t stream);
 
+/* Editing front end (shape interpolation, part mixing, anchor drift; anchor_gen.py:206-532): dfx_sample_latents' outputs from an
+ * explicit recipe instead of a sampling rule, R output rows over S source shapes.
+ *   code_src (S,zdim,n_class) device: source part codes
+ *   code_a, code_b: HOST int32 (R,n_class): source rows per output row and part.  code_b NULL (then alpha NULL too) or an entry
+ *     -1 = copy src[a] with no arithmetic (-0 stays -0); else code[r,:,j] = src[a] + (src[b] - src[a]) * alpha[r,j], three
+ *     separately rounded fp32 operations (anchor_gen.py:244): the bits of torch's three elementwise ops.
+ *   alpha (R,n_class) device or NULL; valid (R,n_class) device: the final key mask of every row (built by the caller)
+ *   noise_src (Sn,noise_dim) device + noise_row HOST int32 (R) or NULL = identity (then Sn >= R); both NULL iff !cimle
+ *   mean_scale / logvar_shift (R,3,n_class) device or NULL: after the aligner, mean <- mean * s and logvar <- logvar + l, before
+ *     params and the per-point gathers are written (interpolate_params, anchor_gen.py:369-370)
+ *   seg_mode 0: ids = arange*valid + argmax(valid)*(1-valid) (as dfx_sample_latents); 1: ids = arange*valid
+ *     (combine_latent_specific, :437); 2: seg[r] = seg_src[seg_row[r]] with seg_src (Ss,npoints) device int32 ids in
+ *     [0,n_class) and seg_row HOST int32 (R) (both NULL for modes 0 / 1)
+ * outputs as dfx_sample_latents (no valid_out: the caller's `valid` is the mask): part_code (R,zdim,n_class), noise_out
+ * (R,noise_dim), mean / logvar (R,3,n_class), params (R,6,n_class), seg (R,npoints), mean_per_point / logvar_per_point
+ * (R,3,npoints).  Every argument, index maps included, is checked before the first HIP call. */
+int dfx_compose_latents(dfx_latents *h, const float *code_src, int S, const int32_t *code_a, const int32_t *code_b,
+                        const float *alpha, const float *valid, const float *noise_src, int Sn, const int32_t *noise_row,
+                        const float *mean_scale, const float *logvar_shift, int seg_mode, const int32_t *seg_src, int Ss,
+                        const int32_t *seg_row, int R, int npoints, float *part_code, float *noise_out, float *mean,
+                        float *logvar, float *params, int32_t *seg, float *mean_per_point, float *logvar_per_point,
+                        dfx_stream_t stream);
+
 /* Training forward / backward of the part aligner (stage 2: configs/train_*_stage2.py and gen_*.py with train_aligner; replaces torch autograd through
  * PartAlignerTransformer, part_encoders.py:88-143, for the shipped options: cimle with cond_noise_type 0, class_cond + add_class_cond, single_attn,
  * mask_out_unreferenced_code, dropout 0).  Exact fp32, no atomics (aligner_train.hip).  `w` holds the parameter pointers (flow fields unused), `grads` the

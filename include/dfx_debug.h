@@ -76,6 +76,9 @@ void dfx_debug_pipe_waves(int nw);
 /* Slot-boundary clock stamps of two wavefronts of workgroup 0 (device buffer of 2*capacity uint64; NULL = off).
  * Only effective in a library built with -DDFX_TRACE (tools/experiments/trace_slots.py builds one). */
 void dfx_debug_trace(void *device_buf, int capacity);
+/* A dfx_latents handle with n_class / zdim / cimle / noise_dim set and no device memory (free with dfx_latents_destroy): the argument
+ * checks of dfx_compose_latents run against it on a machine without a GPU; a call that passes them fails with "holds no weights". */
+int dfx_debug_latents_stub(dfx_latents **out, int n_class, int zdim, int cimle, int noise_dim);
 
 #ifdef __cplusplus
 }
