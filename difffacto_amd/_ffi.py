@@ -90,6 +90,11 @@ SIGNATURES = {
     "dfx_three_interpolate_grad_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "dfx_chamfer_forward_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "dfx_chamfer_backward_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "dfx_part_snapping_f32": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
+    "dfx_part_boxes_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _D, _P, _P, _P]),
+    "dfx_part_clouds_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "dfx_part_box_pairwise_f32": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _U64, ctypes.c_longlong, _P, _P, _P]),
+    "dfx_debug_part_box_units": (_I, [_U64, ctypes.c_longlong, _I, _I, _P, _P]),
     "dfx_denoiser_create": (_I, [ctypes.POINTER(_P), ctypes.POINTER(DenoiserWeights), _I, _D, _D, _I, _P]),
     "dfx_denoiser_destroy": (None, [_P]),
     "dfx_denoiser_num_timesteps": (_I, [_P]),

@@ -242,6 +242,47 @@ int dfx_chamfer_backward_f32(const float *xyz1, const float *xyz2, const int32_t
                              int B, int N, int M, dfx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Part-level generation metrics — the gen_part evaluation of python/difffacto/datasets/evaluation_utils.py
+ * (compute_snapping_metric :385-421, the box step of compute_bbox_metric :287-333 and its part_l2 / part_miou /
+ * part_chamfer distances :23-82, the extraction step of compute_part_metric :423-486).  part_metrics.hip.
+ * xyz (B,N,3) fp32, labels (B,N) int32 with 1 <= N <= 8192; a label outside [0,C) belongs to no part.  Every argument is
+ * checked on the host before the first HIP call.
+ * ------------------------------------------------------------------------------------------ */
+
+/* Snapping distance of P part pairs per shape (k = 50 in the reference).  pairs: HOST int32 (P,2) = (a,b) in [0,C), 1 <= P <= 64.
+ * Per (shape, pair): d(p,q) = (dx*dx + dy*dy) + dz*dz, no contraction (torch's CPU sum of squares); every point of part a gets its
+ * minimum d to part b and vice versa; the k points of each part with the smallest minima are kept (equal minima: the lower point
+ * index wins; torch's topk leaves the order of ties unspecified); dist = Chamfer of the two k-point sets (mean nearest-neighbour d in
+ * each direction, summed).  Outputs dist (B,P) fp32, status (B,P) int32: 0 = part a or b has no point (dist NaN), 1 = computed,
+ * 2 = a present part has fewer than k points (dist NaN; the reference's topk raises). */
+int dfx_part_snapping_f32(const float *xyz, const int32_t *labels, int B, int N, int C, const int32_t *pairs, int P, int k,
+                          float *dist, int32_t *status, dfx_stream_t stream);
+
+/* Part bounding boxes.  normalize != 0: the shape is first mapped to (x - (min+max)/2) / (largest extent / 2).  Per part with
+ * count > min_points (>= 0): lo = quantile(1 - q), hi = quantile(q) per axis with torch.quantile's linear interpolation (q and 1 - q
+ * rounded to fp32 from double; pos = q (n-1), lerp between the floor and ceil order statistics); q = 1 gives the exact min / max.
+ * q in [0,1].  Outputs boxes (B,C,2,3) = (lo, hi) (NaN for parts not kept), count (B,C) = points per part. */
+int dfx_part_boxes_f32(const float *xyz, const int32_t *labels, int B, int N, int C, int normalize, int min_points, double q,
+                       float *boxes, int32_t *count, dfx_stream_t stream);
+
+/* Part clouds.  Per part with count n > min_points: point p < n_out is part point (p mod n) in index order (the reference's "repeat
+ * until >= n_out, truncate"), then per axis x <- (x - (min+max)/2) / ((max-min)/2) over those n_out points.  mask[p] = p < n.
+ * 1 <= n_out <= 4096 (512 in the reference).  Outputs clouds (B,C,n_out,3), masks (B,C,n_out) (zeros for parts not kept), count (B,C). */
+int dfx_part_clouds_f32(const float *xyz, const int32_t *labels, int B, int N, int C, int min_points, int n_out, float *clouds,
+                        float *masks, int32_t *count, dfx_stream_t stream);
+
+/* Box-set distance matrix D (Ma,Mb), D[i,j] = dist(A_i, B_j): boxes (M,C,2,3) as dfx_part_boxes_f32 writes them, present (M,C) int32
+ * (nonzero = the part has a box).  Per pair the classes are walked in order: presence differs -> +inf; both absent -> skipped;
+ * else a term; D = fp32 mean of the terms (NaN without any).  metric 0 = l2 (mean squared difference of [(hi-lo)/2, (hi+lo)/2]),
+ * 1 = iou (1 - mean IoU in double, boxes read as the reference's get_3d_box at heading 0 reads (l,w,h): x-extent dx, y-extent dz,
+ * z-extent dy), 2 = chamfer (512 points uniform in each box, u (hi-lo) + lo, then Chamfer-L2).  Chamfer draws: units (P,C,2,512,3)
+ * device, P = Ma*Mb local pairs i*Mb + j, side 0 = A; or units NULL = Philox4x32-10 keyed by seed, counter (point, class*2 + side,
+ * global pair (row0 + i)*Mb + j): any split of the rows into launches gives the same matrix. */
+int dfx_part_box_pairwise_f32(const float *boxes_a, const int32_t *present_a, int Ma, const float *boxes_b,
+                              const int32_t *present_b, int Mb, int C, int metric, uint64_t seed, long long row0,
+                              const float *units, float *D, dfx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Latent sampler — the once-per-batch producer of decode's inputs:
  * PartEncoder.sample_latents (python/difffacto/models/encoders/part_encoders.py:1052-1110) =
  * per-part normalising flows run in reverse (python/difffacto/models/encoders/flow.py:21-47,58-72)

@@ -79,6 +79,8 @@ void dfx_debug_trace(void *device_buf, int capacity);
 /* A dfx_latents handle with n_class / zdim / cimle / noise_dim set and no device memory (free with dfx_latents_destroy): the argument
  * checks of dfx_compose_latents run against it on a machine without a GPU; a call that passes them fails with "holds no weights". */
 int dfx_debug_latents_stub(dfx_latents **out, int n_class, int zdim, int cimle, int noise_dim);
+/* The unit draws dfx_part_box_pairwise_f32 makes without `units` for global pairs pair0 .. pair0+P-1: units (P,C,2,512,3) device. */
+int dfx_debug_part_box_units(uint64_t seed, long long pair0, int P, int C, float *units, dfx_stream_t stream);
 
 #ifdef __cplusplus
 }
