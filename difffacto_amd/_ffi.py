@@ -55,6 +55,13 @@ class LatentWeights(ctypes.Structure):
                [("blocks", AlignerBlockWeights * DFX_MAX_DEPTH)]
 
 
+class NoiseOptProblem(ctypes.Structure):
+    """dfx_noise_opt_problem (include/dfx.h): targets, masks and constants of the aligner-noise optimization."""
+    _fields_ = [(n, c_fp) for n in ("fit_mean", "fit_logvar", "fix", "edit_mean", "edit_mean_sel", "edit_logvar", "edit_var_sel")] + \
+               [(n, ctypes.c_double) for n in ("fit_weight", "reg_weight", "lr0", "beta1", "beta2", "adam_eps", "factor", "threshold", "min_lr",
+                                               "lr_eps", "stop_atol", "stop_rtol")] + [("patience", ctypes.c_int32)]
+
+
 class PointNetV2Weights(ctypes.Structure):
     _fields_ = [("num_anchors", ctypes.c_int32), ("zdim", ctypes.c_int32), ("reweight_by_anchor", ctypes.c_int32),
                 ("bn_eps", ctypes.c_float)] + \
@@ -121,6 +128,9 @@ SIGNATURES = {
     "dfx_aligner_train_workspace_bytes": (_SZ, [_I] * 7),
     "dfx_aligner_train_forward": (_I, [ctypes.POINTER(LatentWeights), _P, _SZ, _P, _P, _P, _P, _P, _I, _P]),
     "dfx_aligner_train_backward": (_I, [ctypes.POINTER(LatentWeights), _P, _SZ, _P, _P, _P, ctypes.POINTER(LatentWeights), _P, _I, _P]),
+    "dfx_aligner_input_backward": (_I, [ctypes.POINTER(LatentWeights), _P, _SZ, _P, _P, _P, _P, _P, _I, _P]),
+    "dfx_noise_opt_workspace_bytes": (_SZ, [ctypes.POINTER(LatentWeights), _I]),
+    "dfx_noise_opt_run": (_I, [ctypes.POINTER(LatentWeights), _P, _SZ, ctypes.POINTER(NoiseOptProblem), _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dfx_shared_mlp_create": (_I, [ctypes.POINTER(_P), _I, ctypes.POINTER(ctypes.c_int32)] + [ctypes.POINTER(c_fp)] * 6 + [_F, ctypes.c_uint32, _P]),
     "dfx_pointnet_v2_create": (_I, [ctypes.POINTER(_P), ctypes.POINTER(PointNetV2Weights), _P]),
     "dfx_pointnet_v2_destroy": (None, [_P]),

@@ -15,6 +15,15 @@
 
 #include "dfx_common.h"
 
+int dfx::aligner_train_check(const dfx_latent_weights *w, const char *who) {
+  DFX_REQUIRE(w, "%s: null weights", who);
+  DFX_REQUIRE(w->n_class >= 1 && w->n_class <= 8 && w->depth >= 1 && w->depth <= DFX_MAX_DEPTH, "%s: n_class %d / depth %d", who, w->n_class, w->depth);
+  DFX_REQUIRE(w->d_head == 16 || w->d_head == 32 || w->d_head == 64, "%s: d_head %d not in {16, 32, 64}", who, w->d_head);
+  DFX_REQUIRE((w->n_heads * w->d_head) % 64 == 0 && w->n_heads * w->d_head <= 1024, "%s: inner dim %d", who, w->n_heads * w->d_head);
+  DFX_REQUIRE(w->cimle && w->noise_dim > 0, "%s: the training path is the cIMLE configuration (noise concatenated per token, no pre_norm)", who);
+  return DFX_OK;
+}
+
 namespace {
 
 constexpr int TS = 16;   // product tile
@@ -89,6 +98,16 @@ __global__ void k_tokens_bwd(const float *__restrict__ dX, float *__restrict__ d
   if (t >= (long long)R * Z * J) return;
   const int j = t % J, c = (t / J) % Z, r = t / ((long long)J * Z);
   dcode[t] = dX[((size_t)r * J + j) * IC + c];
+}
+
+// the transpose of k_tokens for the noise: d noise[r][c] = scale * sum_j dX0[(r, j)][Z + c]  (j ascending: fixed order, no atomics)
+__global__ void k_noise_bwd(const float *__restrict__ dX, float *__restrict__ dnoise, int R, int Z, int J, int ND, float scale) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long long)R * ND) return;
+  const int c = t % ND, r = t / ND, IC = Z + ND;
+  float s = 0.f;
+  for (int j = 0; j < J; ++j) s += dX[((size_t)r * J + j) * IC + Z + c];
+  dnoise[t] = scale * s;
 }
 
 // LayerNorm over the last dimension (C a multiple of 64, <= 1024): one wavefront per row; stats = (mean, rstd) per row; two passes like torch
@@ -172,43 +191,48 @@ __global__ void k_attn_fwd(const float *__restrict__ QKV, const float *__restric
     o[d] = a;
   }
 }
-// backward: one thread per (shape, head) walks the J x J pairs in fixed order -> dQKV (no atomics)
+// backward: one thread per (shape, head, channel d) -> dQKV (no atomics).  Every thread of a (shape, head) repeats the J x J softmax-gradient scalars
+// (the same operations in the same order, so the same bits in every lane) and accumulates its own channel of dq / dk / dv in registers, in the order
+// a single walk over the (j, jj) pairs would: dq[j] over jj ascending, dk[jj] and dv[jj] over j ascending.
 template <int DH>
 __global__ void k_attn_bwd(const float *__restrict__ QKV, const float *__restrict__ P, const float *__restrict__ dO, float *__restrict__ dQKV, int R, int J, int H,
                            float scale) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= R * H) return;
-  const int h = t % H, r = t / H, C = H * DH;
-  for (int j = 0; j < J; ++j)
-    for (int d = 0; d < DH; ++d) {
-      dQKV[((size_t)r * J + j) * 3 * C + h * DH + d] = 0.f;
-      dQKV[((size_t)r * J + j) * 3 * C + C + h * DH + d] = 0.f;
-      dQKV[((size_t)r * J + j) * 3 * C + 2 * C + h * DH + d] = 0.f;
-    }
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long long)R * H * DH) return;
+  const int d = t % DH, h = (t / DH) % H, r = t / ((long long)DH * H), C = H * DH;
+  float adk[8], adv[8];
+#pragma unroll
+  for (int jj = 0; jj < 8; ++jj) adk[jj] = 0.f, adv[jj] = 0.f;
   for (int j = 0; j < J; ++j) {
     const float *p = P + (((size_t)r * J + j) * H + h) * J;
     const float *dout = dO + ((size_t)r * J + j) * C + h * DH;
     const float *q = QKV + ((size_t)r * J + j) * 3 * C + h * DH;
     float dP[8], dot = 0.f;
-    for (int jj = 0; jj < J; ++jj) {
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj) {
+      if (jj >= J) break;
       const float *v = QKV + ((size_t)r * J + jj) * 3 * C + 2 * C + h * DH;
       float s = 0.f;
-      for (int d = 0; d < DH; ++d) s = fmaf(dout[d], v[d], s);
+      for (int dd = 0; dd < DH; ++dd) s = fmaf(dout[dd], v[dd], s);
       dP[jj] = s;
       dot = fmaf(p[jj], s, dot);
     }
-    for (int jj = 0; jj < J; ++jj) {
+    float adq = 0.f;
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj) {
+      if (jj >= J) break;
       const float ds = p[jj] * (dP[jj] - dot) * scale;   // d sim (masked keys: p = 0 -> 0)
-      const float *k = QKV + ((size_t)r * J + jj) * 3 * C + C + h * DH;
-      float *dq = dQKV + ((size_t)r * J + j) * 3 * C + h * DH;
-      float *dk = dQKV + ((size_t)r * J + jj) * 3 * C + C + h * DH;
-      float *dv = dQKV + ((size_t)r * J + jj) * 3 * C + 2 * C + h * DH;
-      for (int d = 0; d < DH; ++d) {
-        dq[d] = fmaf(ds, k[d], dq[d]);
-        dk[d] = fmaf(ds, q[d], dk[d]);
-        dv[d] = fmaf(p[jj], dout[d], dv[d]);
-      }
+      adq = fmaf(ds, QKV[((size_t)r * J + jj) * 3 * C + C + h * DH + d], adq);
+      adk[jj] = fmaf(ds, q[d], adk[jj]);
+      adv[jj] = fmaf(p[jj], dout[d], adv[jj]);
     }
+    dQKV[((size_t)r * J + j) * 3 * C + h * DH + d] = adq;
+  }
+#pragma unroll
+  for (int jj = 0; jj < 8; ++jj) {
+    if (jj >= J) break;
+    dQKV[((size_t)r * J + jj) * 3 * C + C + h * DH + d] = adk[jj];
+    dQKV[((size_t)r * J + jj) * 3 * C + 2 * C + h * DH + d] = adv[jj];
   }
 }
 
@@ -277,19 +301,60 @@ size_t carve(Ws &w, char *base, int R, int J, int C, int IC, int H, int depth) {
   w.dAG = take(M * 8 * C), w.dHID = take(M * 4 * C), w.dOUT = take(M * 6), w.dX0 = take(M * IC);
   return off;
 }
-int check(const dfx_latent_weights *w, const char *who) {
-  DFX_REQUIRE(w, "%s: null weights", who);
-  DFX_REQUIRE(w->n_class >= 1 && w->n_class <= 8 && w->depth >= 1 && w->depth <= DFX_MAX_DEPTH, "%s: n_class %d / depth %d", who, w->n_class, w->depth);
-  DFX_REQUIRE(w->d_head == 16 || w->d_head == 32 || w->d_head == 64, "%s: d_head %d not in {16, 32, 64}", who, w->d_head);
-  DFX_REQUIRE((w->n_heads * w->d_head) % 64 == 0 && w->n_heads * w->d_head <= 1024, "%s: inner dim %d", who, w->n_heads * w->d_head);
-  DFX_REQUIRE(w->cimle && w->noise_dim > 0, "%s: the training path is the cIMLE configuration (noise concatenated per token, no pre_norm)", who);
-  return DFX_OK;
-}
+int check(const dfx_latent_weights *w, const char *who) { return dfx::aligner_train_check(w, who); }
 template <class F>
 void attn_dispatch(int dh, F &&f) {
   if (dh == 16) f(std::integral_constant<int, 16>{});
   else if (dh == 32) f(std::integral_constant<int, 32>{});
   else f(std::integral_constant<int, 64>{});
+}
+
+// The backward chain behind dfx_aligner_train_forward.  The dH chain (data gradients) is the same launches in the same order whether `grads` is
+// given or not; with grads == NULL every weight-gradient product, column sum and LayerNorm-parameter launch is left out.
+void backward_chain(const dfx_latent_weights *w, Ws &s, const float *d_mean, const float *d_logvar, const dfx_latent_weights *grads,
+                    float *d_part_code, float *d_noise, int B, hipStream_t st) {
+  const int J = w->n_class, C = w->n_heads * w->d_head, IC = w->zdim + w->noise_dim, H = w->n_heads, M = B * J;
+  auto mut = [](const float *p) { return const_cast<float *>(p); };
+  const float scale = 1.0f / sqrtf((float)w->d_head);
+  k_split_bwd<<<nblk((long long)M * 6), 256, 0, st>>>(d_mean, d_logvar, s.dOUT, B, J);
+  if (grads) linear_dw(st, s.dOUT, 6, s.Xnf, C, mut(grads->proj_out_w), M, 6, C);
+  if (grads) k_colsum<<<1, 64, 0, st>>>(s.dOUT, 6, mut(grads->proj_out_b), M, 6, 0, 1);
+  linear_dx(st, s.dOUT, 6, w->proj_out_w, nullptr, s.dXn, C, M, 6, C);
+  k_ln_bwd<<<nblk(M, 4), 256, 0, st>>>(s.dXn, s.H[w->depth], s.stf, w->post_norm_w, nullptr, s.dH, s.XH, M, C);
+  if (grads) k_ln_param<<<nblk(C), 256, 0, st>>>(s.dXn, s.XH, mut(grads->post_norm_w), mut(grads->post_norm_b), M, C);
+  for (int i = w->depth - 1; i >= 0; --i) {
+    const dfx_aligner_block_weights &k = w->blocks[i], &g = (grads ? grads : w)->blocks[i];   // g: only used under `if (grads)`
+    // h_out = h1 + ff_out(hid) : dH is the gradient at h_out
+    if (grads) linear_dw(st, s.dH, C, s.HID[i], 4 * C, mut(g.ff_out_w), M, C, 4 * C);
+    if (grads) k_colsum<<<nblk(C), 256, 0, st>>>(s.dH, C, mut(g.ff_out_b), M, C, 0, 1);
+    linear_dx(st, s.dH, C, k.ff_out_w, nullptr, s.dHID, 4 * C, M, C, 4 * C);
+    k_geglu_bwd<<<nblk((long long)M * 4 * C), 256, 0, st>>>(s.AG[i], s.dHID, s.dAG, M, 4 * C);
+    if (grads) linear_dw(st, s.dAG, 8 * C, s.Xn3[i], C, mut(g.ff_proj_w), M, 8 * C, C);
+    if (grads) k_colsum<<<nblk(8 * C), 256, 0, st>>>(s.dAG, 8 * C, mut(g.ff_proj_b), M, 8 * C, 0, 1);
+    linear_dx(st, s.dAG, 8 * C, k.ff_proj_w, nullptr, s.dXn, C, M, 8 * C, C);
+    k_ln_bwd<<<nblk(M, 4), 256, 0, st>>>(s.dXn, s.H1[i], s.st3[i], k.norm3_w, s.dH, s.dH1, s.XH, M, C);   // dH1 = dH + LN3'(dxn3)
+    if (grads) k_ln_param<<<nblk(C), 256, 0, st>>>(s.dXn, s.XH, mut(g.norm3_w), mut(g.norm3_b), M, C);
+    // h1 = h + to_out(att)
+    if (grads) linear_dw(st, s.dH1, C, s.O[i], C, mut(g.to_out_w), M, C, C);
+    if (grads) k_colsum<<<nblk(C), 256, 0, st>>>(s.dH1, C, mut(g.to_out_b), M, C, 0, 1);
+    linear_dx(st, s.dH1, C, k.to_out_w, nullptr, s.dO, C, M, C, C);
+    attn_dispatch(w->d_head, [&](auto dh) { k_attn_bwd<decltype(dh)::value><<<nblk((long long)B * H * w->d_head), 256, 0, st>>>(s.QKV[i], s.P[i], s.dO, s.dQKV, B, J, H, scale); });
+    if (grads) linear_dw(st, s.dQKV, 3 * C, s.Xn2[i], C, mut(g.to_q), M, C, C);
+    if (grads) linear_dw(st, s.dQKV + C, 3 * C, s.Xn2[i], C, mut(g.to_k), M, C, C);
+    if (grads) linear_dw(st, s.dQKV + 2 * C, 3 * C, s.Xn2[i], C, mut(g.to_v), M, C, C);
+    linear_dx(st, s.dQKV, 3 * C, k.to_q, nullptr, s.dXn, C, M, C, C);
+    linear_dx(st, s.dQKV + C, 3 * C, k.to_k, s.dXn, s.dXn, C, M, C, C);
+    linear_dx(st, s.dQKV + 2 * C, 3 * C, k.to_v, s.dXn, s.dXn, C, M, C, C);
+    k_ln_bwd<<<nblk(M, 4), 256, 0, st>>>(s.dXn, s.H[i], s.st2[i], k.norm2_w, s.dH1, s.dH, s.XH, M, C);     // dH(in) = dH1 + LN2'(dxn2)
+    if (grads) k_ln_param<<<nblk(C), 256, 0, st>>>(s.dXn, s.XH, mut(g.norm2_w), mut(g.norm2_b), M, C);
+  }
+  // h0 = proj_in(x0) + class_emb[token]
+  if (grads) for (int j = 0; j < J; ++j) k_colsum<<<nblk(C), 256, 0, st>>>(s.dH, C, mut(grads->class_emb) + (size_t)j * C, M, C, j, J);
+  if (grads) linear_dw(st, s.dH, C, s.X0, IC, mut(grads->proj_in_w), M, C, IC);
+  if (grads) k_colsum<<<nblk(C), 256, 0, st>>>(s.dH, C, mut(grads->proj_in_b), M, C, 0, 1);
+  if (d_part_code || d_noise) linear_dx(st, s.dH, C, w->proj_in_w, nullptr, s.dX0, IC, M, C, IC);
+  if (d_part_code) k_tokens_bwd<<<nblk((long long)B * w->zdim * J), 256, 0, st>>>(s.dX0, d_part_code, B, w->zdim, J, IC);
+  if (d_noise) k_noise_bwd<<<nblk((long long)B * w->noise_dim), 256, 0, st>>>(s.dX0, d_noise, B, w->zdim, J, w->noise_dim, w->noise_scale);
 }
 
 }  // namespace
@@ -342,53 +407,26 @@ int dfx_aligner_train_backward(const dfx_latent_weights *w, void *workspace, siz
   int rc = check(w, "aligner_train_backward");
   if (rc) return rc;
   DFX_REQUIRE(B > 0 && valid && (d_mean || d_logvar) && grads && workspace, "aligner_train_backward: null argument");
-  const int J = w->n_class, C = w->n_heads * w->d_head, IC = w->zdim + w->noise_dim, H = w->n_heads, M = B * J;
   Ws s;
-  DFX_REQUIRE(carve(s, static_cast<char *>(workspace), B, J, C, IC, H, w->depth) <= workspace_bytes, "aligner_train_backward: workspace too small");
-  hipStream_t st = dfx::as_stream(stream);
-  auto mut = [](const float *p) { return const_cast<float *>(p); };
-  const float scale = 1.0f / sqrtf((float)w->d_head);
-  k_split_bwd<<<nblk((long long)M * 6), 256, 0, st>>>(d_mean, d_logvar, s.dOUT, B, J);
-  linear_dw(st, s.dOUT, 6, s.Xnf, C, mut(grads->proj_out_w), M, 6, C);
-  k_colsum<<<1, 64, 0, st>>>(s.dOUT, 6, mut(grads->proj_out_b), M, 6, 0, 1);
-  linear_dx(st, s.dOUT, 6, w->proj_out_w, nullptr, s.dXn, C, M, 6, C);
-  k_ln_bwd<<<nblk(M, 4), 256, 0, st>>>(s.dXn, s.H[w->depth], s.stf, w->post_norm_w, nullptr, s.dH, s.XH, M, C);
-  k_ln_param<<<nblk(C), 256, 0, st>>>(s.dXn, s.XH, mut(grads->post_norm_w), mut(grads->post_norm_b), M, C);
-  for (int i = w->depth - 1; i >= 0; --i) {
-    const dfx_aligner_block_weights &k = w->blocks[i], &g = grads->blocks[i];
-    // h_out = h1 + ff_out(hid) : dH is the gradient at h_out
-    linear_dw(st, s.dH, C, s.HID[i], 4 * C, mut(g.ff_out_w), M, C, 4 * C);
-    k_colsum<<<nblk(C), 256, 0, st>>>(s.dH, C, mut(g.ff_out_b), M, C, 0, 1);
-    linear_dx(st, s.dH, C, k.ff_out_w, nullptr, s.dHID, 4 * C, M, C, 4 * C);
-    k_geglu_bwd<<<nblk((long long)M * 4 * C), 256, 0, st>>>(s.AG[i], s.dHID, s.dAG, M, 4 * C);
-    linear_dw(st, s.dAG, 8 * C, s.Xn3[i], C, mut(g.ff_proj_w), M, 8 * C, C);
-    k_colsum<<<nblk(8 * C), 256, 0, st>>>(s.dAG, 8 * C, mut(g.ff_proj_b), M, 8 * C, 0, 1);
-    linear_dx(st, s.dAG, 8 * C, k.ff_proj_w, nullptr, s.dXn, C, M, 8 * C, C);
-    k_ln_bwd<<<nblk(M, 4), 256, 0, st>>>(s.dXn, s.H1[i], s.st3[i], k.norm3_w, s.dH, s.dH1, s.XH, M, C);   // dH1 = dH + LN3'(dxn3)
-    k_ln_param<<<nblk(C), 256, 0, st>>>(s.dXn, s.XH, mut(g.norm3_w), mut(g.norm3_b), M, C);
-    // h1 = h + to_out(att)
-    linear_dw(st, s.dH1, C, s.O[i], C, mut(g.to_out_w), M, C, C);
-    k_colsum<<<nblk(C), 256, 0, st>>>(s.dH1, C, mut(g.to_out_b), M, C, 0, 1);
-    linear_dx(st, s.dH1, C, k.to_out_w, nullptr, s.dO, C, M, C, C);
-    attn_dispatch(w->d_head, [&](auto dh) { k_attn_bwd<decltype(dh)::value><<<nblk((long long)B * H, 64), 64, 0, st>>>(s.QKV[i], s.P[i], s.dO, s.dQKV, B, J, H, scale); });
-    linear_dw(st, s.dQKV, 3 * C, s.Xn2[i], C, mut(g.to_q), M, C, C);
-    linear_dw(st, s.dQKV + C, 3 * C, s.Xn2[i], C, mut(g.to_k), M, C, C);
-    linear_dw(st, s.dQKV + 2 * C, 3 * C, s.Xn2[i], C, mut(g.to_v), M, C, C);
-    linear_dx(st, s.dQKV, 3 * C, k.to_q, nullptr, s.dXn, C, M, C, C);
-    linear_dx(st, s.dQKV + C, 3 * C, k.to_k, s.dXn, s.dXn, C, M, C, C);
-    linear_dx(st, s.dQKV + 2 * C, 3 * C, k.to_v, s.dXn, s.dXn, C, M, C, C);
-    k_ln_bwd<<<nblk(M, 4), 256, 0, st>>>(s.dXn, s.H[i], s.st2[i], k.norm2_w, s.dH1, s.dH, s.XH, M, C);     // dH(in) = dH1 + LN2'(dxn2)
-    k_ln_param<<<nblk(C), 256, 0, st>>>(s.dXn, s.XH, mut(g.norm2_w), mut(g.norm2_b), M, C);
-  }
-  // h0 = proj_in(x0) + class_emb[token]
-  for (int j = 0; j < J; ++j) k_colsum<<<nblk(C), 256, 0, st>>>(s.dH, C, mut(grads->class_emb) + (size_t)j * C, M, C, j, J);
-  linear_dw(st, s.dH, C, s.X0, IC, mut(grads->proj_in_w), M, C, IC);
-  k_colsum<<<nblk(C), 256, 0, st>>>(s.dH, C, mut(grads->proj_in_b), M, C, 0, 1);
-  if (d_part_code) {
-    linear_dx(st, s.dH, C, w->proj_in_w, nullptr, s.dX0, IC, M, C, IC);
-    k_tokens_bwd<<<nblk((long long)B * w->zdim * J), 256, 0, st>>>(s.dX0, d_part_code, B, w->zdim, J, IC);
-  }
+  DFX_REQUIRE(carve(s, static_cast<char *>(workspace), B, w->n_class, w->n_heads * w->d_head, w->zdim + w->noise_dim, w->n_heads, w->depth) <= workspace_bytes,
+              "aligner_train_backward: workspace too small");
+  backward_chain(w, s, d_mean, d_logvar, grads, d_part_code, nullptr, B, dfx::as_stream(stream));
   return dfx::check_launch("aligner_train_backward");
+}
+
+/* The data-gradient half of dfx_aligner_train_backward: the same dH chain, no weight-gradient launch, and the noise gradient
+ * d_noise[r][c] = noise_scale * sum_j dX0[(r, j)][zdim + c] (the transpose of k_tokens).  At least one of d_noise / d_part_code is given. */
+int dfx_aligner_input_backward(const dfx_latent_weights *w, void *workspace, size_t workspace_bytes, const float *valid, const float *d_mean,
+                               const float *d_logvar, float *d_noise, float *d_part_code, int B, dfx_stream_t stream) {
+  int rc = check(w, "aligner_input_backward");
+  if (rc) return rc;
+  DFX_REQUIRE(B > 0 && valid && (d_mean || d_logvar) && workspace, "aligner_input_backward: null argument");
+  DFX_REQUIRE(d_noise || d_part_code, "aligner_input_backward: neither d_noise nor d_part_code given");
+  Ws s;
+  DFX_REQUIRE(carve(s, static_cast<char *>(workspace), B, w->n_class, w->n_heads * w->d_head, w->zdim + w->noise_dim, w->n_heads, w->depth) <= workspace_bytes,
+              "aligner_input_backward: workspace too small");
+  backward_chain(w, s, d_mean, d_logvar, nullptr, d_part_code, d_noise, B, dfx::as_stream(stream));
+  return dfx::check_launch("aligner_input_backward");
 }
 
 }  // extern "C"

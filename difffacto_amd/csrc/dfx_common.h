@@ -86,6 +86,9 @@ struct EventTimer {
   void begin(hipStream_t s);
   void end();
 };
+// Configuration check shared by the aligner's training entry points (aligner_train.hip) and the noise optimizer on top of them (noise_opt.hip).
+int aligner_train_check(const dfx_latent_weights *w, const char *who);
+
 extern bool g_event_timing;
 extern float g_last_ms;
 extern const char *g_last_variant;   // name of the denoiser kernel the last launch() took (dfx_last_kernel_variant)

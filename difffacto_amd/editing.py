@@ -11,6 +11,13 @@ applications; the reference's AnchorDiffAE.interpolate_latent / combine_latent /
 aligner noise and the chain noise are drawn from ``generator`` (torch's global generator when None), the chain's Philox key
 is ``seed`` when given.
 
+Part re-configuration (the reference's tools/shape_edit.py and tools/optimize_noise.py: gradient descent on the aligner's cIMLE
+noise) is ``reconfigure_part`` / ``invert_noise``: every row (a shape x a candidate edit x a random start) is an independent
+problem, all of them optimized by ONE ``dfx_noise_opt_run`` call, then one ``dfx_compose_latents`` and one chain launch.
+
+    out = reconfigure_part(encoder, diffusion, codes, ref_mean, ref_var, edit_part=0, new_var=v, fix_parts=[0, 1, 1, 1])
+    out = invert_noise(encoder, codes, ref_mean, ref_var)                           # the noise that reproduces a configuration
+
 The recipe builders below are host-side index bookkeeping (no GPU): rows are ``r = b * K + k`` like the reference's
 ``repeat_interleave(K, dim=0)``.
 """
@@ -167,3 +174,166 @@ def drift_anchors(encoder, diffusion, codes, scale, parts=(0, 2), axis=1, valid_
                                           mean_scale=s.to(device), logvar_shift=l.to(device), **seg_kw)
     return {"pred": pred.reshape(B, K, npoints, 3), "seg_mask": seg.reshape(B, K, npoints),
             "anchors": mean_pp.transpose(1, 2).reshape(B, K, npoints, 3)}
+
+
+# ---------------------------------------------------------------------------------------------------- aligner-noise optimization
+# constants of tools/shape_edit.py:83-85,126 (Adam defaults, ReduceLROnPlateau(factor 0.5, patience 10, min_lr 5e-2), torch.allclose) and of
+# edit_latent's call there (fit_weight 0.05); reg_weight = AnchorDiffAE's reg_loss_weight default
+NOISE_OPT_DEFAULTS = {"fit_weight": 0.05, "reg_weight": 1.0, "lr0": 1.0, "beta1": 0.9, "beta2": 0.999, "adam_eps": 1e-8, "factor": 0.5,
+                      "threshold": 1e-4, "min_lr": 5e-2, "lr_eps": 1e-8, "stop_atol": 1e-8, "stop_rtol": 1e-5, "patience": 10}
+
+
+def noise_problem(valid, ref_mean, ref_var, fix_parts, edit_part, new_mean=None, new_var=None, fit_weight=0.05, reg_weight=1.0, **constants):
+    """Targets and masks of ``LatentSampler.optimize_noise`` for R rows, the terms of ``AnchorDiffAE.edit_latent`` (anchor_gen.py:877-892) per row:
+
+        fit  = sum(f * ((mean - ref_mean)^2 + (logvar - log ref_var)^2)) / sum(f),   f = valid * fix_parts          (:877-879)
+        edit = mse(mean[..., edit_part], new_mean) + mse(logvar[..., edit_part], log new_var)   (each absent when None)   (:880-888)
+
+    valid (R,J) 0/1; ref_mean / ref_var (R,3,J); fix_parts (J,) or (R,J) 0/1 (the reference's ``fix_ids``); edit_part an int, (R,) ints or None
+    (no edit term: ``optimize_latent``'s objective with fix_parts all ones); new_mean / new_var (3,) or (R,3).  Host tensors (fp32).
+    ValueError for an edited part that is absent and for a row without any fixed present part (the reference divides by zero there).  Where
+    f = 0 the fit target is set to 0 (the reference multiplies log(ref_var) of an absent part by 0: NaN when that variance is 0)."""
+    f32 = lambda a: torch.as_tensor(a).detach().cpu().to(torch.float32)
+    valid, ref_mean, ref_var = f32(valid), f32(ref_mean), f32(ref_var)
+    R, J = valid.shape
+    if tuple(ref_mean.shape) != (R, 3, J) or tuple(ref_var.shape) != (R, 3, J):
+        raise ValueError(f"noise_problem: ref_mean / ref_var (R,3,J) = ({R},3,{J}) expected")
+    fix = valid * f32(fix_parts).reshape(-1, J).expand(R, J)
+    if bool((fix.sum(1) == 0).any()):
+        raise ValueError("noise_problem: a row has no fixed part that is present (the fit term would divide by zero)")
+    keep = fix[:, None, :].expand(R, 3, J) != 0
+    unknown = set(constants) - set(NOISE_OPT_DEFAULTS)
+    if unknown:
+        raise TypeError(f"noise_problem: unknown constants {sorted(unknown)}")
+    p = {"fit_mean": torch.where(keep, ref_mean, torch.zeros(())), "fit_logvar": torch.where(keep, torch.log(torch.where(keep, ref_var, torch.ones(()))), torch.zeros(())),
+         "fix": fix, "fit_weight": float(fit_weight), "reg_weight": float(reg_weight), **constants}
+    if edit_part is None:
+        if new_mean is not None or new_var is not None:
+            raise ValueError("noise_problem: an edit target without edit_part")
+        return p
+    ep = torch.as_tensor(edit_part).reshape(-1).expand(R).long()
+    if bool(((ep < 0) | (ep >= J)).any()) or bool((valid[torch.arange(R), ep] == 0).any()):
+        raise ValueError("noise_problem: the edited part is absent (or its id is out of range)")
+    sel = torch.zeros(R, J)
+    sel[torch.arange(R), ep] = 1.0
+    for name, tgt, key, selkey in (("new_mean", new_mean, "edit_mean", "edit_mean_sel"), ("new_var", new_var, "edit_logvar", "edit_var_sel")):
+        if tgt is None:
+            continue
+        t = f32(tgt).reshape(-1, 3).expand(R, 3)
+        full = torch.zeros(R, 3, J)
+        full[torch.arange(R), :, ep] = torch.log(t) if name == "new_var" else t
+        p[key], p[selkey] = full, sel.clone()
+    return p
+
+
+def noise_losses(problem, mean, logvar, z):
+    """The per-row loss terms of ``noise_problem`` at (mean, logvar, z) in torch (any device / dtype; the formulas k_edit_loss implements):
+    dict L, fit, edit, reg, each (R,)."""
+    g = lambda k: None if problem.get(k) is None else torch.as_tensor(problem[k]).to(mean)
+    f = g("fix")[:, None, :]
+    fit = (f * ((mean - g("fit_mean")) ** 2 + (logvar - g("fit_logvar")) ** 2)).sum((1, 2)) / g("fix").sum(1)
+    edit = torch.zeros_like(fit)
+    if g("edit_mean_sel") is not None:
+        edit = edit + (g("edit_mean_sel")[:, None, :] * (mean - g("edit_mean")) ** 2).sum((1, 2)) / 3
+    if g("edit_var_sel") is not None:
+        edit = edit + (g("edit_var_sel")[:, None, :] * (logvar - g("edit_logvar")) ** 2).sum((1, 2)) / 3
+    reg = (z.to(mean) ** 2).sum(1)
+    c = {**NOISE_OPT_DEFAULTS, **{k: v for k, v in problem.items() if k in NOISE_OPT_DEFAULTS}}
+    return {"L": c["fit_weight"] * fit + edit + c["reg_weight"] * reg, "fit": fit, "edit": edit, "reg": reg}
+
+
+def noise_opt_replay(losses, grads, z0, **constants):
+    """Float64 restatement of ONE row of k_noise_step (noise_opt.hip): ``torch.optim.Adam`` defaults driven by the gradient sequence
+    ``grads`` (K, noise_dim), then ``ReduceLROnPlateau(mode min, threshold mode rel, cooldown 0)`` and the ``torch.allclose`` stop rule driven
+    by the loss sequence ``losses`` (K,).  The oracle of the kernel's trace (fed with the traced losses and gradients) and, on the CPU, checked
+    against torch's own optimizer and scheduler.  Returns dict: z (n+1, noise_dim) (z[k] = before step k; z[n] = the result), lr (n,) the rate
+    of step k, reduced_at (iterations whose scheduler step lowered the rate), stopped_at (iteration or None), n = iterations run."""
+    c = {**NOISE_OPT_DEFAULTS, **constants}
+    losses, grads = np.asarray(losses, np.float64), np.asarray(grads, np.float64)
+    z = np.asarray(z0, np.float64).reshape(-1).copy()
+    m, v = np.zeros_like(z), np.zeros_like(z)
+    lr, best, prev, bad = float(c["lr0"]), float("inf"), 0.0, 0
+    zs, lrs, reduced, stopped = [z.copy()], [], [], None
+    for k in range(len(losses)):
+        g, L = grads[k], float(losses[k])
+        m = m + (1 - c["beta1"]) * (g - m)
+        v = v * c["beta2"] + (1 - c["beta2"]) * g * g
+        bc1, bc2 = 1 - c["beta1"] ** (k + 1), 1 - c["beta2"] ** (k + 1)
+        z = z - (lr / bc1) * (m / (np.sqrt(v) / np.sqrt(bc2) + c["adam_eps"]))
+        lrs.append(lr)
+        zs.append(z.copy())
+        if L < best * (1.0 - c["threshold"]):
+            best, bad = L, 0
+        else:
+            bad += 1
+        if bad > c["patience"]:
+            new = max(lr * c["factor"], c["min_lr"])
+            if lr - new > c["lr_eps"]:
+                lr = new
+                reduced.append(k)
+            bad = 0
+        if abs(L - prev) <= c["stop_atol"] + c["stop_rtol"] * abs(prev):
+            stopped = k
+            break
+        prev = L
+    return {"z": np.stack(zs), "lr": np.asarray(lrs), "reduced_at": reduced, "stopped_at": stopped, "n": len(lrs)}
+
+
+def _optimize_rows(encoder, diffusion, codes, problem_of, valid_id, shape_row, z0, max_iter, npoints, seed, generator, trace):
+    device, codes, valid_id = _setup(encoder, codes, valid_id)
+    S, J = codes.shape[0], encoder.n_class
+    rows = np.arange(S, dtype=np.int32) if shape_row is None else np.asarray(torch.as_tensor(shape_row).cpu(), dtype=np.int32).reshape(-1)
+    if rows.size == 0 or rows.min() < 0 or rows.max() >= S:
+        raise ValueError(f"shape_row: indices into the {S} source shapes expected")
+    idx = torch.as_tensor(rows, dtype=torch.long, device=device)
+    valid = valid_id[idx].contiguous()
+    problem = problem_of(idx.cpu(), valid.cpu())
+    if z0 is None:
+        z0 = _noise(encoder, len(rows), device, generator)
+    opt = encoder.sampler().optimize_noise(codes[idx], valid, z0, problem, max_iter, trace=trace)
+    out = {"z": opt["z"], "mean": opt["mean"], "logvar": opt["logvar"], "iters_done": opt["iters_done"], "trace": opt["trace"],
+           "losses": noise_losses(problem, opt["mean"], opt["logvar"], opt["z"]), "problem": problem}
+    if diffusion is not None:
+        pred, seg, mean_pp, _valid, _lat = _run(encoder, diffusion, codes, np.repeat(rows[:, None], J, 1), valid, npoints, seed, generator,
+                                                noise_src=opt["z"])
+        out.update({"pred": pred, "seg_mask": seg, "anchors": mean_pp.transpose(1, 2)})
+    return out
+
+
+@torch.no_grad()
+def reconfigure_part(encoder, diffusion, codes, ref_mean, ref_var, edit_part, new_mean=None, new_var=None, fix_parts=None, valid_id=None,
+                     shape_row=None, z0=None, max_iter=300, fit_weight=0.05, reg_weight=1.0, npoints=2048, seed=None, generator=None,
+                     trace=False, **constants):
+    """Edit one part's position (``new_mean``) and / or size (``new_var``) and let the other parts re-arrange themselves: the reference's
+    tools/shape_edit.py, for R rows at once.  Row r edits shape ``shape_row[r]`` of ``codes`` (S,zdim,J) (default: one row per shape), so rows
+    can be several shapes x several candidate edits x several random starts; ``ref_mean`` / ``ref_var`` (S,3,J) are the shapes' own part
+    parameters, ``fix_parts`` (J,) / (R,J) 0/1 the parts held to them (default: every part but the edited one), ``edit_part`` an int or (R,),
+    ``new_mean`` / ``new_var`` (3,) or (R,3), ``z0`` (R,noise_dim) the start (drawn when None).  Rows do not see each other (the reference's
+    batch mean would couple them).  ONE optimizer call, one ``dfx_compose_latents`` with the optimized noise rows, ONE chain launch.
+    Returns dict: z (R,noise_dim), mean / logvar (R,3,J) at z, iters_done (R,), losses {L, fit, edit, reg} (R,) at z, trace, problem, and
+    pred (R,npoints,3), seg_mask (R,npoints), anchors (R,npoints,3) (omitted with ``diffusion=None``)."""
+    J = encoder.n_class
+
+    def problem_of(idx, valid):
+        ep = torch.as_tensor(edit_part).reshape(-1).expand(len(idx)).long()
+        fix = fix_parts
+        if fix is None:
+            fix = torch.ones(len(idx), J)
+            fix[torch.arange(len(idx)), ep] = 0.0
+        return noise_problem(valid, torch.as_tensor(ref_mean).cpu()[idx], torch.as_tensor(ref_var).cpu()[idx], fix, ep, new_mean, new_var,
+                             fit_weight=fit_weight, reg_weight=reg_weight, **constants)
+
+    return _optimize_rows(encoder, diffusion, codes, problem_of, valid_id, shape_row, z0, max_iter, npoints, seed, generator, trace)
+
+
+@torch.no_grad()
+def invert_noise(encoder, codes, ref_mean, ref_var, diffusion=None, valid_id=None, shape_row=None, z0=None, max_iter=300, fit_weight=1.0,
+                 reg_weight=1.0, npoints=2048, seed=None, generator=None, trace=False, **constants):
+    """The aligner noise under which a shape's part codes give its own configuration ``ref_mean`` / ``ref_var`` (S,3,J): the reference's
+    tools/optimize_noise.py (``optimize_latent``'s fit + reg objective over the present parts), rows as in ``reconfigure_part`` (several random
+    starts per shape through ``shape_row``).  Returns ``reconfigure_part``'s dict (clouds only with a ``diffusion``)."""
+    def problem_of(idx, valid):
+        return noise_problem(valid, torch.as_tensor(ref_mean).cpu()[idx], torch.as_tensor(ref_var).cpu()[idx], torch.ones(valid.shape[1]), None,
+                             fit_weight=fit_weight, reg_weight=reg_weight, **constants)
+
+    return _optimize_rows(encoder, diffusion, codes, problem_of, valid_id, shape_row, z0, max_iter, npoints, seed, generator, trace)

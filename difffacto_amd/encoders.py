@@ -278,7 +278,7 @@ class PartAlignerTransformer(nn.Module):
         otherwise the inference kernels of the latent sampler."""
         if self.cimle and (noise is None or noise.shape[1] != self.noise_dim):
             noise = torch.zeros(x.shape[0], self.noise_dim, device=x.device)             # part_encoders.py:97-98
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+        if torch.is_grad_enabled() and (x.requires_grad or (noise is not None and noise.requires_grad) or any(p.requires_grad for p in self.parameters())):
             if not self.cimle:
                 _unsupported("training the part aligner without cimle (pre_norm path)")
             if any(isinstance(m, nn.Dropout) and m.p > 0 for m in self.modules()) and self.training:

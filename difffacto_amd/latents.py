@@ -53,7 +53,7 @@ class LatentSampler:
             t = t.detach().to(device=self.device, dtype=torch.float32).contiguous()
             if shape is not None and tuple(t.shape) != tuple(shape):
                 raise RuntimeError(f"{key}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
-            keep.append(t)
+            keep.append((key, t))
             return t.data_ptr()
 
         w = _ffi.LatentWeights()
@@ -87,7 +87,11 @@ class LatentSampler:
         with torch.cuda.device(self.device):
             rc = _ffi.lib().dfx_latents_create(ctypes.byref(handle), ctypes.byref(w), _ffi.current_stream())
         _ffi.check(rc, "dfx_latents_create")
-        del keep, flow_ptrs   # create() synchronised the stream
+        # create() synchronised the stream and packed its own copies.  The aligner's plain fp32 tensors stay, for the entry point that takes
+        # dfx_latent_weights directly (optimize_noise: the exact-fp32 training kernels); the flows are not needed there
+        w.flow, w.flow_depth = None, 0
+        self._w, self._keep = w, [t for key, t in keep if key.startswith("part_aligner.")]
+        del keep, flow_ptrs
         self._h = handle
 
     def close(self):
@@ -199,3 +203,39 @@ class LatentSampler:
                 _ffi.ptr(out["logvar_per_point"]), _ffi.current_stream())
         _ffi.check(rc, "dfx_compose_latents")
         return out
+
+    def optimize_noise(self, part_code, valid, z0, problem, max_iter, trace=False):
+        """``dfx_noise_opt_run``: R independent gradient descents on the aligner noise (tools/shape_edit.py:80-129 per row), enqueued
+        without host round trips.  part_code (R,zdim,J), valid (R,J), z0 (R,noise_dim); ``problem``: dict with the (R,3,J) targets
+        ``fit_mean`` / ``fit_logvar``, the (R,J) mask ``fix`` (= valid * fix_ids), optionally ``edit_mean`` + ``edit_mean_sel`` and
+        ``edit_logvar`` + ``edit_var_sel``, and the scalars of ``editing.NOISE_OPT_DEFAULTS`` (``editing.noise_problem`` builds it).
+        Returns dict: z, mean, logvar (at the returned z), iters_done (R,) int32, trace (max_iter,R,5 + 2 noise_dim) or None."""
+        from . import editing
+        if not self.cimle:
+            raise RuntimeError("optimize_noise needs the cIMLE aligner")
+        part_code, valid, z = self._f(part_code), self._f(valid), self._f(z0).clone()
+        R, J, ND = part_code.shape[0], self.n_class, self.noise_dim
+        assert tuple(part_code.shape) == (R, self.zdim, J) and tuple(valid.shape) == (R, J) and tuple(z.shape) == (R, ND)
+        p, keep = _ffi.NoiseOptProblem(), []
+        for name, shape in (("fit_mean", (R, 3, J)), ("fit_logvar", (R, 3, J)), ("fix", (R, J)), ("edit_mean", (R, 3, J)), ("edit_mean_sel", (R, J)),
+                            ("edit_logvar", (R, 3, J)), ("edit_var_sel", (R, J))):
+            t = self._f(problem.get(name))
+            if t is not None:
+                assert tuple(t.shape) == shape, (name, tuple(t.shape), shape)
+                keep.append(t)
+                setattr(p, name, t.data_ptr())
+        for name, default in editing.NOISE_OPT_DEFAULTS.items():
+            setattr(p, name, type(default)(problem.get(name, default)))
+        lib = _ffi.lib()
+        nbytes = lib.dfx_noise_opt_workspace_bytes(ctypes.byref(self._w), R)
+        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+        mean = torch.empty(R, 3, J, dtype=torch.float32, device=self.device)
+        logvar = torch.empty_like(mean)
+        iters = torch.empty(R, dtype=torch.int32, device=self.device)
+        tr = torch.empty(int(max_iter), R, 5 + 2 * ND, dtype=torch.float32, device=self.device) if trace else None
+        with torch.cuda.device(self.device):
+            rc = lib.dfx_noise_opt_run(ctypes.byref(self._w), (ws.data_ptr() + 255) & ~255, nbytes, ctypes.byref(p), _ffi.ptr(part_code), _ffi.ptr(valid),
+                                       _ffi.ptr(z), _ffi.ptr(mean), _ffi.ptr(logvar), _ffi.ptr(iters), _ffi.ptr(tr), R, int(max_iter),
+                                       _ffi.current_stream())
+        _ffi.check(rc, "dfx_noise_opt_run")
+        return {"z": z, "mean": mean, "logvar": logvar, "iters_done": iters, "trace": tr}

@@ -94,9 +94,9 @@ class AnchorDiffAE(nn.Module):
         self.num_timesteps, self.num_anchors, self.npoints = int(num_timesteps), num_anchors, npoints
         # detach_anchor=False raises in the training forward (stage1_losses); detach_variance detaches a tensor the reference no longer reads
         # (anchor_gen.py:1013-1014 vs :1002), and learn_var / global_shift / global_scale / vertical_only are stored and never read by the
-        # reference (:95-102): accepted and without effect, like there; noise_reg_loss / reg_loss_weight only enter the language branches
-        # (:891,:911), which raise above (train_language).
+        # reference (:95-102): accepted and without effect, like there.
         self.detach_anchor, self.detach_variance = detach_anchor, detach_variance
+        self.noise_reg_loss, self.reg_loss_weight = noise_reg_loss, reg_loss_weight           # edit_latent / optimize_latent (:891, :911)
         self.fixed_id = [0] * num_anchors
         self.points_per_anchor = npoints // num_anchors
         self.ret_traj, self.ret_interval, self.save_pred_xstart = ret_traj, ret_interval, save_pred_xstart
@@ -128,6 +128,78 @@ class AnchorDiffAE(nn.Module):
             _unsupported("cache_noise(eval_whole=True) (the reference's branch raises ValueError at anchor_gen.py:819)")
         noise, idx = self.encoder.sample_noise(pcds, device, self.sample_noise_num)
         return noise[torch.arange(noise.shape[0], device=noise.device), idx]
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # Part re-configuration (tools/shape_edit.py, tools/optimize_noise.py): ONE evaluation of the objective, differentiable in the aligner
+    # noise ``z`` through training.AlignerTrainFn (dfx_aligner_train_forward / dfx_aligner_input_backward), so the reference's own loop
+    # (``Adam([z])`` + ``ReduceLROnPlateau``) runs on top unmodified.  Freeze the model (``requires_grad_(False)``): PointNetV2 in eval() has
+    # no backward, and with frozen weights the aligner's backward is the data-gradient chain alone.  Many problems at once, without the host
+    # round trips: ``editing.reconfigure_part`` / ``editing.invert_noise``.
+    def edit_latent(self, z, input, seg_flag, valid_id, ref_means, ref_vars, fix_ids, edit_part_id, edit_part_mean, edit_part_var, fit_weight=1):
+        """anchor_gen.py:872-893: {'fit_loss' (B,), 'edit_loss' (1,) or (), 'reg_loss' (B,) with ``noise_reg_loss``}.  The part codes are
+        computed without a graph (they do not depend on ``z``)."""
+        fit_loss_dict = dict()
+        with torch.no_grad():
+            part_code_means, _ = self.encoder.get_part_code(input, seg_flag)
+        part_code = part_code_means.transpose(1, 2)
+        mean, logvar = self.encoder.get_params_from_part_code(part_code, valid_id, noise=z)
+        fit_loss = (torch.cat([mean, logvar], dim=1) - torch.cat([ref_means, torch.log(ref_vars)], dim=1)) ** 2
+        fit_loss = fit_loss * (valid_id * fix_ids).unsqueeze(1)
+        fit_loss = fit_loss.sum(dim=(-1, -2)) / (valid_id * fix_ids).sum(dim=-1)
+        if edit_part_mean is not None:
+            edit_l_mean = torch.nn.functional.mse_loss(mean[..., edit_part_id], edit_part_mean)
+        else:
+            edit_l_mean = torch.zeros(1, device=mean.device)
+        if edit_part_var is not None:
+            edit_l_var = torch.nn.functional.mse_loss(logvar[..., edit_part_id], torch.log(edit_part_var))
+        else:
+            edit_l_var = torch.zeros(1, device=mean.device)
+        fit_loss_dict["fit_loss"] = fit_weight * fit_loss
+        fit_loss_dict["edit_loss"] = edit_l_var + edit_l_mean
+        if self.noise_reg_loss:
+            fit_loss_dict["reg_loss"] = self.reg_loss_weight * (z ** 2).sum(1)
+        return fit_loss_dict
+
+    def optimize_latent(self, pcds, z, device="cuda"):
+        """anchor_gen.py:895-913: the encoder's loss dict (prior terms, 'fit_loss' (B,)) at aligner noise ``z`` (B,1,noise_dim) or
+        (B,noise_dim), plus 'reg_loss'.  Goes through ``self.encoder(...)`` like the reference, reparameterisation draw included."""
+        _ctx, _mean_pp, _logvar_pp, _flag_pp, fit_los_dict, _ = self.encoder(pcds, device, noise=z if z.dim() == 3 else z.unsqueeze(1))
+        if self.noise_reg_loss:
+            fit_los_dict["reg_loss"] = self.reg_loss_weight * (z ** 2).sum(1)
+        return fit_los_dict
+
+    @torch.no_grad()
+    def cimle_forward(self, pcds, device="cuda", noise=None):
+        """anchor_gen.py:837-870: decode every shape under K given aligner noises ``noise`` (B,K,noise_dim) (default: 10 candidates of
+        ``sample_noise``).  Keys: "{k}_sample {i}" for every key of decode's dict, "sample prior {i}", "pred", "input", "input_ref",
+        "seg_mask", "pred_seg_mask", "ref_seg_mask", "shift", "scale"; everything on the CPU."""
+        inp = pcds["input"].to(device)
+        ref = pcds["ref"].to(device)
+        input_seg_mask = pcds["seg_mask"].to(device)
+        seg_mask = pcds["ref_seg_mask"].to(device)
+        valid_id = pcds["present"].to(device)
+        B, N, C = ref.shape
+        if noise is None:
+            noise, _ = self.encoder.sample_noise(pcds, device, 10)
+        noise = noise.detach()
+        if noise.dim() == 2:
+            noise = noise.unsqueeze(1)
+        K = noise.shape[1]
+        ctx, mean_pp, logvar_pp, _flag, _losses, _lat = self.encoder(pcds, device, noise=noise)
+        var_pp = torch.exp(logvar_pp)
+        priors = torch.randn_like(var_pp).transpose(1, 2) * torch.sqrt(var_pp.transpose(1, 2)) + mean_pp.transpose(1, 2)
+        seg_mask, valid_id = (t.repeat_interleave(K, dim=0) for t in (seg_mask, valid_id))
+        _pred = self.decode(mean_pp, ctx=ctx, device=device, variance=var_pp, anchor_assignments=seg_mask.to(torch.int32), valid_id=valid_id)
+        pred = {}
+        for i in range(K):
+            for k, v in _pred.items():
+                pred[f"{k}_sample {i}"] = _fold(v, K)[:, i]
+        for i in range(K):
+            pred[f"sample prior {i}"] = priors.reshape(B, K, N, C)[:, i]
+        pred["pred"] = _fold(_pred["pred"], K)[:, 0]
+        pred.update({"input": inp, "input_ref": ref, "seg_mask": input_seg_mask, "pred_seg_mask": seg_mask, "ref_seg_mask": pcds["ref_seg_mask"],
+                     "shift": pcds["shift"], "scale": pcds["scale"]})
+        return {k: v.detach().cpu() for k, v in pred.items()}
 
     # ------------------------------------------------------------------------------------------------------------------
     def forward(self, pcds, device="cuda", epoch=0, **kwargs):

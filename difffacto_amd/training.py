@@ -430,7 +430,7 @@ def _aligner_struct(tensors, cfg):
 
 class AlignerTrainFn(torch.autograd.Function):
     """PartAlignerTransformer.forward (part_encoders.py:88-143; the shipped cIMLE configuration) with its backward on libdfx's exact-fp32 training
-    kernels (aligner_train.hip): differentiable in the aligner's parameters and in part_code."""
+    kernels (aligner_train.hip): differentiable in the aligner's parameters, in part_code and in the cIMLE noise."""
 
     @staticmethod
     def forward(ctx, cfg, part_code, valid, noise, *params):
@@ -461,26 +461,36 @@ class AlignerTrainFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_mean, d_logvar):
         _check_first_backward(ctx, "AlignerTrainFn")
-        n_class, zdim = ctx.cfg[0], ctx.cfg[1]
+        n_class, zdim, noise_dim = ctx.cfg[0], ctx.cfg[1], ctx.cfg[4]
         dev = ctx.vd.device
-        views = _flat_slices([p.shape for p in ctx.ps], dev)
         dz = torch.empty(ctx.B, zdim, n_class, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        dn = torch.empty(ctx.B, noise_dim, dtype=torch.float32, device=dev) if ctx.needs_input_grad[3] else None
         dm = None if d_mean is None else _need(d_mean.contiguous(), "d_mean")
         dl = None if d_logvar is None else _need(d_logvar.contiguous(), "d_logvar")
-        w, g = _aligner_struct(ctx.ps, ctx.cfg), _aligner_struct(views, ctx.cfg)
+        w, lib = _aligner_struct(ctx.ps, ctx.cfg), _ffi.lib()
+        weights = any(ctx.needs_input_grad[4:])
+        out = (None,) * len(ctx.ps)
         with torch.cuda.device(dev):
-            _ffi.check(_ffi.lib().dfx_aligner_train_backward(w, ctx.ws_ptr, ctx.nbytes, ctx.vd.data_ptr(), _ffi.ptr(dm), _ffi.ptr(dl), g, _ffi.ptr(dz), ctx.B,
-                                                             _ffi.current_stream()), "dfx_aligner_train_backward")
+            if weights:
+                views = _flat_slices([p.shape for p in ctx.ps], dev)
+                g = _aligner_struct(views, ctx.cfg)
+                _ffi.check(lib.dfx_aligner_train_backward(w, ctx.ws_ptr, ctx.nbytes, ctx.vd.data_ptr(), _ffi.ptr(dm), _ffi.ptr(dl), g, _ffi.ptr(dz), ctx.B,
+                                                          _ffi.current_stream()), "dfx_aligner_train_backward")
+                out = tuple(_assign_or_return(ctx.leaves, views))
+            # frozen weights (noise optimization, anchor_gen.py:872-913): the data-gradient chain alone.  Weights AND noise requiring a gradient: a second
+            # pass of that chain over the saved activations for d_noise (rare; same kernels, so the two routes give d_noise the same bits)
+            if dn is not None or (dz is not None and not weights):
+                _ffi.check(lib.dfx_aligner_input_backward(w, ctx.ws_ptr, ctx.nbytes, ctx.vd.data_ptr(), _ffi.ptr(dm), _ffi.ptr(dl), _ffi.ptr(dn),
+                                                          None if weights else _ffi.ptr(dz), ctx.B, _ffi.current_stream()), "dfx_aligner_input_backward")
         ctx.ws = None
         ctx.ws_ptr = None
-        out = _assign_or_return(ctx.leaves, views)
         ctx.leaves = None
-        return (None, dz, None, None) + tuple(out)
+        return (None, dz, None, dn) + out
 
 
 def aligner_train_forward(params, part_code, valid, noise, n_class=4, zdim=256, n_heads=8, d_head=32, noise_dim=32, noise_scale=100.0):
     """`params`: dict state_dict-key (relative to the part aligner) -> fp32 cuda tensor.  Returns (mean, logvar), each (B, 3, n_class), differentiable in
-    the parameters and in part_code (valid / noise are data)."""
+    the parameters, in part_code and in noise (valid is data)."""
     depth = 0
     while f"transformer_blocks.{depth}.norm2.weight" in params:
         depth += 1

@@ -6,6 +6,12 @@ shapes, drift part anchors — each one dfx_compose_latents call + one persisten
 
 Without a checkpoint the networks are random-init (synthetic weights): the clouds are noise-shaped, the calls and shapes are real.
 Writes interpolate.npy (shapes, steps, N, 3), mix.npy (shapes, 1, N, 3), drift.npy (shapes, steps, N, 3) and their seg ids.
+
+    python examples/edit.py --reconfigure --shapes 4 --starts 3 --part 0
+
+re-configures instead: part --part of every shape is made 1.2 / 1.5 times larger along z (two candidate edits) and the other parts re-arrange
+themselves, by gradient descent on the aligner noise from --starts random starts per edit; all shapes x edits x starts rows are ONE
+dfx_noise_opt_run call and one chain launch (editing.reconfigure_part).  Writes reconfigure.npy (shapes, edits, N, 3): the best start per edit.
 """
 import argparse
 import os
@@ -31,6 +37,9 @@ def main():
     ap.add_argument("--checkpoint", default=None, help="reference checkpoint (Runner.save format: {'model': state_dict})")
     ap.add_argument("--out-dir", default="edits")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--reconfigure", action="store_true", help="edit the size of --part and let the other parts re-arrange (noise optimization)")
+    ap.add_argument("--starts", type=int, default=3, help="--reconfigure: random noise starts per candidate edit")
+    ap.add_argument("--max-iter", type=int, default=300, help="--reconfigure: iterations of the noise optimization")
     a = ap.parse_args()
 
     enc, diff = build(a.config, a.timesteps, a.precision, 0)
@@ -50,6 +59,27 @@ def main():
     g = torch.Generator().manual_seed(a.seed)
     codes = enc.sampler().flow_reverse(torch.randn(B, enc.zdim, enc.n_class, generator=g).cuda())   # part codes from the flow prior
     os.makedirs(a.out_dir, exist_ok=True)
+    if a.reconfigure:
+        # the shapes' own configuration: the aligner's parameters under one noise draw per shape
+        valid = torch.ones(B, enc.n_class)
+        mean, logvar = enc.sampler().part_aligner(codes, valid, torch.randn(B, enc.part_aligner.noise_dim, generator=g))
+        factors = torch.tensor([1.2, 1.5])
+        E, T = len(factors), a.starts
+        shape_row = np.repeat(np.arange(B), E * T)
+        var = torch.exp(logvar).cpu()
+        new_var = var[torch.as_tensor(shape_row), :, a.part].clone()
+        new_var[:, 2] *= factors.repeat_interleave(T).repeat(B)
+        out = editing.reconfigure_part(enc, diff, codes, mean.cpu(), var, a.part, new_var=new_var, shape_row=shape_row, max_iter=a.max_iter,
+                                       npoints=N, generator=g)
+        L = out["losses"]["L"].reshape(B, E, T)
+        best = L.argmin(2)                                                                            # the best start of every (shape, edit)
+        pick = (torch.arange(B * E, device=best.device) * T + best.reshape(-1))
+        pred = out["pred"][pick].reshape(B, E, N, 3)
+        np.save(os.path.join(a.out_dir, "reconfigure.npy"), pred.cpu().numpy())
+        np.save(os.path.join(a.out_dir, "reconfigure_seg.npy"), out["seg_mask"][pick].reshape(B, E, N).cpu().numpy())
+        print(f"reconfigure: {B * E * T} rows in one optimizer call, iterations {int(out['iters_done'].min())}..{int(out['iters_done'].max())}, "
+              f"best loss per (shape, edit) {[[round(float(x), 4) for x in row] for row in L.min(2)[0].cpu()]} -> {a.out_dir}/reconfigure.npy {tuple(pred.shape)}")
+        return
     runs = {
         "interpolate": lambda: editing.interpolate_part(enc, diff, codes, a.part, a.steps, npoints=N, generator=g),
         "mix": lambda: editing.mix_parts(enc, diff, codes, np.stack([np.roll(np.arange(B), -j) for j in range(enc.n_class)], 1),

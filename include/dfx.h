@@ -379,6 +379,47 @@ int dfx_aligner_train_forward(const dfx_latent_weights *w, void *workspace, size
 int dfx_aligner_train_backward(const dfx_latent_weights *w, void *workspace, size_t workspace_bytes, const float *valid, const float *d_mean,
                                const float *d_logvar, const dfx_latent_weights *grads, float *d_part_code, int B, dfx_stream_t stream);
 
+/* The data-gradient half of dfx_aligner_train_backward, for callers that differentiate in the INPUTS only (frozen weights; the noise optimization
+ * below): runs after dfx_aligner_train_forward on the same workspace, the same dH chain (same kernels, same order: d_part_code has the bits
+ * dfx_aligner_train_backward writes), no weight-gradient product, column sum or LayerNorm-parameter launch and no `grads` struct.
+ *   d_noise (B,noise_dim) or NULL: d_noise[r,c] = noise_scale * sum_j dX0[(r,j), zdim + c], j ascending (the transpose of the token build; no atomics)
+ *   d_part_code (B,zdim,n_class) or NULL; at least one of the two is given.  Arguments are checked before the first HIP call. */
+int dfx_aligner_input_backward(const dfx_latent_weights *w, void *workspace, size_t workspace_bytes, const float *valid, const float *d_mean,
+                               const float *d_logvar, float *d_noise, float *d_part_code, int B, dfx_stream_t stream);
+
+/* Part re-configuration editing: gradient descent on the aligner's cIMLE noise z (tools/shape_edit.py:80-129 around AnchorDiffAE.edit_latent,
+ * anchor_gen.py:872-893, + parse_losses; tools/optimize_noise.py / optimize_latent :895-913 with both selectors zero and fix = valid), R independent
+ * problems per call (noise_opt.hip).  Per row r, J = n_class:
+ *   fit  = sum_{c<3,j} fix[r,j] ((mean - fit_mean)^2 + (logvar - fit_logvar)^2)[r,c,j] / sum_j fix[r,j]      fix = valid * fix_ids, not all zero
+ *   edit = sum_j edit_mean_sel[r,j] (1/3) sum_c (mean - edit_mean)^2[r,c,j] + sum_j edit_var_sel[r,j] (1/3) sum_c (logvar - edit_logvar)^2[r,c,j]
+ *   reg  = sum_c z[r,c]^2;     L = fit_weight fit + edit + reg_weight reg
+ * Every row has its own torch.optim.Adam state (amsgrad off), ReduceLROnPlateau (mode min, threshold mode rel, cooldown 0) on L and stop flag
+ * (|L - prev| <= stop_atol + stop_rtol |prev|, prev starting at 0, as torch.allclose); a stopped row is never written again.  UNLIKE the reference,
+ * whose batch mean couples the rows of a batch, no row sees another one: a row gives the same bits alone and inside any batch.
+ * All pointers are device pointers; (R,3,J) targets, (R,J) masks; a selector and its target are NULL together (= that term is absent). */
+typedef struct {
+  const float *fit_mean, *fit_logvar, *fix;
+  const float *edit_mean, *edit_mean_sel;
+  const float *edit_logvar, *edit_var_sel;
+  double fit_weight, reg_weight;
+  double lr0, beta1, beta2, adam_eps;                 /* reference: 1, 0.9, 0.999, 1e-8 */
+  double factor, threshold, min_lr, lr_eps;           /* reference: 0.5, 1e-4, 5e-2, 1e-8 */
+  double stop_atol, stop_rtol;                        /* reference: 1e-8, 1e-5 */
+  int32_t patience;                                   /* reference: 10 */
+} dfx_noise_opt_problem;
+
+/*   workspace: dfx_noise_opt_workspace_bytes(w, R) device bytes (0 for a configuration the training kernels do not take)
+ *   part_code (R,zdim,J), valid (R,J); z (R,noise_dim): in = the start, out = the result; mean / logvar (R,3,J): the aligner's output at the
+ *   RETURNED z; iters_done (R): iterations a row took part in (a row that stops at iteration s: s + 1)
+ *   trace (max_iter,R,5 + 2 noise_dim) or NULL: L, fit, edit, reg, the learning rate of this iteration's Adam step, z before the step, the total
+ *   gradient (d_noise + 2 reg_weight z); zeros for the iterations after a row stopped.
+ * Enqueues max_iter x [aligner forward, loss, input backward, step] and a final forward on `stream`, with no host synchronization except one
+ * read of the stopped-row count every 32 iterations (to stop enqueuing once every row is frozen; no result depends on it). */
+size_t dfx_noise_opt_workspace_bytes(const dfx_latent_weights *w, int R);
+int dfx_noise_opt_run(const dfx_latent_weights *w, void *workspace, size_t workspace_bytes, const dfx_noise_opt_problem *p, const float *part_code,
+                      const float *valid, float *z, float *mean, float *logvar, int32_t *iters_done, float *trace, int R, int max_iter,
+                      dfx_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * PointNet++ set-abstraction / feature-propagation layers, eval mode — the part of
  * pointnet2_ops the reference leaves to PyTorch: QueryAndGroup / GroupAll
