@@ -102,6 +102,12 @@ SIGNATURES = {
     "dfx_part_clouds_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dfx_part_box_pairwise_f32": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _U64, ctypes.c_longlong, _P, _P, _P]),
     "dfx_debug_part_box_units": (_I, [_U64, ctypes.c_longlong, _I, _I, _P, _P]),
+    "dfx_occupancy_num_cells": (_I, [_I, _I]),
+    "dfx_occupancy_cell_mask": (_I, [_I, _I, _P]),
+    "dfx_occupancy_grid_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "dfx_occupancy_jsd_f64": (_I, [_P, _P, _I, _P, _P]),
+    "dfx_occupancy_entropy_f64": (_I, [_P, _I, ctypes.c_int64, _P, _P]),
+    "dfx_debug_occupancy_host": (_I, [_P, _I, _I, _I, _P]),
     "dfx_denoiser_create": (_I, [ctypes.POINTER(_P), ctypes.POINTER(DenoiserWeights), _I, _D, _D, _I, _P]),
     "dfx_denoiser_destroy": (None, [_P]),
     "dfx_denoiser_num_timesteps": (_I, [_P]),

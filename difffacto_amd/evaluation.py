@@ -5,8 +5,10 @@ python/difffacto/datasets/evaluation_utils.py (``emd_approx`` :84-89, ``EMD_CD``
 The distance work (nearest-neighbour scans, the auction) is native; what remains in torch is bookkeeping on the small
 (N_sample x N_ref) distance matrices.  Point clouds are (num_clouds, n, 3) float32 device tensors.
 
-The part-level metrics of the gen_part evaluation (snapping, part boxes, per-part metrics; ``evaluate_gen_part``) follow below."""
+The part-level metrics of the gen_part evaluation (snapping, part boxes, per-part metrics; ``evaluate_gen_part``) follow below,
+then the occupancy-grid JSD (``jsd_between_point_cloud_sets`` :568-583 and its helpers, ``part_jsd``)."""
 import functools
+import warnings
 
 import numpy as np
 import torch
@@ -478,3 +480,162 @@ def evaluate_gen_part(results, class_choice, n_class=4, batch_size=32, seed=None
     metrics.update(part)
     metrics.update(bbox)
     return metrics
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Occupancy-grid JSD (evaluation_utils.py:544-648, from latent_3d_points): every point goes to its nearest cell of a resolution^3
+# grid in the unit cube, clipped to the sphere of radius 0.5; the JSD compares the two sets' per-cell point counts.  The point work
+# (nearest kept cell, counters) and the reductions run in libdfx's occupancy.hip on integer counters: the same cells and counts as
+# the reference's KD-tree, an exact tie going to the lower cell index.  Clouds are read as float32.
+OCCUPANCY_MAX_RESOLUTION = 40
+OCCUPANCY_MAX_CLASSES = 16
+
+
+def occupancy_num_cells(resolution, in_sphere=True):
+    """Kept cells of the grid (host only)."""
+    n = _ffi.lib().dfx_occupancy_num_cells(int(resolution), int(bool(in_sphere)))
+    if n < 0:
+        _ffi.check(n, "dfx_occupancy_num_cells")
+    return n
+
+
+def occupancy_cell_mask(resolution, in_sphere=True):
+    """The keep mask (R,R,R) bool, C order (host only)."""
+    R = int(resolution)
+    mask = np.zeros((R, R, R) if 2 <= R <= OCCUPANCY_MAX_RESOLUTION else (1,), np.uint8)
+    _ffi.check(_ffi.lib().dfx_occupancy_cell_mask(R, int(bool(in_sphere)), mask.ctypes.data_as(_ffi.c_fp)), "dfx_occupancy_cell_mask")
+    return mask.astype(bool)
+
+
+def occupancy_grid(pclouds, labels=None, n_class=0, resolution=28, in_sphere=True, return_index=False, out=None):
+    """Native occupancy counters of B clouds (B,N,3): -> (counters int64 (rows,cells), bernoulli int32 (rows,cells), cell_index int32
+    (B,N) or None, n_bad int32 (1,)) on the device; rows = n_class + 1 with ``labels`` (B,N) (row 0 = every point, row 1 + c = the
+    points labelled c), else 1.  ``out`` = (counters, bernoulli, n_bad) of an earlier call is added to (chunked sets).  Shapes, dtypes
+    and devices are checked here, before a pointer reaches the library: ValueError."""
+    x = _dev_cloud(pclouds)
+    if x.dim() != 3 or x.shape[2] != 3 or x.shape[0] == 0 or x.shape[1] == 0:
+        raise ValueError(f"occupancy_grid: clouds of shape {tuple(x.shape)}, expected (B,N,3) with B, N > 0")
+    B, N, _ = x.shape
+    lab = None if labels is None else _dev_labels(labels, x.device)
+    if lab is not None:
+        if tuple(lab.shape) != (B, N):
+            raise ValueError(f"occupancy_grid: labels of shape {tuple(lab.shape)}, expected {(B, N)}")
+        if not 0 <= int(n_class) <= OCCUPANCY_MAX_CLASSES:
+            raise ValueError(f"occupancy_grid: n_class = {n_class} outside [0,{OCCUPANCY_MAX_CLASSES}]")
+    rows = 1 if lab is None else int(n_class) + 1
+    cells = occupancy_num_cells(resolution, in_sphere)
+    if out is None:
+        counters = torch.empty(rows, max(cells, 1), dtype=torch.int64, device=x.device)
+        bern = torch.empty(rows, max(cells, 1), dtype=torch.int32, device=x.device)
+        n_bad = torch.empty(1, dtype=torch.int32, device=x.device)
+    else:
+        counters, bern, n_bad = out
+        for name, t, shape, dtype in (("counters", counters, (rows, cells), torch.int64), ("bernoulli", bern, (rows, cells), torch.int32),
+                                      ("n_bad", n_bad, (1,), torch.int32)):
+            if not (torch.is_tensor(t) and tuple(t.shape) == shape and t.dtype == dtype and t.device == x.device and t.is_contiguous()):
+                raise ValueError(f"occupancy_grid: out's {name} must be a contiguous {dtype} tensor of shape {shape} on {x.device}, got "
+                                 f"{(tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t) else type(t).__name__}")
+    index = torch.empty(B, N, dtype=torch.int32, device=x.device) if return_index else None
+    with torch.cuda.device(x.device):
+        _ffi.check(_ffi.lib().dfx_occupancy_grid_f32(_ffi.ptr(x), _ffi.ptr(lab), B, N, int(n_class), int(resolution), int(bool(in_sphere)),
+                                                     int(out is not None), _ffi.ptr(counters), _ffi.ptr(bern), _ffi.ptr(index),
+                                                     _ffi.ptr(n_bad), _ffi.current_stream()), "dfx_occupancy_grid_f32")
+    return counters, bern, index, n_bad
+
+
+def _require_finite(n_bad, what):
+    n = int(n_bad.item())
+    if n:
+        raise ValueError(f"{what}: input contains {n} point(s) with NaN or infinity")
+
+
+_COUNT_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+
+
+def _device_jsd(P, Q):
+    """P, Q: contiguous int64 vectors of one length on one device."""
+    assert P.device == Q.device and P.dtype == Q.dtype == torch.int64 and P.shape == Q.shape and P.dim() == 1, (P.device, Q.device, P.shape, Q.shape)
+    out = torch.empty(1, dtype=torch.float64, device=P.device)
+    with torch.cuda.device(P.device):
+        _ffi.check(_ffi.lib().dfx_occupancy_jsd_f64(_ffi.ptr(P), _ffi.ptr(Q), P.numel(), _ffi.ptr(out), _ffi.current_stream()),
+                   "dfx_occupancy_jsd_f64")
+    return out
+
+
+def unit_cube_grid_point_cloud(resolution, clip_sphere=False):
+    """(grid, spacing) (:547-565): the cell centres of a resolution^3 grid in the unit cube, float32 (R,R,R,3); with clip_sphere the
+    cells inside the sphere of radius 0.5, (cells,3) in C order."""
+    R = int(resolution)
+    spacing = 1.0 / float(R - 1)
+    axis = (np.arange(R, dtype=np.float64) * spacing - 0.5).astype(np.float32)
+    grid = np.stack(np.meshgrid(axis, axis, axis, indexing="ij"), -1)
+    if clip_sphere:
+        grid = grid.reshape(-1, 3)[occupancy_cell_mask(R, True).reshape(-1)]
+    return grid, spacing
+
+
+def entropy_of_occupancy_grid(pclouds, grid_resolution, in_sphere=False, verbose=False):
+    """(entropy, counters) (:586-626): counters (cells,) float64 numpy = points per cell over all clouds; entropy = the mean over the
+    cells of the entropy (nats) of "the cell is occupied in a cloud".  Non-finite input raises ValueError (sklearn's check)."""
+    x = _dev_cloud(pclouds)
+    if verbose:
+        bound = 0.5 + 10e-4
+        if float(x.max().abs()) > bound or float(x.min().abs()) > bound:
+            warnings.warn("Point-clouds are not in unit cube.")
+        if in_sphere and float(x.square().sum(2).sqrt().max()) > bound:
+            warnings.warn("Point-clouds are not in unit sphere.")
+    counters, bern, _, n_bad = occupancy_grid(x, resolution=grid_resolution, in_sphere=in_sphere)
+    _require_finite(n_bad, "entropy_of_occupancy_grid")
+    ent = torch.empty(1, dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        _ffi.check(_ffi.lib().dfx_occupancy_entropy_f64(_ffi.ptr(bern), bern.shape[1], x.shape[0], _ffi.ptr(ent), _ffi.current_stream()),
+                   "dfx_occupancy_entropy_f64")
+    return np.float64(ent.item()), counters[0].cpu().numpy().astype(np.float64)
+
+
+def jensen_shannon_divergence(P, Q):
+    """JSD in bits of two count vectors (:629-648), np.float64.  Two integer tensors of which one is on a device go to the native
+    fixed-order reduction there (the other one is moved to it); anything else, float weights included, is summed with numpy on the
+    host."""
+    if torch.is_tensor(P) and torch.is_tensor(Q) and (P.is_cuda or Q.is_cuda) and P.dtype in _COUNT_DTYPES and Q.dtype in _COUNT_DTYPES:
+        device = P.device if P.is_cuda else Q.device
+        P, Q = P.to(device=device, dtype=torch.int64), Q.to(device=device, dtype=torch.int64)
+        if bool((P < 0).any()) or bool((Q < 0).any()):
+            raise ValueError("Negative values.")
+        if P.shape != Q.shape:
+            raise ValueError("Non equal size.")
+        return np.float64(_device_jsd(P.reshape(-1).contiguous(), Q.reshape(-1).contiguous()).item())
+    P = np.asarray(P.cpu() if torch.is_tensor(P) else P, np.float64)
+    Q = np.asarray(Q.cpu() if torch.is_tensor(Q) else Q, np.float64)
+    if np.any(P < 0) or np.any(Q < 0):
+        raise ValueError("Negative values.")
+    if len(P) != len(Q):
+        raise ValueError("Non equal size.")
+
+    def bits(v):
+        v = v[v > 0]
+        return -np.sum(v * np.log(v)) / np.log(2.0)
+    P_, Q_ = P / np.sum(P), Q / np.sum(Q)
+    return np.float64(bits((P_ + Q_) / 2.0) - (bits(P_) + bits(Q_)) / 2.0)
+
+
+def jsd_between_point_cloud_sets(sample_pcs, ref_pcs, resolution=28):
+    """JSD between two sets of clouds (S,N,3) inside the unit cube (:568-583): occupancy counters on the sphere-clipped grid."""
+    cs, _, _, bad_s = occupancy_grid(sample_pcs, resolution=resolution, in_sphere=True)
+    cr, _, _, bad_r = occupancy_grid(_dev_cloud(ref_pcs).to(cs.device), resolution=resolution, in_sphere=True)
+    out = _device_jsd(cs[0], cr[0])
+    _require_finite(bad_s + bad_r, "jsd_between_point_cloud_sets")
+    return np.float64(out.item())
+
+
+def part_jsd(preds, preds_mask, refs, refs_mask, n_class=4, resolution=28):
+    """{"jsd": whole shapes, "part_c_jsd": the points labelled c} from one counting pass per set (labels outside [0,n_class) count in
+    "jsd" only).  A part without points in either set gives NaN."""
+    cp, _, _, bad_p = occupancy_grid(preds, preds_mask, n_class, resolution, True)
+    cr, _, _, bad_r = occupancy_grid(_dev_cloud(refs).to(cp.device), refs_mask, n_class, resolution, True)
+    vals = torch.cat([_device_jsd(cp[r], cr[r]) for r in range(n_class + 1)])
+    empty = ((cp.sum(1) == 0) | (cr.sum(1) == 0)).cpu()
+    _require_finite(bad_p + bad_r, "part_jsd")
+    vals = vals.cpu().numpy()
+    vals[empty.numpy()] = np.nan
+    return {("jsd" if r == 0 else f"part_{r - 1}_jsd"): np.float64(vals[r]) for r in range(n_class + 1)}

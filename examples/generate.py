@@ -3,7 +3,7 @@
 configs/gen_*.py, anchor_gen.py:1034-1084): latent sampler -> fused reverse chain -> optional generation metrics.
 
     python examples/generate.py --config gen_chair --shapes 32 --K 2 --timesteps 100 [--checkpoint pretrained/chair.pth]
-                                [--ddim 25] [--metrics] [--out clouds.npy]
+                                [--ddim 25] [--metrics [--jsd]] [--out clouds.npy]
 
 Without a checkpoint the networks are random-init (synthetic weights): the clouds are noise-shaped, the timings are real.
 """
@@ -52,9 +52,12 @@ def main():
     ap.add_argument("--precision", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--checkpoint", default=None, help="reference checkpoint (Runner.save format: {'model': state_dict})")
     ap.add_argument("--metrics", action="store_true", help="MMD / COV / 1-NNA of the first half of the clouds against the second")
+    ap.add_argument("--jsd", action="store_true", help="with --metrics: occupancy-grid JSD of the two halves, whole shapes and per part")
     ap.add_argument("--out", default=None)
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
+    if a.jsd and not a.metrics:
+        ap.error("--jsd adds to the generation metrics: pass --metrics as well")
 
     enc, diff = build(a.config, a.timesteps, a.precision, a.ddim)
     if a.checkpoint:
@@ -92,6 +95,10 @@ def main():
         m = n // 2
         t0 = time.perf_counter()
         res = compute_all_metrics(unit[:m].contiguous(), unit[m:2 * m].contiguous(), batch_size=32)
+        if a.jsd:   # the evaluation's [-1, 1] normalisation, scaled into the unit cube (exact in fp32)
+            from difffacto_amd.evaluation import _normalize_shapes, part_jsd
+            half, seg = _normalize_shapes(pred) * 0.5, out["pred_seg_mask"]
+            res.update(part_jsd(half[:m].contiguous(), seg[:m], half[m:2 * m].contiguous(), seg[m:2 * m], n_class=4))
         torch.cuda.synchronize()
         print(f"metrics of clouds[:{m}] vs clouds[{m}:{2 * m}] ({time.perf_counter() - t0:.1f} s): " + ", ".join(f"{k} {float(v):.4g}" for k, v in sorted(res.items())))
 

@@ -283,6 +283,42 @@ int dfx_part_box_pairwise_f32(const float *boxes_a, const int32_t *present_a, in
                               const float *units, float *D, dfx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Occupancy-grid JSD — unit_cube_grid_point_cloud, entropy_of_occupancy_grid, jensen_shannon_divergence and
+ * jsd_between_point_cloud_sets of python/difffacto/datasets/evaluation_utils.py:544-648.  occupancy.hip, DESIGN.md §5.9.
+ * The grid: R = resolution in [2,40] cells per axis, axis value a[i] = float32(i * (1.0 / (R - 1)) - 0.5) (product and
+ * difference in double); with in_sphere a cell (i,j,k) is kept when the float32 sqrt((x*x + y*y) + z*z) <= 0.5f (numpy's norm of a
+ * float32 row, no contraction); kept cells are numbered in C order over (i,j,k): the compact index.  A point belongs to the
+ * kept cell with the smallest (dx*dx + dy*dy) + dz*dz, coordinates widened to double and every operation rounded to double
+ * (sklearn's KD-tree on the same grid); an exact tie goes to the lower compact index.
+ * ------------------------------------------------------------------------------------------ */
+
+/* Number of kept cells (host only; no GPU call).  < 0 on error (resolution outside [2,40]). */
+int dfx_occupancy_num_cells(int resolution, int in_sphere);
+
+/* The keep mask, HOST uint8 (R,R,R) in C order: 1 = kept (host only; no GPU call). */
+int dfx_occupancy_cell_mask(int resolution, int in_sphere, uint8_t *host_mask);
+
+/* Counts the points of B clouds xyz (B,N,3) into the grid.  rows = C + 1 with labels (int32 (B,N), 0 <= C <= 16), else 1 (labels
+ * NULL, C ignored): row 0 takes every point, row 1 + c the points labelled c; a label outside [0,C) counts in row 0 only.
+ * counters int64 (rows,cells): points per cell.  bernoulli int32 (rows,cells): clouds with at least one point in the cell.
+ * cell_index int32 (B,N), nullable: the compact index per point.  A point with a non-finite coordinate is counted nowhere but in
+ * n_bad (int32, 1) and gets cell_index -1.  accumulate == 0: counters, bernoulli and n_bad are zeroed first; != 0: added to, so
+ * a large set can be fed in chunks.  Integer counting: the result does not depend on scheduling.  The first call per
+ * (device, resolution, in_sphere) allocates the grid's column table (at most 6.7 KB, kept for the life of the process) and uploads
+ * it with a blocking copy; on a capturing stream that first call is refused (make one call outside the capture first).  Fails for
+ * a grid without kept cells (R = 2 with in_sphere). */
+int dfx_occupancy_grid_f32(const float *xyz, const int32_t *labels, int B, int N, int C, int resolution, int in_sphere,
+                           int accumulate, int64_t *counters, int32_t *bernoulli, int32_t *cell_index, int32_t *n_bad,
+                           dfx_stream_t stream);
+
+/* jsd (double, 1) = H((P+Q)/2) - (H(P) + H(Q))/2 in bits, P = counters_p / sum, Q = counters_q / sum (rows of `cells` int64);
+ * fixed-order fp64 sums: bit-reproducible, and exactly 0 for equal rows.  NaN when a row sums to 0. */
+int dfx_occupancy_jsd_f64(const int64_t *counters_p, const int64_t *counters_q, int cells, double *jsd, dfx_stream_t stream);
+
+/* entropy (double, 1) = sum over cells with bernoulli > 0 of H([p, 1 - p]) in nats, p = bernoulli / n_shapes, divided by cells. */
+int dfx_occupancy_entropy_f64(const int32_t *bernoulli, int cells, int64_t n_shapes, double *entropy, dfx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Latent sampler — the once-per-batch producer of decode's inputs:
  * PartEncoder.sample_latents (python/difffacto/models/encoders/part_encoders.py:1052-1110) =
  * per-part normalising flows run in reverse (python/difffacto/models/encoders/flow.py:21-47,58-72)

@@ -81,6 +81,9 @@ void dfx_debug_trace(void *device_buf, int capacity);
 int dfx_debug_latents_stub(dfx_latents **out, int n_class, int zdim, int cimle, int noise_dim);
 /* The unit draws dfx_part_box_pairwise_f32 makes without `units` for global pairs pair0 .. pair0+P-1: units (P,C,2,512,3) device. */
 int dfx_debug_part_box_units(uint64_t seed, long long pair0, int P, int C, float *units, dfx_stream_t stream);
+/* Host-side run (no GPU) of k_occupancy's per-point search, compiled from the kernel's own functions: the compact cell index of n HOST
+ * points (n,3) on the grid of dfx_occupancy_grid_f32, -1 for a non-finite point. */
+int dfx_debug_occupancy_host(const float *host_xyz, int n, int resolution, int in_sphere, int32_t *host_cell_index);
 
 #ifdef __cplusplus
 }

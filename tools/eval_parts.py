@@ -3,10 +3,11 @@
 and whole-shape MMD / COV / 1-NNA, merged as ShapeNetSeg.evaluate does (evaluation.evaluate_gen_part).
 
     python tools/eval_parts.py SAMPLES REFS [--class Chair] [--n-class 4] [--thresh 1.0] [--cov-thresh 100]
-                               [--metric chamfer|iou|l2] [--no-nn] [--seed S]
+                               [--metric chamfer|iou|l2] [--no-nn] [--seed S] [--jsd]
 
 SAMPLES / REFS: a `bench.py --dump-outputs` folder (clouds.npy (M,N,3), seg_mask.npy (M,N)) or an .npz with `clouds` and `seg_mask`.
---thresh / --cov-thresh / --metric / --no-nn set the box metric as the offline tool's flags do."""
+--thresh / --cov-thresh / --metric / --no-nn set the box metric as the offline tool's flags do.  --jsd adds the occupancy-grid JSD of the
+whole shapes (`jsd`) and of every part (`part_k_jsd`), on the normalised clouds scaled by 0.5 into the unit cube."""
 import argparse
 import json
 import os
@@ -37,6 +38,7 @@ def main():
     ap.add_argument("--metric", default="chamfer", choices=sorted(ev.BOX_METRIC_IDS))
     ap.add_argument("--no-nn", action="store_true")
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--jsd", action="store_true")
     a = ap.parse_args()
     (xs, ms), (xr, mr) = load(a.samples), load(a.refs)
     results = [dict(pred=torch.from_numpy(xs.astype(np.float32)), pred_seg_mask=torch.from_numpy(ms.astype(np.int64)),
@@ -48,6 +50,8 @@ def main():
     out.update(ev.compute_part_metric(p, pm, r, rm, 32, n_class=a.n_class))
     out.update(ev.compute_bbox_metric(p, pm, r, rm, 32, n_class=a.n_class, thresh=a.thresh, metric=a.metric, no_nn=a.no_nn,
                                       cov_thresh=a.cov_thresh, seed=a.seed))
+    if a.jsd:
+        out.update(ev.part_jsd(p * 0.5, pm, r * 0.5, rm, n_class=a.n_class))
     print(json.dumps({k: float(v) for k, v in out.items()}, indent=1))
 
 
