@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "denoiser_internal.h"
+#include "denoiser_plan.h"   // (ahead of the pragma: the planner's cost arithmetic is not contracted)
 
 #pragma clang fp contract(fast)
 
@@ -854,7 +855,6 @@ __global__ void __launch_bounds__(NW * 64) k_denoise(const KParams p) {
 //        management barrier of r) finished at least one barrier earlier.
 // Wavefronts per workgroup: 8 (256 points) when that fills the chip; 4 or 2 for small batches, so that a single shape still
 // spreads over 16 / 32 CUs (same per-wave instruction stream, bit-identical results; the ring then takes 6 / 12 pieces per wave).
-constexpr int PIPE_NW = 8;
 constexpr int SLOT_BYTES = 24 * 1024;
 constexpr int NSLOT = 5;   // records in flight ahead of the compute: NSLOT - 2
 
@@ -2308,7 +2308,6 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams 
 // registers round 0 of phase H has freed).  The next block's attention record | c_t row | b2 are fetched by LDS-DMA during phase H into the other half of
 // a double buffer.  One workgroup per CU (128 fragment registers), LDS 77 KiB.
 constexpr int C16_NW = 8, C16_PTS = 16;
-constexpr double C16_ROUND_MS = 1e9;   // ms per round of g_num_cus workgroups at N = 2048, T = 1000 (launch()'s cost model; 1e9 = never chosen automatically until measured)
 constexpr int C16_XN = 0;                                            // 4 x 64 uint4: LN3 output, B fragments of the four k-steps
 constexpr int C16_HID = C16_XN + 4 * 1024;                           // 16 x 64 uint4: GELU output, B fragment of every 32-unit chunk
 constexpr int C16_AT = C16_HID + FF_CHUNKS * 1024;                   // 2 x [attention record 17 KiB | c_t row 1 KiB | b2 1 KiB]
@@ -2948,10 +2947,25 @@ __global__ void k_mse_finish(const double *acc, float *loss, int has_flags, doub
 }
 
 bool g_force_direct = false;
-int g_force_nw = 0;       // debug: wavefronts per workgroup of the pipelined kernel (0 = by batch size)
-int g_num_cus = 256;
+int g_force_nw = 0;       // debug: code of dfx_debug_pipe_waves (denoiser_plan.h: force_from_code)
+int g_num_cus = 256;      // the MI355X's; never read from the device
 unsigned long long *g_trace = nullptr;
 int g_trace_cap = 0;
+
+// The kernels in the order of denoiser_plan.h's Variant, with their dynamic LDS bytes
+struct VariantKernel {
+  void (*kernel)(KParams);
+  int lds;
+};
+const VariantKernel KERNELS[NUM_VARIANTS] = {
+    {k_denoise_pipe<8>, PipeCfg<8>::L_TOTAL},     {k_denoise_pipe<4>, PipeCfg<4>::L_TOTAL},     {k_denoise_pipe<2>, PipeCfg<2>::L_TOTAL},
+    {k_denoise_pipe2, P2_LDS},                    {k_denoise_coop, CL_TOTAL},                   {k_denoise_coop2, C2_TOTAL},
+    {k_denoise_coop16, C16_TOTAL},                {k_denoise_pipe_f32<8>, PipeCfg<8>::L_TOTAL}, {k_denoise_pipe_f32<4>, PipeCfg<4>::L_TOTAL},
+    {k_denoise_pipe_f32<2>, PipeCfg<2>::L_TOTAL}, {k_denoise<DFX_PREC_BF16, 4>, 0},             {k_denoise<DFX_PREC_F32, 4>, 0},
+};
+static_assert(info(Variant::Pipe2Tiles).threads == P2_NW * 64 && info(Variant::Coop).threads == COOP_NW * 64 && info(Variant::Coop2).threads == COOP_NW * 64 &&
+                  info(Variant::Coop16).threads == C16_NW * 64 && info(Variant::Coop16).points == C16_PTS && info(Variant::Pipe8).points == PipeCfg<8>::PTS,
+              "denoiser_plan.h's table against the kernels' launch bounds");
 
 int launch(const dfx_denoiser *d, const void *shape_ctx, KParams &p, hipStream_t st) {
   ShapeCtxView v;
@@ -2962,85 +2976,23 @@ int launch(const dfx_denoiser *d, const void *shape_ctx, KParams &p, hipStream_t
   p.as_ms = v.as_ms;
   p.trace = g_trace;
   p.trace_cap = g_trace_cap;
-  constexpr int NW = 4;
-  const int fnw = g_force_nw == 161 ? 0 : g_force_nw;   // 161 = automatic, with k_denoise_coop16 ruled out (A/B of the launcher's choice)
-  const long long waves = ((long long)p.B * p.N) / 32;
-  const long long grid = (waves + NW - 1) / NW;
-  if (grid > 0x7fffffffLL) return set_error(DFX_ERR_INVALID_ARG, "denoiser: B*N too large");
-  // Which kernel: the pipelined one works on tiles of nw x 32 points of one shape (a partial last tile idles whole wavefronts) with
-  // nw = 8, 4 or 2 wavefronts per workgroup — the per-wave instruction stream and the results are the same, fewer wavefronts spread a
-  // small batch over more CUs; the co-operative one (k_denoise_coop) puts eight wavefronts on ONE 32-point tile.  One workgroup per CU
-  // either way, so a launch runs in rounds of g_num_cus workgroups, and the cheapest estimate wins.  Per-round costs as measured at
-  // N = 2048, T = 1000 (profiles/r02_small_batch_sweep.txt; only their ratios matter): co-operative 32.7 ms, pipelined 86.5 / 88.5 /
-  // 93.5 ms for nw = 2 / 4 / 8, times 1 + 0.36 L^4 for a round that fills the fraction L of the chip's wavefront slots (the power cap).
-  auto tiles = [&](int nw) { return (long long)((p.N + nw * 32 - 1) / (nw * 32)); };
-  auto rounds_cost = [&](long long wgs, double base, double fill_per_wg) {
-    const long long full = wgs / g_num_cus, rest = wgs % g_num_cus;
-    auto f = [](double L) { return 1.0 + 0.36 * L * L * L * L; };
-    return base * (full * f(g_num_cus * fill_per_wg) + (rest ? f(rest * fill_per_wg) : 0.0));
-  };
-  // (a bf16 engine without the W1 bias fold — DenoiserDev::w1_fold = 0: every hidden channel is an outlier of some block's W1', or the debug
-  // switch — has the plain pack, which only the direct kernel and k_denoise_coop16 read: the other chain kernels take b1' from slot 127)
-  const bool bf16 = d->dev.prec == DFX_PREC_BF16 && !g_force_direct && d->dev.w1_fold;
-  const bool f32 = d->dev.prec == DFX_PREC_F32 && !g_force_direct;
-  int nw = PIPE_NW;
-  double best = 1e300;
-  for (int c = 8; c >= 2; c >>= 1) {
-    if (tiles(c) * c * 32 > 3LL * p.N && c > 2) continue;   // padding of a small shape
-    const double cost = rounds_cost(tiles(c) * p.B, c == 8 ? 93.5 : c == 4 ? 88.5 : 86.5, c / (8.0 * g_num_cus));
-    if (cost < best) best = cost, nw = c;
-  }
-  const bool pipe2 = bf16 && fnw == 64 && tiles(8) * 256 <= 3LL * p.N;   // two tiles per wavefront (k_denoise_pipe2): 256-point workgroup tiles
-  if (fnw > 1 && fnw != 64 && fnw != 16 && fnw < 160) nw = fnw;
-  if (pipe2) nw = 8;
-  const long long wpg = tiles(nw);
-  // (~3x faster per point than the direct kernel: taken unless the padding of a small shape eats that factor)
-  const bool pipe = bf16 && wpg * nw * 32 <= 3LL * p.N;
-  // the exact-fp32 chain: same tiling; ~3x the direct kernel's rate per point, so a padded small shape may still take it
-  const bool pipe_f32 = f32 && fnw != 1 && wpg * nw * 32 <= 3LL * p.N;
-  const bool coop = bf16 && !pipe2 && (fnw == 1 || (fnw == 16 && p.N % 64 != 0) || (fnw == 0 && (pipe ? rounds_cost(waves, 32.7, 0.0) < best : waves <= g_num_cus)));   // (16 = two tiles per workgroup: needs N % 64 == 0, else this one)
-  // two tiles per co-operative workgroup (k_denoise_coop2; dfx_debug_pipe_waves(16) forces it): 48.2 ms per round of g_num_cus workgroups at N = 2048,
-  // T = 1000 — between one and two rounds of k_denoise_coop (B = 5 .. 8 shapes of 2048 points) the cheapest
-  const double coop_cost = rounds_cost(waves, 32.7, 0.0), coop2_cost = rounds_cost((waves + 1) / 2, 48.2, 0.0);
-  const bool coop2 = bf16 && !pipe2 && p.N % 64 == 0 && (fnw == 16 || (fnw == 0 && coop2_cost < coop_cost && (!pipe || coop2_cost < best)));
-  // 16-point tiles (k_denoise_coop16, round 5): 2 x the workgroups of k_denoise_coop at about half the time per round — the fastest choice while the batch
-  // is at most two rounds of it (B <= 4 shapes of 2048 points); works with either W1 pack.  dfx_debug_pipe_waves(160) forces it, (161) rules it out.
-  const long long tiles16 = ((long long)p.B * p.N) / 16;
-  const double coop16_cost = rounds_cost(tiles16, C16_ROUND_MS, 0.0);
-  const bool coop16 = d->dev.prec == DFX_PREC_BF16 && !g_force_direct && !pipe2 &&
-                      (fnw == 160 || (fnw == 0 && g_force_nw != 161 && coop16_cost < (coop2 ? coop2_cost : coop ? coop_cost : bf16 ? best : 3.0 * best)));   // (an engine without the fold falls back to the direct kernel, ~3x the pipelined estimate: ADVICE r5)
-  if (pipe || coop || coop2 || pipe_f32 || coop16) {
+  // (the size check stays here, on the direct kernels' workgroup count as before; the planner itself takes any B, N)
+  if (((long long)p.B * p.N / 32 + 3) / 4 > 0x7fffffffLL) return set_error(DFX_ERR_INVALID_ARG, "denoiser: B*N too large");
+  const Plan plan = plan_launch({d->dev.prec, d->dev.w1_fold != 0, g_force_direct, force_from_code(g_force_nw), p.B, p.N, g_num_cus});
+  const VariantKernel &k = KERNELS[(int)plan.v];
+  if (k.lds > 0) {
     static PerDeviceOnce attrs;
     DFX_HIP_TRY(attrs.run([] {
-      hipError_t e = set_max_lds(reinterpret_cast<const void *>(k_denoise_pipe<8>), PipeCfg<8>::L_TOTAL);
-      if (e == hipSuccess) e = set_max_lds(reinterpret_cast<const void *>(k_denoise_pipe<4>), PipeCfg<4>::L_TOTAL);
-      if (e == hipSuccess) e = set_max_lds(reinterpret_cast<const void *>(k_denoise_pipe<2>), PipeCfg<2>::L_TOTAL);
-      if (e == hipSuccess) e = set_max_lds(reinterpret_cast<const void *>(k_denoise_coop), CL_TOTAL);
-      if (e == hipSuccess) e = set_max_lds(reinterpret_cast<const void *>(k_denoise_coop2), C2_TOTAL);
-      if (e == hipSuccess) e = set_max_lds(reinterpret_cast<const void *>(k_denoise_coop16), C16_TOTAL);
-      if (e == hipSuccess) e = set_max_lds(reinterpret_cast<const void *>(k_denoise_pipe2), P2_LDS);
-      if (e == hipSuccess) e = set_max_lds(reinterpret_cast<const void *>(k_denoise_pipe_f32<8>), PipeCfg<8>::L_TOTAL);
-      if (e == hipSuccess) e = set_max_lds(reinterpret_cast<const void *>(k_denoise_pipe_f32<4>), PipeCfg<4>::L_TOTAL);
-      if (e == hipSuccess) e = set_max_lds(reinterpret_cast<const void *>(k_denoise_pipe_f32<2>), PipeCfg<2>::L_TOTAL);
+      hipError_t e = hipSuccess;
+      for (const VariantKernel &vk : KERNELS)
+        if (e == hipSuccess && vk.lds > 0) e = set_max_lds(reinterpret_cast<const void *>(vk.kernel), vk.lds);
       return e;
     }));
   }
   EventTimer tm;
   tm.begin(st);
-  const char *variant;
-  if (coop16) variant = "k_denoise_coop16", k_denoise_coop16<<<(int)tiles16, C16_NW * 64, C16_TOTAL, st>>>(p);
-  else if (pipe2) variant = "k_denoise_pipe2", k_denoise_pipe2<<<(int)(wpg * p.B), P2_NW * 64, P2_LDS, st>>>(p);
-  else if (coop2 && !(fnw == 1)) variant = "k_denoise_coop2", k_denoise_coop2<<<(int)(waves / 2), COOP_NW * 64, C2_TOTAL, st>>>(p);
-  else if (coop) variant = "k_denoise_coop", k_denoise_coop<<<(int)waves, COOP_NW * 64, CL_TOTAL, st>>>(p);
-  else if (pipe && nw == 8) variant = "k_denoise_pipe<8>", k_denoise_pipe<8><<<(int)(wpg * p.B), 8 * 64, PipeCfg<8>::L_TOTAL, st>>>(p);
-  else if (pipe && nw == 4) variant = "k_denoise_pipe<4>", k_denoise_pipe<4><<<(int)(wpg * p.B), 4 * 64, PipeCfg<4>::L_TOTAL, st>>>(p);
-  else if (pipe) variant = "k_denoise_pipe<2>", k_denoise_pipe<2><<<(int)(wpg * p.B), 2 * 64, PipeCfg<2>::L_TOTAL, st>>>(p);
-  else if (pipe_f32 && nw == 8) variant = "k_denoise_pipe_f32<8>", k_denoise_pipe_f32<8><<<(int)(wpg * p.B), 8 * 64, PipeCfg<8>::L_TOTAL, st>>>(p);
-  else if (pipe_f32 && nw == 4) variant = "k_denoise_pipe_f32<4>", k_denoise_pipe_f32<4><<<(int)(wpg * p.B), 4 * 64, PipeCfg<4>::L_TOTAL, st>>>(p);
-  else if (pipe_f32) variant = "k_denoise_pipe_f32<2>", k_denoise_pipe_f32<2><<<(int)(wpg * p.B), 2 * 64, PipeCfg<2>::L_TOTAL, st>>>(p);
-  else if (d->dev.prec == DFX_PREC_BF16) variant = "k_denoise<bf16>", k_denoise<DFX_PREC_BF16, NW><<<(int)grid, NW * 64, 0, st>>>(p);
-  else variant = "k_denoise<f32>", k_denoise<DFX_PREC_F32, NW><<<(int)grid, NW * 64, 0, st>>>(p);
-  g_last_variant = variant;
+  hipLaunchKernelGGL(k.kernel, dim3((unsigned)plan.grid), dim3(info(plan.v).threads), k.lds, st, p);
+  g_last_variant = info(plan.v).name;
   const int rc = check_launch("denoiser kernel");
   tm.end();
   return rc;
@@ -3167,7 +3119,12 @@ int dfx_masked_mse_f32(const float *target, const float *pred, const float *flag
 }
 
 void dfx_debug_force_direct(int on) { g_force_direct = on != 0; }
-void dfx_debug_pipe_waves(int nw) { g_force_nw = (nw == 8 || nw == 4 || nw == 2 || nw == 1 || nw == 64 || nw == 16 || nw == 160 || nw == 161) ? nw : 0; }
+void dfx_debug_pipe_waves(int nw) { g_force_nw = nw; }
+const char *dfx_debug_plan_variant(int prec, int w1_fold, int force_direct, int pipe_waves_code, int B, int N, long long *grid_out) {
+  const Plan plan = plan_launch({prec, w1_fold != 0, force_direct != 0, force_from_code(pipe_waves_code), B, N, g_num_cus});
+  if (grid_out) *grid_out = plan.grid;
+  return info(plan.v).name;
+}
 void dfx_debug_trace(void *device_buf, int capacity) {
   g_trace = static_cast<unsigned long long *>(device_buf);
   g_trace_cap = capacity;

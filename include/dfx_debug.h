@@ -53,11 +53,11 @@ void dfx_debug_fps_shape(int threads, int points_per_thread);
 int dfx_debug_gemm_bf16(int tn, const void *A, int lda, int a_bf16, const void *B, int ldb, int b_bf16, const float *bias,
                         const float *resid, float *C, float *db, float *workspace, size_t workspace_floats, int M, int N, int K,
                         dfx_stream_t stream);
-/* Debug/A-B switch: force the direct (non LDS-pipelined) kernel for every launch. */
 /* Box calibration for bench.py: a bare v_mfma_f32_32x32x16_bf16 stream (one wavefront per SIMD on every CU, pseudo-random operands, nothing
  * else) of `iters` x 16 MFMAs per wavefront; *ms_out = HIP-event duration, *tflops_out = executed MFMA TFLOP/s — what this chip sustains on the
  * matrix pipe at its power cap and clocks (iters = 150000 runs ~50 ms).  Synchronises `stream`. */
 int dfx_debug_bare_mfma(int iters, float *ms_out, double *tflops_out, dfx_stream_t stream);
+/* Debug/A-B switch: force the direct (non LDS-pipelined) kernel for every launch. */
 void dfx_debug_force_direct(int on);
 /* dfx_denoiser_create's decision about the W1 bias fold of bf16 engines (dfx_denoiser_w1_fold): -1 = from the weights (default: channel 127
  * while its column of W1 diag(gamma3) is ordinary, else the hidden channel with the smallest column over all blocks, exchanged with 127 at
@@ -65,14 +65,27 @@ void dfx_debug_force_direct(int on);
 void dfx_debug_w1_fold(int mode);
 /* The hidden channel whose K slot of the packed W1 carries b1' (127 unless create relabelled the channels; -1 = engine without the fold). */
 int dfx_debug_w1_fold_channel(const dfx_denoiser *d);
-/* Debug: wavefronts per workgroup of the pipelined chain kernel (8, 4 or 2), or 1 = the co-operative latency kernel (one
- * 32-point tile per workgroup, eight wavefronts on it; for an fp32 denoiser: the direct kernel), or 64 = k_denoise_pipe2 (bf16 only:
- * four wavefronts of two 32-point tiles each; when its 256-point workgroup tiles would pad a shape by more than 3x —
- * ceil(N / 256) * 256 > 3 N — the request falls back SILENTLY to the 8-wavefront kernel, and an fp32 denoiser ignores it), or 16 =
- * k_denoise_coop2 (bf16 only: the co-operative kernel with two 32-point tiles per workgroup; N % 64 != 0 falls back to the one-tile kernel);
- * 0 = chosen from the batch size; any other value is treated as 0.  All variants of one precision are bit-identical.
+/* Debug: force one chain-kernel variant of the denoiser launches (csrc/denoiser_plan.h: force_from_code).  The codes:
+ *     0 = automatic: chosen from the batch shape by the cost model (the default); any value not listed here is treated as 0;
+ *   161 = automatic, with k_denoise_coop16 ruled out (the cost model never picks it today, so the same choice as 0);
+ *     8, 4, 2 = wavefronts per workgroup of the pipelined chain kernel (k_denoise_pipe<NW>, for an fp32 denoiser k_denoise_pipe_f32<NW>);
+ *       tiles of NW x 32 points that would pad a shape by more than 3x fall back to the direct kernel;
+ *     1 = the co-operative latency kernel k_denoise_coop (one 32-point tile per workgroup, eight wavefronts on it); for an fp32 denoiser: the
+ *       direct kernel;
+ *    16 = k_denoise_coop2 (bf16 only: the co-operative kernel with two 32-point tiles per workgroup; N % 64 != 0 falls back to k_denoise_coop);
+ *    64 = k_denoise_pipe2 (bf16 only: four wavefronts of two 32-point tiles each; when its 256-point workgroup tiles would pad a shape by more
+ *       than 3x - ceil(N / 256) * 256 > 3 N - the request falls back SILENTLY to the automatic choice among k_denoise_pipe<4>, <2> and the
+ *       direct kernel);
+ *   160 = k_denoise_coop16 (bf16 only: the co-operative kernel on 16-point tiles; reads either W1 pack; NOT bit-identical to the others).
+ * An fp32 denoiser ignores 16, 64 and 160; a bf16 engine without the W1 bias fold, or under dfx_debug_force_direct, takes the direct kernel
+ * whatever the code, except that 160 still applies without the fold.  All other variants of one precision are bit-identical.
  * dfx_last_kernel_variant() (dfx.h) names the kernel a launch actually took. */
 void dfx_debug_pipe_waves(int nw);
+/* Host-side run (no GPU) of the launcher's planner (csrc/denoiser_plan.h): the name dfx_last_kernel_variant() would report after a denoiser
+ * launch of B shapes of N points on an engine of precision `prec` (DFX_PREC_*) with / without the W1 bias fold, under dfx_debug_force_direct(force_direct)
+ * and dfx_debug_pipe_waves(pipe_waves_code); *grid_out (may be NULL) = its workgroups.  A pure function of its arguments: the process-global
+ * switches are not read. */
+const char *dfx_debug_plan_variant(int prec, int w1_fold, int force_direct, int pipe_waves_code, int B, int N, long long *grid_out);
 /* Slot-boundary clock stamps of two wavefronts of workgroup 0 (device buffer of 2*capacity uint64; NULL = off).
  * Only effective in a library built with -DDFX_TRACE (tools/experiments/trace_slots.py builds one). */
 void dfx_debug_trace(void *device_buf, int capacity);

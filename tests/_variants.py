@@ -4,7 +4,7 @@ import contextlib
 
 NAMES = {"bf16": {8: "k_denoise_pipe<8>", 4: "k_denoise_pipe<4>", 2: "k_denoise_pipe<2>", 1: "k_denoise_coop", 64: "k_denoise_pipe2", 16: "k_denoise_coop2", 160: "k_denoise_coop16"},
          "f32": {8: "k_denoise_pipe_f32<8>", 4: "k_denoise_pipe_f32<4>", 2: "k_denoise_pipe_f32<2>", 1: "k_denoise<f32>"}}
-AUTO = {"bf16": set(NAMES["bf16"].values()) - {"k_denoise_pipe2"} | {"k_denoise<bf16>"},   # (k_denoise_coop16: the launcher's choice for the smallest batches)
+AUTO = {"bf16": set(NAMES["bf16"].values()) - {"k_denoise_pipe2"} | {"k_denoise<bf16>"},   # (k_denoise_coop16: allowed here, though the cost model never picks it today — denoiser_plan.h: C16_ROUND_MS)
         "f32": set(NAMES["f32"].values())}
 
 
