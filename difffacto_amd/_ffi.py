@@ -166,6 +166,7 @@ SIGNATURES = {
     "dfx_debug_stats_merge": (None, [_P, _I, _I, _P]),
     "dfx_debug_rowmap": (None, [_I, _P, _P]),
     "dfx_debug_emd_state_global": (None, [_I]),
+    "dfx_debug_chamfer_queries": (None, [_I]),
     "dfx_debug_fps_shape": (None, [_I, _I]),
     "dfx_pointnet_v2_train_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "dfx_pointnet_v2_train_forward": (_I, [ctypes.POINTER(PointNetV2Weights), _P, _SZ, _P, _P, _P, _P, _F, _I, _I, _I, _P]),

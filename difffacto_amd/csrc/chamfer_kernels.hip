@@ -84,6 +84,8 @@ __global__ void __launch_bounds__(256) chamfer_grad_kernel(const float *__restri
   }
 }
 
+int g_chamfer_queries = 0;   // debug: 1 / 2 force chamfer_nn_kernel<1> / <2>; 0 = the launcher's own rule
+
 }  // namespace
 
 extern "C" {
@@ -96,7 +98,9 @@ int dfx_chamfer_forward_f32(const float *xyz1, const float *xyz2, float *dist1, 
   DFX_REQUIRE(xyz1 && xyz2 && dist1 && dist2 && idx1 && idx2, "chamfer_forward: null pointer");
   hipStream_t st = dfx::as_stream(stream);
   auto run = [&](const float *q, const float *r, float *d, int32_t *ix, int n, int m) {
-    if ((long long)B * ((n + 511) / 512) >= 256) {   // a workgroup per CU even with two query points per thread
+    const bool two = g_chamfer_queries ? g_chamfer_queries == 2
+                                       : (long long)B * ((n + 511) / 512) >= 256;   // a workgroup per CU even with two query points per thread
+    if (two) {
       const int w = (n + 511) / 512;
       chamfer_nn_kernel<2><<<B * w, 256, 0, st>>>(q, r, d, ix, n, m, w);
     } else {
@@ -108,6 +112,8 @@ int dfx_chamfer_forward_f32(const float *xyz1, const float *xyz2, float *dist1, 
   run(xyz2, xyz1, dist2, idx2, M, N);
   return dfx::check_launch("chamfer_forward");
 }
+
+void dfx_debug_chamfer_queries(int q) { g_chamfer_queries = q == 1 || q == 2 ? q : 0; }
 
 int dfx_chamfer_backward_f32(const float *xyz1, const float *xyz2, const int32_t *idx1, const int32_t *idx2,
                              const float *grad_dist1, const float *grad_dist2, float *grad_xyz1, float *grad_xyz2,

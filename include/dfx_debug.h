@@ -44,6 +44,10 @@ void dfx_debug_rowmap(int tiled, int *out_b, int *out_a);
 void dfx_debug_lin_split_k(int mode);
 /* Debug / A-B switch: 1 keeps the EMD auction's state in global memory for every n (default 0: in LDS when n <= 2688). */
 void dfx_debug_emd_state_global(int on);
+/* Debug / A-B switch: query points per thread of the Chamfer nearest-neighbour kernel in both directions of dfx_chamfer_forward_f32: 1 or 2 force
+ * chamfer_nn_kernel<1> / <2> with ceil(n / (256 q)) workgroups per cloud; 0 (default, and any other value) = the launcher's own rule (<2> when
+ * B * ceil(n / 512) >= 256).  Bit-identical results either way. */
+void dfx_debug_chamfer_queries(int q);
 /* Debug / sweep: workgroup shape of the register-resident FPS kernel (threads in {256, 512, 1024} x points per thread in {2..32},
  * used when threads * points >= N; 0, 0 = automatic). */
 void dfx_debug_fps_shape(int threads, int points_per_thread);
