@@ -194,9 +194,11 @@ __global__ void k_attn_fwd(const float *__restrict__ QKV, const float *__restric
 // backward: one thread per (shape, head, channel d) -> dQKV (no atomics).  Every thread of a (shape, head) repeats the J x J softmax-gradient scalars
 // (the same operations in the same order, so the same bits in every lane) and accumulates its own channel of dq / dk / dv in registers, in the order
 // a single walk over the (j, jj) pairs would: dq[j] over jj ascending, dk[jj] and dv[jj] over j ascending.
+// masked_fill_ (attention.py:192-197) passes no gradient to sim at an absent key.  While a shape has a present part p is exactly 0 there, so ds is 0
+// either way; in a shape with every part absent the forward's p is 1 / J on all keys, and only `valid` says that ds is 0 (dv still gets p dout).
 template <int DH>
-__global__ void k_attn_bwd(const float *__restrict__ QKV, const float *__restrict__ P, const float *__restrict__ dO, float *__restrict__ dQKV, int R, int J, int H,
-                           float scale) {
+__global__ void k_attn_bwd(const float *__restrict__ QKV, const float *__restrict__ valid, const float *__restrict__ P, const float *__restrict__ dO,
+                           float *__restrict__ dQKV, int R, int J, int H, float scale) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (long long)R * H * DH) return;
   const int d = t % DH, h = (t / DH) % H, r = t / ((long long)DH * H), C = H * DH;
@@ -221,7 +223,7 @@ __global__ void k_attn_bwd(const float *__restrict__ QKV, const float *__restric
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj) {
       if (jj >= J) break;
-      const float ds = p[jj] * (dP[jj] - dot) * scale;   // d sim (masked keys: p = 0 -> 0)
+      const float ds = valid[(size_t)r * J + jj] != 0.f ? p[jj] * (dP[jj] - dot) * scale : 0.f;   // d sim (masked keys: 0)
       adq = fmaf(ds, QKV[((size_t)r * J + jj) * 3 * C + C + h * DH + d], adq);
       adk[jj] = fmaf(ds, q[d], adk[jj]);
       adv[jj] = fmaf(p[jj], dout[d], adv[jj]);
@@ -311,7 +313,7 @@ void attn_dispatch(int dh, F &&f) {
 
 // The backward chain behind dfx_aligner_train_forward.  The dH chain (data gradients) is the same launches in the same order whether `grads` is
 // given or not; with grads == NULL every weight-gradient product, column sum and LayerNorm-parameter launch is left out.
-void backward_chain(const dfx_latent_weights *w, Ws &s, const float *d_mean, const float *d_logvar, const dfx_latent_weights *grads,
+void backward_chain(const dfx_latent_weights *w, Ws &s, const float *valid, const float *d_mean, const float *d_logvar, const dfx_latent_weights *grads,
                     float *d_part_code, float *d_noise, int B, hipStream_t st) {
   const int J = w->n_class, C = w->n_heads * w->d_head, IC = w->zdim + w->noise_dim, H = w->n_heads, M = B * J;
   auto mut = [](const float *p) { return const_cast<float *>(p); };
@@ -338,7 +340,7 @@ void backward_chain(const dfx_latent_weights *w, Ws &s, const float *d_mean, con
     if (grads) linear_dw(st, s.dH1, C, s.O[i], C, mut(g.to_out_w), M, C, C);
     if (grads) k_colsum<<<nblk(C), 256, 0, st>>>(s.dH1, C, mut(g.to_out_b), M, C, 0, 1);
     linear_dx(st, s.dH1, C, k.to_out_w, nullptr, s.dO, C, M, C, C);
-    attn_dispatch(w->d_head, [&](auto dh) { k_attn_bwd<decltype(dh)::value><<<nblk((long long)B * H * w->d_head), 256, 0, st>>>(s.QKV[i], s.P[i], s.dO, s.dQKV, B, J, H, scale); });
+    attn_dispatch(w->d_head, [&](auto dh) { k_attn_bwd<decltype(dh)::value><<<nblk((long long)B * H * w->d_head), 256, 0, st>>>(s.QKV[i], valid, s.P[i], s.dO, s.dQKV, B, J, H, scale); });
     if (grads) linear_dw(st, s.dQKV, 3 * C, s.Xn2[i], C, mut(g.to_q), M, C, C);
     if (grads) linear_dw(st, s.dQKV + C, 3 * C, s.Xn2[i], C, mut(g.to_k), M, C, C);
     if (grads) linear_dw(st, s.dQKV + 2 * C, 3 * C, s.Xn2[i], C, mut(g.to_v), M, C, C);
@@ -410,7 +412,7 @@ int dfx_aligner_train_backward(const dfx_latent_weights *w, void *workspace, siz
   Ws s;
   DFX_REQUIRE(carve(s, static_cast<char *>(workspace), B, w->n_class, w->n_heads * w->d_head, w->zdim + w->noise_dim, w->n_heads, w->depth) <= workspace_bytes,
               "aligner_train_backward: workspace too small");
-  backward_chain(w, s, d_mean, d_logvar, grads, d_part_code, nullptr, B, dfx::as_stream(stream));
+  backward_chain(w, s, valid, d_mean, d_logvar, grads, d_part_code, nullptr, B, dfx::as_stream(stream));
   return dfx::check_launch("aligner_train_backward");
 }
 
@@ -425,7 +427,7 @@ int dfx_aligner_input_backward(const dfx_latent_weights *w, void *workspace, siz
   Ws s;
   DFX_REQUIRE(carve(s, static_cast<char *>(workspace), B, w->n_class, w->n_heads * w->d_head, w->zdim + w->noise_dim, w->n_heads, w->depth) <= workspace_bytes,
               "aligner_input_backward: workspace too small");
-  backward_chain(w, s, d_mean, d_logvar, nullptr, d_part_code, d_noise, B, dfx::as_stream(stream));
+  backward_chain(w, s, valid, d_mean, d_logvar, nullptr, d_part_code, d_noise, B, dfx::as_stream(stream));
   return dfx::check_launch("aligner_input_backward");
 }
 

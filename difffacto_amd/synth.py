@@ -65,23 +65,24 @@ def make_denoiser_weights(seed=0, depth=5):
     return W
 
 
-def latent_param_shapes(n_class=N_CLASS, flow_depth=14, flow_hidden=256, depth=5, heads=8, d_head=32, noise_dim=32):
+def latent_param_shapes(n_class=N_CLASS, flow_depth=14, flow_hidden=256, depth=5, heads=8, d_head=32, noise_dim=32, zdim=ZDIM):
     """(name, shape) of the gen-path encoder parameters, reference ``state_dict`` names relative to
-    ``encoder.`` (flow.py:9-19, part_encoders.py:52-86 with configs/gen_chair.py:14-38)."""
+    ``encoder.`` (flow.py:9-19, part_encoders.py:52-86 with configs/gen_chair.py:14-38).  ``flow_depth`` 0: no flows;
+    ``noise_dim`` 0: the aligner without cIMLE (proj_in takes the part code alone)."""
     s = []
-    half = ZDIM - ZDIM // 2
+    half = zdim - zdim // 2
     for i in range(n_class):
         for l in range(flow_depth):
             p = f"flow.{i}.chain.{l}.net_s_t."
             s += [(p + "0.weight", (flow_hidden, half)), (p + "0.bias", (flow_hidden,)),
                   (p + "2.weight", (flow_hidden, flow_hidden)), (p + "2.bias", (flow_hidden,)),
-                  (p + "4.weight", ((ZDIM - half) * 2, flow_hidden)), (p + "4.bias", ((ZDIM - half) * 2,))]
+                  (p + "4.weight", ((zdim - half) * 2, flow_hidden)), (p + "4.bias", ((zdim - half) * 2,))]
     inner = heads * d_head
     P = "part_aligner."
     s += [(P + "class_emb.weight", (n_class, inner)),
           (P + "pre_norm.weight", (inner,)), (P + "pre_norm.bias", (inner,)),
           (P + "post_norm.weight", (inner,)), (P + "post_norm.bias", (inner,)),
-          (P + "proj_in.weight", (inner, ZDIM + noise_dim)), (P + "proj_in.bias", (inner,))]
+          (P + "proj_in.weight", (inner, zdim + noise_dim)), (P + "proj_in.bias", (inner,))]
     for i in range(depth):
         p = f"{P}transformer_blocks.{i}."
         s += [(p + "ff.net.0.proj.weight", (8 * inner, inner)), (p + "ff.net.0.proj.bias", (8 * inner,)),

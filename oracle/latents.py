@@ -10,7 +10,8 @@ SURVEY.md §8 row F2: ``PartEncoder.sample_latents`` for the shipped gen configs
   class_cond + add_class_cond (class embedding added after proj_in), cimle with
   cond_noise_type 0 (noise * noise_scale concatenated to every token), use_linear,
   single_attn (self-attention over the n_class tokens, keys masked by valid_id); pre_norm is
-  NOT applied on this configuration (part_encoders.py:115-131)
+  NOT applied on this configuration (part_encoders.py:115-131).  ``cimle=False``: no noise channels, and
+  pre_norm after the class embedding (:130-131)
 * ``PartEncoder.sample_latents``            part_encoders.py:1052-1110 (fixed_id mixing, K-fold
   repeat, seg-mask ids) with ``PartEncoderForTransformerDecoder.prepare_ctx`` :1317-1326 and
   ``gather_all`` :417-428
@@ -64,18 +65,24 @@ def aligner_depth(W):
     return d
 
 
-def part_aligner_forward(W, part_code, valid_id, noise, noise_scale=100.0, heads=8):
-    """part_encoders.py:88-143.  part_code (B,zdim,J)  valid_id (B,J)  noise (B,noise_dim)
+def part_aligner_forward(W, part_code, valid_id, noise, noise_scale=100.0, heads=8, cimle=True):
+    """part_encoders.py:88-143.  part_code (B,zdim,J)  valid_id (B,J)  noise (B,noise_dim), None without cimle
     -> mean (B,3,J), logvar (B,3,J)."""
     P = "part_aligner."
     B, _, J = part_code.shape
-    nz = (noise * F32(noise_scale)).astype(F32)
-    x = np.concatenate([part_code, np.repeat(nz[:, :, None], J, axis=2)], axis=1)     # (B, zdim+noise_dim, J)
+    if cimle:
+        nz = (noise * F32(noise_scale)).astype(F32)
+        x = np.concatenate([part_code, np.repeat(nz[:, :, None], J, axis=2)], axis=1) # (B, zdim+noise_dim, J)
+    else:
+        assert noise is None
+        x = part_code
     x = np.ascontiguousarray(x.transpose(0, 2, 1))                                    # b c n -> b n c
     x = linear(x, W[P + "proj_in.weight"], W[P + "proj_in.bias"])
     x = (x + W[P + "class_emb.weight"][None]).astype(F32)
     # part_encoders.py:115-131: with cimle and cond_noise_type 0 NO branch applies pre_norm (the `else`
     # that holds it pairs with `if self.cimle`); its parameters exist in the state_dict but are unused.
+    if not cimle:
+        x = layer_norm(x, W[P + "pre_norm.weight"], W[P + "pre_norm.bias"])
     for i in range(aligner_depth(W)):
         p = f"{P}transformer_blocks.{i}."
         xn = layer_norm(x, W[p + "norm2.weight"], W[p + "norm2.bias"])
@@ -97,12 +104,12 @@ def seg_mask_ids(valid_id, sample_points):
 
 
 def sample_latents(W, w_noise, aligner_noise, valid_id, fixed_id, K, sample_points, prior_var=1.0,
-                   noise_scale=100.0, log_scale_var=0.0, part_code=None):
+                   noise_scale=100.0, log_scale_var=0.0, part_code=None, heads=8, cimle=True):
     """part_encoders.py:1052-1110 (use_flow, cimle, no selective sampling).
 
     w_noise (S,zdim,J) standard normal; aligner_noise (S*K,noise_dim); valid_id (S,J); fixed_id (J,).
-    Returns the reference's 6-tuple as a dict."""
-    S, _, J = w_noise.shape
+    Without cimle (:1068-1070) K is 1 and there is no noise.  Returns the reference's 6-tuple as a dict."""
+    S, J = np.shape(valid_id)
     if part_code is None:
         part_code = (w_noise * F32(np.sqrt(prior_var))).astype(F32)
         depth = flow_depth(W)
@@ -111,16 +118,20 @@ def sample_latents(W, w_noise, aligner_noise, valid_id, fixed_id, K, sample_poin
                                   for i in range(J)], axis=-1)
     fixed_id = np.asarray(fixed_id, dtype=F32)
     valid_id = np.asarray(valid_id, dtype=F32)
-    noise = np.asarray(aligner_noise, dtype=F32)
+    if cimle:
+        noise = np.asarray(aligner_noise, dtype=F32)
+    else:
+        assert K == 1 and aligner_noise is None
+        noise = None
     fixed_codes = part_code[0][None]
     fixed_valid = np.clip(valid_id[0][None] + fixed_id[None], 0, 1)
     part_code = (part_code * (1 - fixed_id)[None, None] + fixed_id[None, None] * fixed_codes).astype(F32)
     valid_id = (valid_id * (1 - fixed_id)[None] + fixed_id[None] * fixed_valid).astype(F32)
-    if np.any(fixed_id == 1):
+    if noise is not None and np.any(fixed_id == 1):
         noise = np.broadcast_to(noise.reshape(S, K, -1)[0][None], (S, K, noise.shape[-1])).reshape(S * K, -1)
     part_code = np.repeat(part_code, K, axis=0)
     valid_id = np.repeat(valid_id, K, axis=0)
-    mean, logvar = part_aligner_forward(W, part_code, valid_id, noise, noise_scale=noise_scale)
+    mean, logvar = part_aligner_forward(W, part_code, valid_id, noise, noise_scale=noise_scale, heads=heads, cimle=cimle)
     seg = seg_mask_ids(valid_id, sample_points)
     lv = (logvar + F32(log_scale_var)).astype(F32)
     idx = seg[:, None, :].astype(np.int64)

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from difffacto_amd import synth
+from _latent_cfg import _aligner_torch
 from _replay import replay_draws
 
 pytestmark = pytest.mark.gpu
@@ -165,34 +166,6 @@ def test_callers_without_a_noise_gradient_keep_their_launches_and_bits(monkeypat
 
 
 # ---------------------------------------------------------------------------------------------------- 3: torch autograd through a restatement
-def _aligner_torch(W, code, valid, noise, noise_scale=100.0, heads=8):
-    """oracle/latents.py:part_aligner_forward op by op in torch (float64), for autograd."""
-    P = "part_aligner."
-    F = torch.nn.functional
-    B, _, J = code.shape
-    x = torch.cat([code, (noise * noise_scale)[:, :, None].expand(-1, -1, J)], dim=1).transpose(1, 2)
-    x = F.linear(x, W[P + "proj_in.weight"], W[P + "proj_in.bias"]) + W[P + "class_emb.weight"][None]
-    depth = 0
-    while f"{P}transformer_blocks.{depth}.norm2.weight" in W:
-        depth += 1
-    for i in range(depth):
-        p = f"{P}transformer_blocks.{i}."
-        C = x.shape[-1]
-        xn = F.layer_norm(x, (C,), W[p + "norm2.weight"], W[p + "norm2.bias"], 1e-5)
-        q, k, v = (F.linear(xn, W[p + f"attn2.to_{n}.weight"]).reshape(B, J, heads, C // heads).transpose(1, 2) for n in "qkv")
-        sim = torch.einsum("bhid,bhjd->bhij", q, k) * (C // heads) ** -0.5
-        sim = sim.masked_fill(~valid.bool()[:, None, None, :], -torch.finfo(torch.float32).max)
-        o = torch.einsum("bhij,bhjd->bhid", sim.softmax(-1), v).transpose(1, 2).reshape(B, J, C)
-        x = F.linear(o, W[p + "attn2.to_out.0.weight"], W[p + "attn2.to_out.0.bias"]) + x
-        h = F.linear(F.layer_norm(x, (C,), W[p + "norm3.weight"], W[p + "norm3.bias"], 1e-5), W[p + "ff.net.0.proj.weight"], W[p + "ff.net.0.proj.bias"])
-        a, gate = h.chunk(2, dim=-1)
-        x = F.linear(a * F.gelu(gate), W[p + "ff.net.2.weight"], W[p + "ff.net.2.bias"]) + x
-    C = x.shape[-1]
-    x = F.linear(F.layer_norm(x, (C,), W[P + "post_norm.weight"], W[P + "post_norm.bias"], 1e-5), W[P + "proj_out.weight"], W[P + "proj_out.bias"])
-    h = x.transpose(1, 2)
-    return h[:, :3], h[:, 3:]
-
-
 @pytest.mark.parametrize("B,seed,absent", [(2, 5, [(0, 1)]), (7, 6, [(2, 0), (4, 3), (4, 2)])])
 def test_noise_gradient_vs_torch_autograd_through_the_oracle(B, seed, absent):
     """gate 3: shapes and weights the goldens do not cover.  The torch restatement is first held to oracle/latents.py's forward."""
