@@ -108,6 +108,9 @@ SIGNATURES = {
     "dfx_occupancy_jsd_f64": (_I, [_P, _P, _I, _P, _P]),
     "dfx_occupancy_entropy_f64": (_I, [_P, _I, ctypes.c_int64, _P, _P]),
     "dfx_debug_occupancy_host": (_I, [_P, _I, _I, _I, _P]),
+    "dfx_batch_draw": (_I, [_P, _I, _P, _P, _I, _I, _I, _U64, _P, _P, _P, _P]),
+    "dfx_batch_build_f32": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _D, _I, _I] + [_P] * 12),
+    "dfx_debug_batch_build_host": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _D, _I, _I] + [_P] * 11),
     "dfx_denoiser_create": (_I, [ctypes.POINTER(_P), ctypes.POINTER(DenoiserWeights), _I, _D, _D, _I, _P]),
     "dfx_denoiser_destroy": (None, [_P]),
     "dfx_denoiser_num_timesteps": (_I, [_P]),

@@ -319,6 +319,40 @@ int dfx_occupancy_jsd_f64(const int64_t *counters_p, const int64_t *counters_q, 
 int dfx_occupancy_entropy_f64(const int32_t *bernoulli, int cells, int64_t n_shapes, double *entropy, dfx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training-batch assembly — _ShapeNetSegParts.__getitem__ (python/difffacto/datasets/shapenet_seg.py:436-543) with pc_norm
+ * (dataset_utils.py:55-95), over a device-resident ragged set: points (P,3) float32, labels (P) int32, offsets (S+1) int64 (cloud s
+ * is rows offsets[s] .. offsets[s+1]-1).  batch_kernels.hip, DESIGN.md §5.10.  index (B) int64 picks the clouds.
+ * Scale modes: 0 none, 1 shape_unit, 2 shape_half, 3 shape_34, 4 shape_bbox (scale_mode and part_scale_mode), 5 shape_canonical,
+ * 6 shape_canonical_bbox (part_scale_mode only).  1 <= n_class <= 8, 10 <= npoints <= 8192.
+ * ------------------------------------------------------------------------------------------ */
+
+/* The random inputs of a batch from Philox4x32-7: key = seed, counter = (group of four values, purpose, sample_id[b]), so an item's
+ * draws depend on (seed, sample_id[b]) only, not on its row or on B.  choice int32 (B,N) = (u32 * M) >> 32 with M the size of cloud
+ * index[b] (bias < M / 2^32 per value; all 0 for an index outside [0,S) or an empty cloud, which dfx_batch_build_f32 reports);
+ * drop_u float32 (B,C) and aug_u float32 (B,6): 24-bit uniforms in [0,1). */
+int dfx_batch_draw(const int64_t *offsets, int S, const int64_t *index, const int64_t *sample_id, int B, int N, int C, uint64_t seed,
+                   int32_t *choice, float *drop_u, float *aug_u, dfx_stream_t stream);
+
+/* Assembles B items, one 256-thread workgroup each, 16 * npoints bytes of LDS.  Per item: gather points / labels at choice; shape
+ * normalisation (fp64 mean, two-pass variance and bounds, rounded once; ref = (x - shift) / scale in float32); for part i = 0..C-1
+ * on the CURRENT labels: with >= 10 points its statistics, present = 0 when an axis std is exactly zero, pc_norm with
+ * part_scale_mode (clip to [1e-2,1] when clip, then a zero scale becomes 1) and the part's input rows; with 1..9 points every point
+ * takes the label of its nearest point outside the part (float32 ((dx*dx) + dy*dy) + dz*dz, first minimum), present 0, shift 0,
+ * scale 1.  dp_present = present, 0 where drop_u < dropout_part.  With augment_shift / augment_scale: rand_scale = aug_u[0:3] / 2 + 0.7,
+ * rand_shift = aug_u[3:6] - 0.5 (ones / zeros for the one that is off), ref = (ref + rand_shift) * rand_scale,
+ * shift += scale * rand_shift, scale = rand_scale * scale.
+ * Outputs: ref, input float32 (B,N,3); seg int64 (B,N); attn_map int64 (B,N,C) one-hot; present, dp_present float32 (B,C);
+ * part_shift, part_scale float32 (B,3,C); shift float32 (B,3); scale float32 (B,3) (three equal values without augmentation).
+ * n_bad int32 (2), zeroed first: [0] sampled labels outside [0,C) (their one-hot row is zero), [1] items whose index is outside
+ * [0,S), whose cloud is empty (their output rows are not written) or that hold a choice outside [0,M) (read as 0).
+ * Bit-reproducible: fixed-order fp64 sums, no floating-point atomics. */
+int dfx_batch_build_f32(const float *points, const int32_t *labels, const int64_t *offsets, int S, const int64_t *index, int B,
+                        const int32_t *choice, const float *drop_u, const float *aug_u, int n_class, int npoints, int scale_mode,
+                        int part_scale_mode, int clip, double dropout_part, int augment_shift, int augment_scale, float *ref,
+                        float *input, int64_t *seg, int64_t *attn_map, float *present, float *dp_present, float *part_shift,
+                        float *part_scale, float *shift, float *scale, int32_t *n_bad, dfx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Latent sampler — the once-per-batch producer of decode's inputs:
  * PartEncoder.sample_latents (python/difffacto/models/encoders/part_encoders.py:1052-1110) =
  * per-part normalising flows run in reverse (python/difffacto/models/encoders/flow.py:21-47,58-72)

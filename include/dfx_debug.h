@@ -101,6 +101,13 @@ int dfx_debug_part_box_units(uint64_t seed, long long pair0, int P, int C, float
 /* Host-side run (no GPU) of k_occupancy's per-point search, compiled from the kernel's own functions: the compact cell index of n HOST
  * points (n,3) on the grid of dfx_occupancy_grid_f32, -1 for a non-finite point. */
 int dfx_debug_occupancy_host(const float *host_xyz, int n, int resolution, int in_sphere, int32_t *host_cell_index);
+/* Host-side run (no GPU) of dfx_batch_build_f32, compiled from the kernel's own per-item routine: the same arguments as HOST
+ * pointers, items one after the other, sums in index order.  An index outside [0,S) or an empty cloud is an error here. */
+int dfx_debug_batch_build_host(const float *points, const int32_t *labels, const int64_t *offsets, int S, const int64_t *index, int B,
+                               const int32_t *choice, const float *drop_u, const float *aug_u, int n_class, int npoints, int scale_mode,
+                               int part_scale_mode, int clip, double dropout_part, int augment_shift, int augment_scale, float *ref,
+                               float *input, int64_t *seg, int64_t *attn_map, float *present, float *dp_present, float *part_shift,
+                               float *part_scale, float *shift, float *scale, int32_t *n_bad);
 
 #ifdef __cplusplus
 }
