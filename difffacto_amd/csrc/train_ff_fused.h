@@ -17,13 +17,13 @@
 // A sum over the points (weight gradients) needs the points on the K axis of the MFMA, i.e. along the registers, and here they are on
 // the lanes: hence the second kernel, which recomputes hid and d[a | g] in the transposed orientation from the fragments.
 //
-// Weights: per optimiser step the block's W1 / W2 are re-packed (k_ff_pack) as bf16 MFMA A-fragments, 24 tiles of 32 x 32 per
-// hidden chunk (48 KiB): W1a, W1g (K = channels, natural order: the B operand comes from memory), W2 (K = hidden units in the
-// accumulator-register order of the GELU output), W2^T (rows = hidden units, K = channels) and W1a^T, W1g^T (rows = channels,
-// K = hidden units in register order).  A workgroup (4 wavefronts = 128 points, two workgroups per CU: one's row loads and stores run
+// Weights: per optimiser step the block's W1 / W2 are re-packed (k_ff_pack) as MFMA A-fragments, tiles of 32 x 32 in a 72 KiB
+// record per hidden chunk: bf16 W1a, W1g (K = channels, natural order: the B operand comes from memory), W2 (K = hidden units in the
+// accumulator-register order of the GELU output) and W2^T (rows = hidden units, K = channels), eight tiles of padding where W1a^T, W1g^T
+// used to be, and the forward's own twelve (T_FW1A ..).  A workgroup (4 wavefronts = 128 points, two workgroups per CU: one's row loads and stores run
 // under the other's chunk loop) streams the chunks L2 -> LDS with LDS-DMA through three buffers — forward: whole chunks (24 KiB), two
-// ahead of the compute, one barrier per chunk; backward: the same since round 6 (BWD_TR: one 24 KiB record [W1a | W1g | W2^T] per chunk, the W1a^T / W1g^T
-// operands read out of it with the LDS transpose read; until then two items per chunk, stage_item, and two barriers) — with counted s_waitcnt vmcnt.
+// ahead of the compute, one barrier per chunk; backward: the same since round 6 (one 24 KiB record [W1a | W1g | W2^T] per chunk, the W1a^T / W1g^T
+// operands read out of it with the LDS transpose read; until then two items per chunk and two barriers) — with counted s_waitcnt vmcnt.
 //
 // A workgroup's four tiles belong to ONE shape (its folded attention fragments sit in LDS once); every memory phase issues all of its loads
 // before it consumes any; both kernels are spill-free (a scratch reload behind output stores waits for their acknowledgements); and between two
@@ -53,27 +53,19 @@ constexpr int C = 128, FH = 512, NCHUNK = FH / 32;
 // the forward without any GELU arithmetic runs 716 -> 607 us).  It reads its OWN twelve tiles of a chunk (T_F*): W1a scaled by FWD_A_SCALE, W1g by
 // FWD_G_SCALE (the polynomial works on u = g / 2; a g / 32 stays inside the fp16 range) and W2 as fp16 times the inverse of their product — exact
 // powers of two.  The backward kernels keep the bf16 tiles 0..23 and the fp32 sigmoid form (their gradients multiply fp32 values that fp16 cannot hold).
-#ifndef DFX_FF_FWD_F16
-#define DFX_FF_FWD_F16 1
-#endif
-constexpr bool FWD_F16 = DFX_FF_FWD_F16 != 0;
-#ifndef DFX_FF_BWD_TR
-#define DFX_FF_BWD_TR 1   // the backward's second product reads W1a / W1g turned around in LDS instead of transposed tiles of its own (see BWD_SPREAD's neighbour below)
-#endif
-constexpr bool BWD_TR = DFX_FF_BWD_TR != 0;
 constexpr float FWD_A_SCALE = 0.0625f, FWD_G_SCALE = 0.5f;
-constexpr int TILES = FWD_F16 ? 36 : 24;          // tiles per chunk in the pack
+constexpr int TILES = 36;                         // tiles per chunk in the pack: the bf16 tiles 0..23 and the forward's own twelve
 constexpr int TILE_U4 = 128;                      // uint4 per tile (2 units x 64 lanes)
-constexpr int CHUNK_U4 = TILES * TILE_U4;         // 4608 uint4 = 72 KiB (48 KiB without the forward's own tiles)
-constexpr int FWD_TILES = 12, BWD_TILES = 12;     // LDS slot size in tiles.  forward: tiles FWD_TILE0 .. + 11 of a chunk; backward: see stage_item
+constexpr int CHUNK_U4 = TILES * TILE_U4;         // 4608 uint4 = 72 KiB
+constexpr int FWD_TILES = 12, BWD_TILES = 12;     // LDS slot size in tiles.  forward: tiles FWD_TILE0 .. + 11 of a chunk; backward: see stage_record_bwd
 enum { T_W1A = 0, T_W1G = 4, T_W2 = 8, T_W2T = 12, T_W1AT = 16, T_W1GT = 20, T_FW1A = 24, T_FW1G = 28, T_FW2 = 32 };
-constexpr int FWD_TILE0 = FWD_F16 ? T_FW1A : 0;   // first tile of the forward's slot image (within it: W1a 0..3, W1g 4..7, W2 8..11 either way)
-constexpr int PACK_RECORDS = FWD_F16 ? NCHUNK + 1 : NCHUNK;   // chunk records in the pack (the forward's skew needs a 17th for the last W2)
+constexpr int FWD_TILE0 = T_FW1A;                 // first tile of ff_fwd's slot image (within it: W1a 0..3, W1g 4..7, W2 8..11, as in tiles 0..11)
+constexpr int PACK_RECORDS = NCHUNK + 1;          // chunk records in the pack (the forward's skew needs a 17th for the last W2)
 
 __host__ __device__ inline int rho(int r, int hf) { return (r & 3) + 8 * (r >> 2) + 4 * hf; }
 // Round 6: where lane l's 16 bytes of a W1a / W1g fragment (tiles 0 .. 7, unit u) sit inside the unit's 1 KiB: slot l ^ (4 u + 8 (l >> 5)).  Every reader of
 // those tiles indexes with it (k_ff's first product, k_ff_wgrad's operands; ds_read_b128 stays conflict-free: an XOR with a constant inside each 16-lane
-// access group).  It is there for the backward's SECOND product, which reads the same tiles turned around (ds_read_b64_tr_b16, see BWD_TR): the 32 lanes of
+// access group).  It is there for the backward's SECOND product, which reads the same tiles turned around (ds_read_b64_tr_b16, see lds_tr16): the 32 lanes of
 // an access group address rows 4 x (unit, k half) apart, which in the lane-linear image are 1024 / 512 bytes apart = the same banks, four ways; with the two
 // bits folded into the row they are 32 distinct 8-byte slots of a 256-byte bank row (SQ_LDS_BANK_CONFLICT 2.5e7 -> 0 per launch).
 __host__ __device__ inline int w1_slot(int lane, int u) { return lane ^ ((u << 2) | ((lane >> 5) << 3)); }
@@ -140,7 +132,7 @@ __global__ void k_ff_pack(PackBatch batch) {
   if (idx >= PACK_RECORDS * TILES * 2 * 64) return;
   const int lane = idx & 63, u = (idx >> 6) & 1, t = (idx >> 7) % TILES, j = idx / (TILES * 128);
   if (j == NCHUNK && t < T_FW2) return;   // the forward's 17th record: only its W2 tiles (hidden chunk 15) are read
-  if (BWD_TR && t >= T_W1AT && t < T_FW1A) return;   // the transposed W1 tiles: nobody reads them (k_ff<true> turns tiles 0 .. 7 around in LDS)
+  if (t >= T_W1AT && t < T_FW1A) return;   // unused padding of the record (once W1a^T / W1g^T: k_ff<true> turns tiles 0 .. 7 around in LDS instead)
   const int i = lane & 31, hf = lane >> 5;
   __bf16 v[8];
 #pragma unroll
@@ -155,7 +147,7 @@ __global__ void k_ff_pack(PackBatch batch) {
     } else if (t < T_W1AT) {             // W2^T: rows = hidden units, k-tile c over the channels, natural K
       const int c = t - T_W2T;
       x = a.w2[(size_t)(32 * c + k_nat(u, hf, e)) * FH + 32 * j + i];
-    } else if (t < T_FW1A) {             // W1a^T / W1g^T: rows = channels 32 ct + i, K = hidden units in register order
+    } else if (t < T_FW1A) {             // W1a^T / W1g^T: rows = channels 32 ct + i, K = hidden units in register order (not reached: the padding returned above)
       const int p = (t - T_W1AT) >> 2, ct = (t - T_W1AT) & 3;
       x = a.w1[(size_t)(p * FH + 32 * j + k_reg(u, hf, e)) * C + 32 * ct + i] * a.g3[32 * ct + i] * (p == 0 ? a.keep_a : 1.0f);
     } else if (t < T_FW2) {              // the forward's W1a / W1g: tiles 0..7 times the fp16 scales (bf16, exact)
@@ -224,12 +216,7 @@ constexpr int DM_WORDS = 10, DM_TILE = DM_WORDS * 64;   // dwords per 32-point t
 // 4 hf .. 4 hf + 3 of every group (accumulator layout: register 4 q + m = element 8 q + 4 hf + m), so the pair computes each group ONCE (half hf
 // takes groups hf and hf + 2) and trades the halves with four v_permlane32_swap.  w[q] = the two words (4 draws) of this lane's elements of group q.
 __device__ __forceinline__ void drop_words(const DropKey &k, unsigned site, unsigned long long g8, int hf, unsigned (&w)[4][2]) {
-#ifdef DFX_ABL_DROP_RNG   // (ablation builds only: wrong factors, no Philox rounds)
-  const unsigned q = (unsigned)g8 * 2654435761u + site;
-  uint4 A = make_uint4(q, q ^ k.k0, q + k.k1, q ^ 0x9E3779B9u), B = make_uint4(q + 1, q ^ k.k1, q + k.k0, q ^ 0xBB67AE85u);
-#else
   uint4 A = drop_group(k, site, g8 + hf), B = drop_group(k, site, g8 + hf + 2);
-#endif
   auto swap = [](unsigned &lo, unsigned &hi) {   // -> lo = [lo of the low half-wave | hi of the low half-wave], hi = [lo of the high | hi of the high]
     const auto r = __builtin_amdgcn_permlane32_swap(lo, hi, false, false);
     lo = r[0], hi = r[1];
@@ -664,40 +651,21 @@ constexpr int B1P_FLOATS = NCHUNK * 64, B2P_FLOATS = 128;
 // transposed sets (PK_XNT, PK_DHT: channels on the lanes, points along the registers) in LDS
 enum { PK_XN = 0, PK_DH = 1, PK_XNT = 2, PK_DHT = 3 };
 constexpr int PK_TILE_U4 = 2 * 8 * 64;   // 16 KiB
-constexpr int NW_BWD = 4;   // wavefronts per workgroup, backward: 128 points; three 24 KiB slots (79 KiB: two workgroups per CU) — one record per chunk (BWD_TR) or two items
-#ifndef DFX_FF_NW_FWD
-#define DFX_FF_NW_FWD 4
-#endif
-constexpr int NW_FWD = DFX_FF_NW_FWD;   // forward: 128 points and 77 KiB of LDS, TWO workgroups per CU — one's row loads / stores run under the other's chunk loop
+constexpr int NW_BWD = 4;   // wavefronts per workgroup, backward: 128 points; three 24 KiB slots (79 KiB: two workgroups per CU), one record per chunk
+constexpr int NW_FWD = 4;   // forward: 128 points and 77 KiB of LDS, TWO workgroups per CU — one's row loads / stores run under the other's chunk loop
 template <bool BWD> constexpr int nw_of() { return BWD ? NW_BWD : NW_FWD; }
 constexpr int NBUF = 3;   // LDS chunk buffers: the stream runs two chunks ahead of the compute
-#ifndef DFX_FF_BWD_SPREAD
-#define DFX_FF_BWD_SPREAD 0   // (measured round 6, same box: 279.3 vs 278.0 us per block — no gain in the backward; the forward keeps its spread)
-#endif
 // s_setprio experiments (round 6, same-box A/Bs, profiles/r06_ab_train_prio.txt): raising a wavefront's priority inside its VALU stretch (the sampling
-// kernel runs its V slots at 3) helps the forward (652 -> 637 us) and HURTS the backward (278 -> 283 per block) and the weight-gradient kernel's
-// producer (224 -> 244): there the other wavefront of the SIMD is the one feeding the matrix pipe
-#ifndef DFX_FF_VPRIO_FWD
-#define DFX_FF_VPRIO_FWD 3
-#endif
-#ifndef DFX_FF_VPRIO_BWD
-#define DFX_FF_VPRIO_BWD 0
-#endif
-#ifndef DFX_FF_MPRIO_BWD
-#define DFX_FF_MPRIO_BWD 0   // priority inside the backward's MFMA bursts
-#endif
-#ifndef DFX_WG_PPRIO
-#define DFX_WG_PPRIO 0       // k_ff_wgrad: producer's GEGLU arithmetic
-#endif
-#ifndef DFX_WG_CPRIO
-#define DFX_WG_CPRIO 0       // k_ff_wgrad: consumer's 24-MFMA stretch
-#endif
-constexpr bool BWD_SPREAD = DFX_FF_BWD_SPREAD != 0;   // backward: ring pieces issued inside the MFMA bursts (see the loop)
+// kernel runs its V slots at 3) helped the forward (652 -> 637 us) and HURT the backward (278 -> 283 per block) and the weight-gradient kernel's
+// producer (224 -> 244): there the other wavefront of the SIMD is the one feeding the matrix pipe.  Only ff_fwd raises it; priority inside the
+// backward's MFMA bursts and the weight-gradient consumer's 24-MFMA stretch was tried too, without gain.
+constexpr int VPRIO_FWD = 3;
 // Round 6: the backward's SECOND product (dxn3 += W1a^T da + W1g^T dg) takes its A operands out of the W1a / W1g tiles of the FIRST product with the LDS
 // transpose read (ds_read_b64_tr_b16: a 16-lane group reads 16 x 4 elements and gets them back turned around — tools/ubench/tr_read_probe.hip pins the lane
-// mapping), instead of from transposed tiles of their own: a chunk is ONE 24 KiB record (not two items, 40 KiB), the ring runs two chunks ahead behind ONE
-// barrier per chunk, and the wave issues six ring pieces per chunk instead of ten.  Same bf16 values, same MFMA operand order: bit-identical gradients.
-static_assert(!(BWD_TR && BWD_SPREAD), "the spread variant belongs to the two-item ring");
+// mapping).  A chunk is ONE 24 KiB record, the ring runs two chunks ahead behind ONE barrier per chunk, and the wave issues six ring pieces per chunk.
+// Until then the operands were transposed tiles of their own (T_W1AT / T_W1GT), a chunk streamed as two items (40 KiB) behind two barriers and the wave
+// issued ten pieces (profiles/r06_ab_train_bwd_tr.txt).  Same bf16 values, same MFMA operand order: bit-identical gradients.  Issuing the two-item ring's
+// pieces from inside the MFMA bursts, as ff_fwd does, was measured on it as well: 279.3 vs 278.0 us per block, no gain in the backward.
 typedef short v4s __attribute__((ext_vector_type(4)));
 typedef short v8s __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ v4s lds_tr16(unsigned lds_addr) {
@@ -726,28 +694,21 @@ __device__ __forceinline__ void stage_record_fwd(const uint4 *frags, int j, unsi
   for (int k = 0; k < FWD_TILES * 2 / NW_FWD; ++k) dma1k(src + (k * NW_FWD + wave) * 1024, voff, lds_buf + (k * NW_FWD + wave) * 1024);
 }
 
-// Backward (BWD_TR = 0; with BWD_TR only the even items exist: item 2 j IS chunk j's record): a chunk streams as two items through a ring of three 24 KiB slots — item 2 j = [W1a | W1g | W2^T] of chunk j (tiles 0..7 and
-// 12..15: GEMM1 and the d hid product), item 2 j + 1 = [W1a^T | W1g^T] (tiles 16..23: the dxn3 product) — so that a workgroup fits into
-// half a CU's LDS.  Wave w copies pieces w, w + 4, ..: six per even item, four per odd one.
-__device__ __forceinline__ void stage_item(const uint4 *frags, int item, unsigned lds_slot, int wave, unsigned voff) {
-  const char *src = reinterpret_cast<const char *>(frags + (size_t)(item >> 1) * CHUNK_U4);
-  if (item & 1) {
+// Backward: chunk j streams as one record [W1a | W1g | W2^T] (tiles 0..7 and 12..15: GEMM1, whose tiles the dxn3 product reads turned around, and the
+// d hid product) into slot j % NBUF of a ring of three 24 KiB slots, so that a workgroup fits into half a CU's LDS.  Wave w copies pieces w, w + 4, ..:
+// six per record.
+__device__ __forceinline__ void stage_record_bwd(const uint4 *frags, int j, unsigned lds_ring, int wave, unsigned voff) {
+  const char *src = reinterpret_cast<const char *>(frags + (size_t)j * CHUNK_U4);
+  const unsigned lds_slot = lds_ring + (j % NBUF) * (BWD_TILES * 2048);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int p = k * NW_BWD + wave;
-      dma1k(src + (32 + p) * 1024, voff, lds_slot + p * 1024);
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const int p = k * NW_BWD + wave;
-      dma1k(src + (p < 16 ? p : p + 8) * 1024, voff, lds_slot + p * 1024);
-    }
+  for (int k = 0; k < 6; ++k) {
+    const int p = k * NW_BWD + wave;
+    dma1k(src + (p < 16 ? p : p + 8) * 1024, voff, lds_slot + p * 1024);
   }
 }
-// LDS tile index of pack tile t (backward: within its item's slot)
+// LDS tile index of pack tile t (backward: W2^T sits behind W1a | W1g in the slot)
 template <bool BWD>
-__device__ __forceinline__ constexpr int lt(int t) { return !BWD ? t : t >= 16 ? t - 16 : t >= 12 ? t - 4 : t; }
+__device__ __forceinline__ constexpr int lt(int t) { return BWD && t >= T_W2T ? t - 4 : t; }
 
 // The same row in the accumulator layout straight from memory: register 4 q + m of tile c = channel 32 c + 8 q + 4 hf + m (= 32 c + rho(4 q + m, hf))
 __device__ __forceinline__ void load_rows_acc(const float *__restrict__ hrow, int hf, v16f (&d)[4]) {
@@ -848,7 +809,7 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
   const RowMap m_dh(a.tiled & TL_DH, lane, pj, hf), m_dhin(a.tiled & TL_DHIN, lane, pj, hf);
   const bool at = a.at_frags != nullptr;
 
-  constexpr int PIECES = FWD_TILES * 2 / NW;   // forward: LDS-DMA instructions per wave and chunk
+  constexpr int PIECES = FWD_TILES * 2 / NW;   // LDS-DMA instructions per wave and chunk: six, forward and backward
   FFT_INIT_CHAIN(a, BWD ? 1 : 0, !BWD && !first ? trace_n : 0);   // (trace builds: the chain's later blocks append)
   FFT(1);
   // ---- prologue, memory side: this lane's rows first (the oldest requests come back first), then the tables, then the ring ----
@@ -878,7 +839,7 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
   // dropout: this tile's bit words (one lane = one point half, the forward's mapping); the backward holds the eight feed-forward words across the loop
   unsigned *dmk = DROP ? a.dmask + (size_t)(rowbase / (32 * C)) * DM_TILE + lane : nullptr;
   const unsigned long long prow = (unsigned long long)(rowbase / C) + pj;   // this lane's row of the (R, .) tensors
-  unsigned dmw = 0;   // forward: the word being assembled; backward: the word of chunks (j & ~1, + 1), requested at the top of every second chunk
+  unsigned dmw = 0;   // forward: the word being assembled; backward: the word of chunks (j & ~1, + 1), read out of the mask buffer in every even chunk
   float *b1s = reinterpret_cast<float *>(ff_smem + TAB_B1);
   float *dump = reinterpret_cast<float *>(ff_smem + TAB_GB3);   // 1 KiB nobody reads
   float *gb2 = reinterpret_cast<float *>(ff_smem + TAB_GB2);   // LayerNorm2 affine | to_out bias (attention sub-block fused in)
@@ -892,14 +853,13 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
   const float *tp2 = lo_half ? (at ? a.bo : a.b1p) : (!BWD ? a.b2p : a.b1p);
   const float tv0 = tp0[tc], tv1 = tp1[tc], tv2 = tp2[tc];
   dma1k(reinterpret_cast<const char *>(a.b1p) + wave * 1024, voff, lds0 + TAB_B1 + wave * 1024);
-  constexpr bool TR = BWD && BWD_TR;
-  // (TR, dropout) the bit word of chunks (0, 1) -> this wave's 256 bytes of the mask buffer: LDS-DMA like the ring's pieces, so that the loop's counted waits
-  // cover it (loads of one kind complete in order; a load that returns to a register does not keep that order against them — HISTORY round 6 #11)
+  // (backward, dropout) the bit word of chunks (0, 1) -> this wave's 256 bytes of the mask buffer: LDS-DMA like the ring's pieces, so that the loop's counted
+  // waits cover it (loads of one kind complete in order; a load that returns to a register does not keep that order against them — HISTORY round 6 #11)
   const unsigned *dmt = DROP ? a.dmask + (size_t)(rowbase / (32 * C)) * DM_TILE : nullptr;   // wave-uniform: this tile's words
-  if (TR && DROP) dma256(dmt, lane * 4, lds0 + TAB_GB3 + wave * 256);   // (as sixteen lanes x 16 bytes instead: measured, no difference)
+  if (BWD && DROP) dma256(dmt, lane * 4, lds0 + TAB_GB3 + wave * 256);   // (as sixteen lanes x 16 bytes instead: measured, no difference)
   if (BWD) {
-    stage_item(a.frags, 0, lds0, wave, voff);
-    stage_item(a.frags, TR ? 2 : 1, lds0 + BUF_BYTES, wave, voff);
+    stage_record_bwd(a.frags, 0, lds0, wave, voff);
+    stage_record_bwd(a.frags, 1, lds0, wave, voff);
   } else {
     if (at) {   // [A_s | M_s] of this shape -> slot 2
       const char *src = reinterpret_cast<const char *>(a.at_frags + (size_t)s * SHAPE_U4);
@@ -914,10 +874,10 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
 #pragma unroll
     for (int j = 0; j < 4; ++j) vmask |= (a.valid[s * 4 + j] != 0.f ? 1u : 0u) << j;
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // ONE round trip: rows, tables, attention fragments, the first two chunks / items
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // ONE round trip: rows, tables, attention fragments, the first two chunks
   {
-    // waves 0, 1: gamma2 | beta2 | b_o; waves 2, 3: b2 — their copies of gamma2 | beta2 go to the dump, or (TR: the dump is the mask buffer) on top of waves 0, 1's: the same values
-    float *d0 = lo_half || TR ? gb2 : dump, *d2 = lo_half ? gb2 + 2 * C : b2s;
+    // waves 0, 1: gamma2 | beta2 | b_o; waves 2, 3: b2 — their copies of gamma2 | beta2 go to the dump, or (backward: the dump is the mask buffer) on top of waves 0, 1's: the same values
+    float *d0 = lo_half || BWD ? gb2 : dump, *d2 = lo_half ? gb2 + 2 * C : b2s;
     d0[tc] = tv0, d0[C + tc] = tv1, d2[tc] = tv2;
   }
   __syncthreads();
@@ -1039,37 +999,19 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
 
 #pragma unroll 1
   for (int j = 0; j < NCHUNK; ++j) {
-    // forward: chunk j + 2 -> the slot of chunk j - 1 (every wave is past it); backward: item 2 j + 2 -> the slot of item 2 j - 1
+    // chunk j + 2 -> the slot of chunk j - 1 (every wave is past its last read: the barrier at the bottom)
     if (!BWD) {
       if (j + NBUF - 1 < NCHUNK) stage_chunk<BWD>(a.frags, j + NBUF - 1, lds0 + ((j + NBUF - 1) % NBUF) * BUF_BYTES, wave, voff);
     } else {
-      // dropout: this lane's bit word of chunks (j, j + 1), requested in front of the item's pieces; one register instead of the tile's eight words
-      // (inline asm: hipcc's own wait for a load it knows would be vmcnt(0) at the first use — behind the NEXT item's pieces).  ROUND 6 FIX: the wait that
-      // covers it is vmcnt(0) at this chunk's item boundary, NOT the counted wait of the other chunks: a load that returns to a register and the LDS-DMA
-      // pieces behind it do not complete in issue order under load — with vmcnt(6) the word was occasionally stale at B = 128 x 2048 (run-to-run
-      // differences of 2e-3 in every gradient below the first block's; tools/soak_train_streams.py with dropout; rounds 5's code had it too).  LDS-DMA
-      // pieces among themselves, and stores against them, keep the counted waits valid (loads of one kind complete in order).
-      if (!TR) {
-        if (DROP && !(j & 1)) asm volatile("global_load_dword %0, %1, off" : "=v"(dmw) : "v"(dmk + (j >> 1) * 64) : "memory");
-        if (!BWD_SPREAD && 2 * j + 2 < 2 * NCHUNK) stage_item(a.frags, 2 * j + 2, lds0 + ((2 * j + 2) % 3) * BUF_BYTES, wave, voff);
-      } else {
-        // one record per chunk, two ahead: chunk j + 2 -> the slot of chunk j - 1 (every wave is past its last read: the barrier below).  Odd chunks first
-        // request the bit word of the NEXT pair (its predecessor was read into a register in chunk j - 1): in front of the pieces, so "at most six
-        // outstanding" at this chunk's end covers it
-        if (DROP && (j & 1) && j + 1 < NCHUNK) dma256(dmt + ((j + 1) >> 1) * 64, lane * 4, lds0 + TAB_GB3 + wave * 256);
-        if (j + 2 < NCHUNK) stage_item(a.frags, 2 * (j + 2), lds0 + ((j + 2) % 3) * BUF_BYTES, wave, voff);
-      }
+      // Dropout: odd chunks first request the bit word of the NEXT pair (its predecessor was read into a register in chunk j - 1): in front of the pieces,
+      // so "at most six outstanding" at this chunk's end covers it.  The word travels by LDS-DMA like the pieces because loads of one kind complete in
+      // order, and a load that returns to a register does not keep that order against them: until round 6 the word was such a load under a counted
+      // wait, and occasionally stale at B = 128 x 2048 (run-to-run differences of 2e-3 in every gradient below the first block's;
+      // tools/soak_train_streams.py with dropout).  LDS-DMA pieces among themselves, and stores against them, keep the counted waits valid.
+      if (DROP && (j & 1) && j + 1 < NCHUNK) dma256(dmt + ((j + 1) >> 1) * 64, lane * 4, lds0 + TAB_GB3 + wave * 256);
+      if (j + 2 < NCHUNK) stage_record_bwd(a.frags, j + 2, lds0, wave, voff);
     }
-    // Round 6 (BWD_SPREAD): the wave's pieces of the next chunk's two items are issued from INSIDE the two MFMA bursts, one behind every fourth MFMA (six
-    // of item 2 j + 2 in the first burst, four of item 2 j + 3 in the second) instead of back to back in front of them, where each LDS-DMA instruction
-    // cost the wave ~100 cycles of issue (MI355X_MICROARCH.md).  Same slots, same counted waits.  The last chunk has nothing to request: its pieces go
-    // to a 1 KiB dump nobody reads (no branch in the bursts).
-    const bool nxt = j + 1 < NCHUNK;
-    const char *isrc = reinterpret_cast<const char *>(a.frags + (size_t)(nxt ? j + 1 : j) * CHUNK_U4) + wave * 1024;
-    const unsigned idst0 = nxt ? lds0 + ((2 * j + 2) % 3) * BUF_BYTES + wave * 1024 : lds0 + TAB_GB3;
-    const unsigned idst1 = nxt ? lds0 + ((2 * j + 3) % 3) * BUF_BYTES + wave * 1024 : lds0 + TAB_GB3;
-    const unsigned istep = nxt ? 4096u : 0u;
-    const uint4 *fr = reinterpret_cast<const uint4 *>(ff_smem + (BWD && !TR ? (2 * j) % 3 : j % NBUF) * BUF_BYTES) + lane;
+    const uint4 *fr = reinterpret_cast<const uint4 *>(ff_smem + (j % NBUF) * BUF_BYTES) + lane;
     const uint4 *fs0 = fr - lane + w1_slot(lane, 0), *fs1 = fr - lane + w1_slot(lane, 1);
     auto frag = [&](int t, int u) -> uint4 { return (t < T_W2 ? (u ? fs1 : fs0) : fr)[(lt<BWD>(t) * 2 + u) * 64]; };   // (W1a / W1g: w1_slot)
     // ---- [a | g] = b1 + W1 xn3 ----
@@ -1102,11 +1044,7 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
       __builtin_amdgcn_sched_barrier(0);
       v16f hv;
 #pragma unroll
-#ifdef DFX_ABL_FWD_GELU   // (ablation builds only, tools/experiments/ab_train_variants.sh: wrong numbers, the loop without its GELU arithmetic)
-      for (int i = 0; i < 8; ++i) set_pair(hv, i, pair(av, i) * pair(gv, i));
-#else
       for (int i = 0; i < 8; ++i) set_pair(hv, i, pair(av, i) * gelu_f2(pair(gv, i)));
-#endif
       if (DROP) {
         // dropout behind the GEGLU (attention.py:84): element (row, unit 32 j + 8 q + 4 hf + m) = group row * 64 + 4 j + q of the site; the scale rides on `a`
         unsigned w[4][2];
@@ -1131,16 +1069,11 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
 #pragma unroll
       for (int r = 0; r < 16; ++r) dhid[r] = 0.f;
       __builtin_amdgcn_sched_barrier(0);
-      if (DFX_FF_MPRIO_BWD) __builtin_amdgcn_s_setprio(DFX_FF_MPRIO_BWD);
 #pragma unroll
       for (int m = 0; m < 24; ++m) {
         if (m >= 16) dhid = mfma(P[m & 7], dhb[(m - 16) >> 1][(m - 16) & 1], dhid);
         else if (m & 1) gv = mfma(P[m & 7], xn[m >> 2][(m >> 1) & 1], gv);
         else av = mfma(P[m & 7], xn[m >> 2][(m >> 1) & 1], av);
-        if (BWD_SPREAD && m % 4 == 0) {   // piece k of item 2 j + 2 (tiles 0..7, 12..15 of the next chunk): destination KiB 4 k + wave, source KiB + 8 from 16 on
-          const int k = m / 4;
-          dma1k(isrc + (k < 4 ? k * 4 : k * 4 + 8) * 1024, voff, idst0 + k * istep);
-        }
         if (m + 8 < 24) P[m & 7] = f1(m + 8);
       }
 #pragma unroll
@@ -1149,23 +1082,9 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
-      // ---- item boundary: item 2 j + 1 must have landed (loads complete in order: only the six pieces of item 2 j + 2, requested at the
-      // top of this chunk, may still be out), every wave is done with item 2 j -> its slot takes item 2 j + 3.  The boundary sits in FRONT
-      // of the GEGLU arithmetic now, so that the second burst's first eight fragments travel while the VALU works ----
+      // ---- the second burst's first eight fragments are requested in FRONT of the GEGLU arithmetic, so that they travel while the VALU works ----
       FFT(10);
-      if (DFX_FF_MPRIO_BWD) __builtin_amdgcn_s_setprio(0);
-      if (!TR) {
-      if (2 * j + 2 < 2 * NCHUNK && !(DROP && !(j & 1))) asm volatile("s_waitcnt vmcnt(6)" : "+v"(dmw)::"memory");   // (dmw: its readers stay behind the wait)
-      else asm volatile("s_waitcnt vmcnt(0)" : "+v"(dmw)::"memory");   // (the last chunk; and with dropout every even chunk: its mask word must have landed)
-      FFT(11);
-#ifndef DFX_ABL_BWD_NOBAR   // (ablation builds only: racy, wrong numbers — what do the loop's two barriers cost?)
-      __syncthreads();
-#endif
-      FFT(12);
-      if (!BWD_SPREAD && 2 * j + 3 < 2 * NCHUNK) stage_item(a.frags, 2 * j + 3, lds0 + ((2 * j + 3) % 3) * BUF_BYTES, wave, voff);
-      }
-      const uint4 *fr2 = reinterpret_cast<const uint4 *>(ff_smem + ((2 * j + 1) % 3) * BUF_BYTES) + lane;
-      // TR: the lane's address inside a 2 KiB W1a / W1g tile for the transpose read.  Lane 16 G + s of group G supplies row (hidden unit) 4 (G >> 1) + (s >> 2)
+      // The lane's address inside a 2 KiB W1a / W1g tile for the transpose read.  Lane 16 G + s of group G supplies row (hidden unit) 4 (G >> 1) + (s >> 2)
       // (+ 16 u + 8 r by the immediate), channels 16 (G & 1) + 4 (s & 3) .. + 3 — in the tile's image: unit G & 1, lane slot row + 32 ((s & 3) >> 1), byte
       // 8 (s & 1) — and receives hidden units 4 (G >> 1) + 0 .. 3 of channel 16 (G & 1) + s: elements 4 r .. 4 r + 3 of the A operand (K in register order)
       // (the row's slot through w1_slot: bits 2, 3 of the row carry the unit and the k half, so r = 0 / 1 need a base each)
@@ -1174,44 +1093,33 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
       const unsigned trb1 = lds0 + (j % 3) * BUF_BYTES + (tu * 64 + w1_slot(trow + 8, tu)) * 16 + 8 * (lane & 1);
       // second burst, MFMA m: row tile ct = m & 3, operand q = m >> 2 (W1a^T unit 0, unit 1, W1g^T unit 0, unit 1: the order per accumulator)
       auto f2 = [&](int m) -> uint4 {
-        if (TR) {
-          const unsigned o = ((m >> 3) * 4 + (m & 3)) * 2048 + ((m >> 2) & 1) * 256;
-          return __builtin_bit_cast(uint4, __builtin_shufflevector(lds_tr16(trb0 + o), lds_tr16(trb1 + o), 0, 1, 2, 3, 4, 5, 6, 7));
-        }
-        return fr2[(lt<BWD>(((m >> 2) < 2 ? T_W1AT : T_W1GT) + (m & 3)) * 2 + ((m >> 2) & 1)) * 64];
+        const unsigned o = ((m >> 3) * 4 + (m & 3)) * 2048 + ((m >> 2) & 1) * 256;
+        return __builtin_bit_cast(uint4, __builtin_shufflevector(lds_tr16(trb0 + o), lds_tr16(trb1 + o), 0, 1, 2, 3, 4, 5, 6, 7));
       };
 #pragma unroll
       for (int i = 0; i < 8; ++i) P[i] = f2(i);
       __builtin_amdgcn_sched_barrier(0);
       if (DROP) {   // d hid in front of the dropout = selected d hid behind it (the scale rides on `a` and on W1a^T)
-        if (TR && !(j & 1)) dmw = reinterpret_cast<const unsigned *>(ff_smem + TAB_GB3)[wave * 64 + lane];   // (landed: the previous chunk's end, or the prologue)
+        if (!(j & 1)) dmw = reinterpret_cast<const unsigned *>(ff_smem + TAB_GB3)[wave * 64 + lane];   // (landed: the previous chunk's end, or the prologue)
         drop_select(dhid, (j & 1) ? dmw >> 16 : dmw);
       }
       // ---- GEGLU backward on the registers ----
-      if (DFX_FF_VPRIO_BWD) __builtin_amdgcn_s_setprio(DFX_FF_VPRIO_BWD);
       v16f da, dg;
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         v2f f, d;
-#ifdef DFX_ABL_BWD_GELU
-        f = pair(gv, i), d = splat2(1.0f);
-#else
         gelu_fd2(pair(gv, i), f, d);
-#endif
         const v2f dh2 = pair(dhid, i);
         set_pair(da, i, dh2 * f);
         set_pair(dg, i, dh2 * pair(av, i) * d);
       }
       const uint4 a0 = pack8(da, 0), a1 = pack8(da, 1), g0 = pack8(dg, 0), g1 = pack8(dg, 1);
       __builtin_amdgcn_sched_barrier(0);
-      if (DFX_FF_VPRIO_BWD) __builtin_amdgcn_s_setprio(0);
-      if (DFX_FF_MPRIO_BWD) __builtin_amdgcn_s_setprio(DFX_FF_MPRIO_BWD);
       // ---- dxn3 += W1a^T da + W1g^T dg ----
 #pragma unroll
       for (int m = 0; m < 16; ++m) {
         const int q = m >> 2;
         acc[m & 3] = mfma(P[m & 7], q == 0 ? a0 : q == 1 ? a1 : q == 2 ? g0 : g1, acc[m & 3]);
-        if (BWD_SPREAD && m % 4 == 0) dma1k(isrc + (32 + m) * 1024, voff, idst1 + (m / 4) * istep);   // piece m / 4 of item 2 j + 3 (tiles 16..23)
         if (m + 8 < 16) P[m & 7] = f2(m + 8);
       }
 #pragma unroll
@@ -1221,33 +1129,16 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (BWD && DFX_FF_MPRIO_BWD) __builtin_amdgcn_s_setprio(0);
-    // chunk j + 1 must have landed: loads complete in order, so "at most PIECES outstanding" leaves only chunk j + 2's pieces
-    // (whatever the order between loads and the backward's stores); no new pieces in the last two iterations -> drain
+    // chunk j + 1 (and, backward, an odd chunk's bit word) must have landed: loads complete in order, so "at most PIECES outstanding" leaves only
+    // chunk j + 2's six pieces (whatever the order between loads and the backward's stores); no new pieces in the last two iterations -> drain
     FFT(13);
-    if (TR) {    // chunk j + 1 (and an odd chunk's bit word) must have landed; the six pieces of chunk j + 2 may still be out
-      if (j + 2 < NCHUNK) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else if (BWD) {   // item 2 j + 2 must have landed; the four pieces of item 2 j + 3 may still be out
-      if (2 * j + 3 < 2 * NCHUNK) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else if (NBUF > 2 && j + 2 < NCHUNK) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PIECES) : "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    if (j + 2 < NCHUNK) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PIECES) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     FFT(14);
-#ifdef DFX_ABL_BWD_NOBAR
-    if (!BWD) __syncthreads();
-#else
     __syncthreads();
-#endif
     FFT(15);
   }
   FFT(3);
-#ifdef DFX_ABL_BWD_NOBAR
-  __syncthreads();
-#endif
   if (!BWD) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) hc[c] = acc[c];   // (dead in the single-block kernel)
@@ -1557,7 +1448,7 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// The forward of one block, round 6 (FWD_F16): the sampling kernel's slot structure on the training kernel's rows.
+// The forward of one block, round 6: the sampling kernel's slot structure on the training kernel's rows.
 //   * records are SKEWED: record j = [W1a | W1g of hidden chunk j | W2 of chunk j - 1] (k_ff_pack), so an iteration is ONE uninterrupted burst of 24 MFMAs
 //     (GEMM2 of chunk j - 1, GEMM1 of chunk j) behind ONE stretch of VALU (the GEGLU of chunk j - 1): 17 iterations, the first without GEMM2, the last
 //     without GEMM1;
@@ -1738,7 +1629,7 @@ __device__ __forceinline__ void ff_fwd(const FfArgs &a, const FfArgs &next, cons
     __builtin_amdgcn_sched_barrier(0);
     uint4 hh[2];
     h2 aa[8], gg[8];
-    if (DFX_FF_VPRIO_FWD) __builtin_amdgcn_s_setprio(DFX_FF_VPRIO_FWD);
+    __builtin_amdgcn_s_setprio(VPRIO_FWD);
     if (S2) {
       if (DROP) {   // dropout behind the GEGLU of chunk j - 1 (attention.py:84), selected on `a`: element (row, unit 32 (j - 1) + 8 q + 4 hf + m) = group row * 64 + 4 (j - 1) + q
         const int jj = j - 1;
@@ -1759,7 +1650,7 @@ __device__ __forceinline__ void ff_fwd(const FfArgs &a, const FfArgs &next, cons
       geglu16_f16_math(aa, gg, hh);
       asm volatile("" : "+v"(hh[0].x), "+v"(hh[0].y), "+v"(hh[0].z), "+v"(hh[0].w), "+v"(hh[1].x), "+v"(hh[1].y), "+v"(hh[1].z), "+v"(hh[1].w));
     }
-    if (DFX_FF_VPRIO_FWD) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int m = 0; m < NM; ++m) {
@@ -1873,7 +1764,7 @@ template <bool BWD, bool DROP>
 __global__ __launch_bounds__(nw_of<BWD>() * 64, 2) void k_ff(FfArgs a) {
   v16f hc[4];
   int tn = 0;
-  if constexpr (!BWD && FWD_F16) {
+  if constexpr (!BWD) {
     if (a.at_frags) {   // (the attention sub-block inside: every shipped launch; dfx_debug_train_fused(2) keeps the round-5 body)
       float tv[3];
       ff_fwd<DROP>(a, a, false, true, false, hc, tv, tn);
@@ -1897,12 +1788,8 @@ __global__ __launch_bounds__(NW_FWD * 64, 2) void k_ff_fwd_chain(FfChain ch) {
   int tn = 0;   // (trace builds only)
   // (Round 6, measured and dropped: the second workgroup of a CU — HW_REG_LDS_ALLOC base != 0 — waiting 16 / 24 / 32 k cycles once at the start, so that the two
   // co-resident workgroups' VALU-only stretches do not coincide: 661 / 672 / 672 us against 646-651 — they are not in step to begin with, the wait is pure cost)
-  if constexpr (FWD_F16) {
-    float tv[3];
-    for (int b = 0; b < ch.n; ++b) ff_fwd<DROP>(ch.blk[b], ch.blk[b + 1 < ch.n ? b + 1 : b], b + 1 < ch.n, b == 0, b > 0, hc, tv, tn);
-  } else {
-    for (int b = 0; b < ch.n; ++b) ff_run<false, DROP>(ch.blk[b], b == 0, hc, tn);
-  }
+  float tv[3];
+  for (int b = 0; b < ch.n; ++b) ff_fwd<DROP>(ch.blk[b], ch.blk[b + 1 < ch.n ? b + 1 : b], b + 1 < ch.n, b == 0, b > 0, hc, tv, tn);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -1935,22 +1822,13 @@ constexpr int WG_CHUNKS = 4, WG_NW = 2 * WG_CHUNKS;   // two wavefronts per chun
 // LDS: the tiles ([xn3 | dh] fragments, 16 KiB) travel in a ring of three slots, two tiles ahead of the producers (L2 latency under load
 // is longer than one tile's arithmetic); the consumers turn tile k around (two MFMAs with a 0/1 selection matrix per 32 x 32 tile, exact)
 // into one of two 16 KiB slots while they multiply tile k - 1
-// Round 6 (WG_TR, measured and left OFF): the consumers read the turned operands straight out of the ring's tile with the LDS transpose read (ds_read_b64_tr_b16,
-// as k_ff<true>'s second product does; the tile's 1 KiB fragments land w1_slot-swizzled — the LDS-DMA lanes fetch each other's 16 bytes — so that the reads are
-// conflict-free): no selection MFMAs, no packs and LDS stores of a turned copy, no turned slots; the ring has four slots (tile k - 1 is still being read while
-// tile k + 2 lands).  Bit-identical, 0 bank conflicts — and 2.3 % SLOWER (alternating same-box runs 225.0 / 226.0 against 230.0 / 231.7 us per block,
-// profiles/r06_ab_train_wgrad_tr.txt): the turning is shared by the four consumers (each turns a quarter, all read 16 whole fragments back with ds_read_b128),
-// the transpose read doubles every consumer's read instructions in front of its MFMAs, and the producer, not the consumer, is this kernel's critical wavefront.
-#ifndef DFX_WG_TR
-#define DFX_WG_TR 0
-#endif
-#ifndef DFX_WG_CSTAGE
-#define DFX_WG_CSTAGE 1   // the consumers issue the ring's LDS-DMA pieces (see stage)
-#endif
-constexpr bool WG_CSTAGE = DFX_WG_CSTAGE != 0;
-constexpr bool WG_TR = DFX_WG_TR != 0;
-constexpr int WG_SLOTS = WG_TR ? 4 : 3, WG_AHEAD = 2;
-constexpr int WG_RING_A = 0, WG_RING_T = WG_SLOTS * 16384, WG_RING = (WG_SLOTS + (WG_TR ? 0 : 2)) * 16384, WG_PACKS = 2 * WG_CHUNKS * 6 * 1024, WG_LDS = WG_RING + WG_PACKS;
+// Round 6, measured and dropped: the consumers reading the turned operands straight out of the ring's tile with the LDS transpose read (ds_read_b64_tr_b16, as
+// k_ff<true>'s second product does; a ring of four slots, no selection MFMAs, no turned slots).  Bit-identical, 0 bank conflicts — and 2.3 % SLOWER
+// (alternating same-box runs 225.0 / 226.0 against 230.0 / 231.7 us per block, profiles/r06_ab_train_wgrad_tr.txt): the turning is shared by the four consumers
+// (each turns a quarter, all read 16 whole fragments back with ds_read_b128), the transpose read doubled every consumer's read instructions in front of its
+// MFMAs, and the producer, not the consumer, is this kernel's critical wavefront.
+constexpr int WG_SLOTS = 3, WG_AHEAD = 2;
+constexpr int WG_RING_A = 0, WG_RING_T = WG_SLOTS * 16384, WG_RING = (WG_SLOTS + 2) * 16384, WG_PACKS = 2 * WG_CHUNKS * 6 * 1024, WG_LDS = WG_RING + WG_PACKS;
 constexpr int WG_MASK = WG_LDS, WG_LDS_DROP = WG_LDS + WG_SLOTS * 2048;   // dropout: the tiles' bit words (2 KiB each) in a ring of their own, same slots
 template <bool DROP>
 __global__ __launch_bounds__(WG_NW * 64, 2) void k_ff_wgrad(FwArgs a) {
@@ -1959,68 +1837,45 @@ __global__ __launch_bounds__(WG_NW * 64, 2) void k_ff_wgrad(FwArgs a) {
   const int pj = lane & 31;
   const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)fw_smem);
   const unsigned voff = lane * 16;
-#ifdef DFX_WG_PAIR_ADJACENT
-  const int cl = wave >> 1;
-  const bool consumer = wave & 1;
-#else
   const int cl = wave & (WG_CHUNKS - 1);
   const bool consumer = wave >= WG_CHUNKS;
-#endif
   // workgroup ids are dealt round-robin over the 8 XCDs: with the slab index in the low bits the four workgroups that stream the same
   // slab (one per chunk group) share an XCD, i.e. one L2 — the slab leaves HBM once instead of four times (nslab is a multiple of 8
   // for all but tiny inputs)
   const int cg = blockIdx.x / a.nslab, slab = blockIdx.x % a.nslab, j = cg * WG_CHUNKS + cl;
   const long long per = (a.ntiles + a.nslab - 1) / a.nslab, t0 = (long long)slab * per, t1 = t0 + per < a.ntiles ? t0 + per : a.ntiles;
   const int nt = t1 > t0 ? (int)(t1 - t0) : 0;
-  // iteration k requests tile k + 2: two 1 KiB pieces per wavefront
+  // Iteration k requests tile k + 2, and the CONSUMERS request the whole tile (consumer cl: pieces cl, cl + 4 of the xhat3 fragments of pk, cl + 8, cl + 12 of
+  // the dh fragments — pk's second set, or the hi half of the gradient tile itself; with dropout consumers 0 and 1 one KiB of the tile's eight feed-forward
+  // bit words each): the producers are this kernel's critical wavefronts and keep their issue slots for the MFMAs and the GEGLU arithmetic.  (Every
+  // wavefront requesting two pieces of its own was the first version: profiles/r06_ab_train_wgrad_cstage.txt.)
   constexpr int AHEAD = WG_AHEAD;
-  const unsigned voffq[2] = {WG_TR ? w1_slot(lane, 0) * 16u : voff, WG_TR ? w1_slot(lane, 1) * 16u : voff};   // (piece 2 wave + q is a fragment of unit q)
+  // (Both entries are the lane's plain offset: the array is what is left of the transpose-read trial's per-unit offsets.  hipcc keeps it in registers and
+  // emits the same instructions for `voff`, but lists the producer's register kills in another order, and the clean-up of this header was pinned by a
+  // byte-identical assembly listing.  A change that may differ in assembler comments can write `voff`.)
+  const unsigned voffq[2] = {voff, voff};
   auto stage = [&](int k) {
-    if (WG_CSTAGE) {
-      // the CONSUMERS request the whole tile (consumer cl: pieces cl, cl + 4, cl + 8, cl + 12; with dropout consumers 0 and 1 one KiB of the bit words each):
-      // the producers are this kernel's critical wavefronts and keep their issue slots for the MFMAs and the GEGLU arithmetic
-      if (consumer && k + AHEAD < nt) {
-        const char *pk = reinterpret_cast<const char *>(a.pk + (size_t)(t0 + k + AHEAD) * PK_TILE_U4);
-        const char *dh = reinterpret_cast<const char *>(a.dhf + (size_t)(t0 + k + AHEAD) * PK_TILE_U4) - 8192;
-        const unsigned slot = __builtin_amdgcn_readfirstlane((unsigned)((k + AHEAD) % WG_SLOTS));
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int p = cl + 4 * q;
-          dma1k((q < 2 ? pk : dh) + p * 1024, voffq[p & 1], lds0 + WG_RING_A + slot * 16384 + p * 1024);
-        }
-        if (DROP && cl < 2)
-          dma1k(reinterpret_cast<const char *>(a.dmask + (size_t)(t0 + k + AHEAD) * DM_TILE) + cl * 1024, voff, lds0 + WG_MASK + slot * 2048 + cl * 1024);
-      }
-      return;
-    }
-    if (k + AHEAD < nt) {
-      // pieces 0 .. 7 (waves 0 .. 3): the xhat3 fragments of pk; 8 .. 15: the dh fragments — pk's second set, or the hi half of the gradient tile itself
-      const char *src = wave >= WG_NW / 2 ? reinterpret_cast<const char *>(a.dhf + (size_t)(t0 + k + AHEAD) * PK_TILE_U4) - 8192
-                                          : reinterpret_cast<const char *>(a.pk + (size_t)(t0 + k + AHEAD) * PK_TILE_U4);
+    if (consumer && k + AHEAD < nt) {
+      const char *pk = reinterpret_cast<const char *>(a.pk + (size_t)(t0 + k + AHEAD) * PK_TILE_U4);
+      const char *dh = reinterpret_cast<const char *>(a.dhf + (size_t)(t0 + k + AHEAD) * PK_TILE_U4) - 8192;
       const unsigned slot = __builtin_amdgcn_readfirstlane((unsigned)((k + AHEAD) % WG_SLOTS));   // (wave-uniform: the LDS address goes through m0)
 #pragma unroll
-      for (int q = 0; q < 2; ++q) dma1k(src + (wave * 2 + q) * 1024, voffq[q], lds0 + WG_RING_A + slot * 16384 + (wave * 2 + q) * 1024);
-      if (DROP)   // + this tile's eight feed-forward bit words: 256 B per wavefront
-        dma256(reinterpret_cast<const char *>(a.dmask + (size_t)(t0 + k + AHEAD) * DM_TILE) + wave * 256, lane * 4,
-               lds0 + WG_MASK + slot * 2048 + wave * 256);
+      for (int q = 0; q < 4; ++q) {
+        const int p = cl + 4 * q;
+        dma1k((q < 2 ? pk : dh) + p * 1024, voffq[p & 1], lds0 + WG_RING_A + slot * 16384 + p * 1024);
+      }
+      if (DROP && cl < 2)
+        dma1k(reinterpret_cast<const char *>(a.dmask + (size_t)(t0 + k + AHEAD) * DM_TILE) + cl * 1024, voff, lds0 + WG_MASK + slot * 2048 + cl * 1024);
     }
   };
   // top of iteration k: everything requested before iteration k - 1 has landed, i.e. tiles <= k (loads complete in order; the last iterations
-  // request nothing: drain)
+  // request nothing: drain).  Only the consumers have pieces in flight: the newest tile's four — five with a KiB of bit words — may stay out
   auto arrive = [&](int k) {
-    if (WG_CSTAGE) {   // (only the consumers have pieces in flight: the newest tile's four — five with a KiB of bit words — may stay out)
-      if (consumer) {
-        if (k + AHEAD - 1 >= nt) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (DROP && cl < 2) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      }
-      __syncthreads();
-      return;
+    if (consumer) {
+      if (k + AHEAD - 1 >= nt) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      else if (DROP && cl < 2) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     }
-    if (k + AHEAD - 1 < nt) {
-      if (DROP) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   };
   uint4 *packs = reinterpret_cast<uint4 *>(fw_smem + WG_RING);
@@ -2051,18 +1906,17 @@ __global__ __launch_bounds__(WG_NW * 64, 2) void k_ff_wgrad(FwArgs a) {
     const int dm_off = (j >> 1) * 64 + 32 * ((pj >> 2) & 1) + 4 * (lane >> 5), dm_bit = 16 * (j & 1) + 4 * (pj >> 3) + (pj & 3);
     // 24 MFMAs of tile k: [a | g]^T = xhat3 W1^T + b1, d hid^T = dh W2
     auto mm = [&](int k, v16f &av, v16f &gv, v16f &dv) {
-      const uint4 *tb = reinterpret_cast<const uint4 *>(fw_smem + WG_RING_A + (k % WG_SLOTS) * 16384);
-      const uint4 *tlu[2] = {tb + (WG_TR ? w1_slot(lane, 0) : lane), tb + (WG_TR ? w1_slot(lane, 1) : lane)};
+      const uint4 *tl = reinterpret_cast<const uint4 *>(fw_smem + WG_RING_A + (k % WG_SLOTS) * 16384) + lane;
 #pragma unroll
       for (int r = 0; r < 16; ++r) av[r] = ba, gv[r] = bg, dv[r] = 0.f;
 #pragma unroll
       for (int c = 0; c < 4; ++c)
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-          const uint4 x = tlu[u][(PK_XN * 8 + c * 2 + u) * 64];
+          const uint4 x = tl[(PK_XN * 8 + c * 2 + u) * 64];
           av = mfma(x, w1a[c][u], av);
           gv = mfma(x, w1g[c][u], gv);
-          dv = mfma(tlu[u][(PK_DH * 8 + c * 2 + u) * 64], w2t[c][u], dv);
+          dv = mfma(tl[(PK_DH * 8 + c * 2 + u) * 64], w2t[c][u], dv);
         }
     };
     // GEGLU forward / backward on tile k's accumulators -> six fragments in LDS
@@ -2090,11 +1944,7 @@ __global__ __launch_bounds__(WG_NW * 64, 2) void k_ff_wgrad(FwArgs a) {
         for (int e = 0; e < 8; ++e) {   // (scalar fp32 here: the packed forms of gelu_fd2 made this kernel 5 % SLOWER — 236 -> 249 us)
           const int r = 8 * u + e;
           float f, d;
-#ifdef DFX_ABL_WG_ACT
-          f = gv[r], d = 1.0f;
-#else
           gelu_fd(gv[r], f, d);
-#endif
           const float hr = av[r] * f;
           hv[e] = DROP ? __builtin_bit_cast(float, __builtin_bit_cast(unsigned, hr) & keepm[r]) : hr;
           da[e] = dv[r] * f;
@@ -2119,9 +1969,7 @@ __global__ __launch_bounds__(WG_NW * 64, 2) void k_ff_wgrad(FwArgs a) {
         v16f av, gv, dv;
         mm(k, av, gv, dv);
         if (k < 12) FFT(14);
-        if (DFX_WG_PPRIO) __builtin_amdgcn_s_setprio(DFX_WG_PPRIO);
         act(k, av, gv, dv);
-        if (DFX_WG_PPRIO) __builtin_amdgcn_s_setprio(0);
         if (k < 12) FFT(13);
       }
     }
@@ -2146,8 +1994,6 @@ __global__ __launch_bounds__(WG_NW * 64, 2) void k_ff_wgrad(FwArgs a) {
     for (int e = 0; e < 8; ++e) o[e] = (__bf16)(pj == 16 * u + 8 * (lane >> 5) + e ? 1.0f : 0.0f);
     sel[u] = *reinterpret_cast<const uint4 *>(o);
   }
-  const int ctu = (lane >> 4) & 1, ctrow = 4 * (lane >> 5) + ((lane & 15) >> 2) + 32 * ((lane & 3) >> 1);
-  const unsigned ctr0 = (ctu * 64 + w1_slot(ctrow, ctu)) * 16 + 8 * (lane & 1), ctr1 = (ctu * 64 + w1_slot(ctrow + 8, ctu)) * 16 + 8 * (lane & 1);
   for (int k = 0; k <= nt; ++k) {
     if (k < 12) FFT(20);
     arrive(k);
@@ -2156,7 +2002,7 @@ __global__ __launch_bounds__(WG_NW * 64, 2) void k_ff_wgrad(FwArgs a) {
     // (Round 6, measured and dropped: issuing the selection MFMAs first, then tile k - 1's fragment reads and multiplications one gradient at a time, and the
     // turned tile's four LDS stores last — so that the reads do not queue behind the read -> MFMA -> MFMA -> pack -> store chain — keeps 32 more registers
     // alive beside the 192 accumulators and reads xn3^T twice: 243 against 231 us per block, profiles/r06_ab_train_wgrad_reorder.txt)
-    if (!WG_TR && k < nt) {   // tile k turned around for the next iteration: consumer cl takes channel tile cl of xn3 and of dh
+    if (k < nt) {   // tile k turned around for the next iteration: consumer cl takes channel tile cl of xn3 and of dh
       const uint4 *tl = reinterpret_cast<const uint4 *>(fw_smem + WG_RING_A + (k % WG_SLOTS) * 16384) + lane;
       uint4 *to = reinterpret_cast<uint4 *>(fw_smem + WG_RING_T + (k & 1) * 16384) + lane;
       v16f z;
@@ -2173,15 +2019,8 @@ __global__ __launch_bounds__(WG_NW * 64, 2) void k_ff_wgrad(FwArgs a) {
     const uint4 *tl = reinterpret_cast<const uint4 *>(fw_smem + WG_RING_T + ((k - 1) & 1) * 16384) - 16 * 64 + lane;   // (index the slot by PK_XNT, PK_DHT)
     const uint4 *pi = packs + (((k - 1) & 1) * WG_CHUNKS + cl) * 6 * 64 + lane;
     const uint4 h0 = pi[0 * 64], h1 = pi[1 * 64], a0 = pi[2 * 64], a1 = pi[3 * 64], g0 = pi[4 * 64], g1 = pi[5 * 64];
-    // WG_TR: operand (kind, channel tile c, K unit uk) = channels on the lanes, points k_reg(uk, hf, e) along the registers, turned out of tile k - 1's own
-    // fragments: lane 16 G + s supplies point row 16 uk + 8 r + 4 (G >> 1) + (s >> 2), channels 16 (G & 1) + 4 (s & 3) .. + 3 (see k_ff<true>'s trb0 / trb1)
-    const unsigned tsb = lds0 + WG_RING_A + ((k - 1) % WG_SLOTS) * 16384;
-    auto turned = [&](int kind, int c, int uk) -> uint4 {
-      if (!WG_TR) return tl[((kind ? PK_DHT : PK_XNT) * 8 + c * 2 + uk) * 64];
-      const unsigned o = tsb + (kind * 8 + c * 2) * 1024 + uk * 256;
-      return __builtin_bit_cast(uint4, __builtin_shufflevector(lds_tr16(o + ctr0), lds_tr16(o + ctr1), 0, 1, 2, 3, 4, 5, 6, 7));
-    };
-    if (DFX_WG_CPRIO) __builtin_amdgcn_s_setprio(DFX_WG_CPRIO);
+    // operand (kind, channel tile c, K unit uk) of the turned tile k - 1: channels on the lanes, points k_reg(uk, hf, e) along the registers
+    auto turned = [&](int kind, int c, int uk) -> uint4 { return tl[((kind ? PK_DHT : PK_XNT) * 8 + c * 2 + uk) * 64]; };
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const uint4 x0 = turned(0, c, 0), x1 = turned(0, c, 1);
@@ -2190,7 +2029,6 @@ __global__ __launch_bounds__(WG_NW * 64, 2) void k_ff_wgrad(FwArgs a) {
       dWa[c] = mfma(a1, x1, mfma(a0, x0, dWa[c]));
       dWg[c] = mfma(g1, x1, mfma(g0, x0, dWg[c]));
     }
-    if (DFX_WG_CPRIO) __builtin_amdgcn_s_setprio(0);
     if (k < 12) FFT(23);
   }
   float *out = a.part + ((size_t)slab * NCHUNK + j) * 12 * 1024 + lane;

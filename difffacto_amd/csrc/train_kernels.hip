@@ -240,14 +240,10 @@ __global__ __launch_bounds__(1024) void k_sum_parts_jobs(SumJobs jobs, int npart
 
 __device__ __forceinline__ float gelu_erf(float g) { return 0.5f * g * (1.f + erff(g * 0.70710678118654752440f)); }
 
-// [a | g] itself is stored as bf16 in bf16 mode (-DDFX_TRAIN_AG_F32 keeps it fp32): written once and read twice per block, it
+// [a | g] itself is stored as bf16 in bf16 mode: written once and read twice per block, it
 // is the largest saved tensor (1 GB at B = 128 x 2048).  Unlike the product-only tensors this IS lossy for the backward:
 // gelu'(g) and a are taken from the rounded values (the tolerance test covers it).
-#ifdef DFX_TRAIN_AG_F32
-constexpr bool AG_BF16 = false;
-#else
 constexpr bool AG_BF16 = true;
-#endif
 template <bool BF>
 __device__ __forceinline__ v4f load4(const float *base, size_t idx) {
   if (BF) return __builtin_convertvector(*reinterpret_cast<const v4bf *>(reinterpret_cast<const __bf16 *>(base) + idx), v4f);
@@ -2310,7 +2306,7 @@ int dfx_denoiser_train_forward(const dfx_denoiser_weights *wt, void *workspace, 
       // q, P, att, xn2, xn3, [a | g], hid never exist in memory
       dfx::ffused::FfArgs fa{};
       fa.frags = w.ff_frags[i], fa.b2p = w.ff_b2p[i], fa.g3 = bw.norm3_w, fa.b3 = bw.norm3_b;
-      fa.b1p = w.ff_b1p[i] + (dfx::ffused::FWD_F16 && t_attn_in_ff ? 2 * dfx::ffused::B1P_FLOATS : 0);   // ff_fwd's table: scaled like its W1 tiles (PackArgs::b1ps)
+      fa.b1p = w.ff_b1p[i] + (t_attn_in_ff ? 2 * dfx::ffused::B1P_FLOATS : 0);   // ff_fwd's table: scaled like its W1 tiles (PackArgs::b1ps)
       fa.h1 = a.h1, fa.h2 = hout, fa.R = R, fa.B = B, fa.N = N;
       // tile-major rows between the fused kernels (train_ff_fused.h): everything but the stem's output and the head's input
       // (+ h1 itself only as what the backward kernels want of it: the xhat3 fragments and 1 / std, TL_H1_FRAG)

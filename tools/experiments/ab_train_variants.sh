@@ -2,6 +2,8 @@
 # Same-box A/B of training-kernel variants (GPU box): every arm = a rebuild of csrc/train_kernels.hip (+ dfx_common.hip) with extra -D flags, then
 # tools/prof_train_kernels.sh (rocprofv3 --kernel-trace --stats over tools/bench_train.py: both arms profiled, comparable) and one un-profiled
 # tools/bench_train.py --long for the wall clock.  usage: ab_train_variants.sh out.txt "name:-DFLAG1 -DFLAG2" "name2:" ...   (an empty flag list = the shipped build)
+# The feed-forward kernels' tuning knobs and timing ablations that profiles/r06_ab_train_*.txt were measured with are not part of the shipped kernels:
+# git apply tools/patches/train_ff_knobs_and_ablations.patch first (its header lists every flag, what it builds and the profile it produced).
 R=${GRAFT_REPO_ROOT:-/root/repo}; OUT=$(realpath -m $1); shift
 mkdir -p $(dirname $OUT); : > $OUT
 cd $R
