@@ -133,6 +133,16 @@ SIGNATURES = {
                                 _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dfx_compose_latents": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _I,
                                  _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dfx_flow_reverse_part": (_I, [_P, _I, _P, _I, _P, _I, _P]),
+    "dfx_part_draw_stats": (_I, [_U64, ctypes.c_longlong, ctypes.c_longlong, _I, _I, _P, _P]),
+    "dfx_select_diverse": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "dfx_select_fit": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "dfx_part_search": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _U64, ctypes.c_longlong, _I, _I,
+                             _P, _P, _P, _P, _P, _P, _P]),
+    "dfx_debug_part_draw_normals": (_I, [_U64, ctypes.c_longlong, _I, _I, _I, _P, _P]),
+    "dfx_debug_part_scores_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "dfx_debug_select_diverse_host": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "dfx_debug_select_fit_host": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "dfx_debug_latents_stub": (_I, [ctypes.POINTER(_P), _I, _I, _I, _I]),
     "dfx_aligner_train_workspace_bytes": (_SZ, [_I] * 7),
     "dfx_aligner_train_forward": (_I, [ctypes.POINTER(LatentWeights), _P, _SZ, _P, _P, _P, _P, _P, _I, _P]),

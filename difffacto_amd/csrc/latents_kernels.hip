@@ -19,6 +19,7 @@
 
 #include "dfx_common.h"
 #include "mfma_linear.h"
+#include "part_sampling.h"
 
 namespace {
 
@@ -254,6 +255,30 @@ __global__ void k_finish_mode(const float *__restrict__ valid, const float *__re
   }
 }
 
+// ---- candidate search (dfx_part_search): the token rows of candidate (g, k) from a per-group recipe ----
+//
+// Row (g Kc + k) * J + j = [code of part j of group g | noise[g Kn + k] * noise_scale] for the first Kc <= Kn candidates of every
+// group, where the code is new_code[g] for part new_part (when given) and code_src[amap[g, j]][:, j] otherwise: k_tokens on codes
+// that are never materialised per candidate.  amap is a device copy of a host-validated map.
+__global__ void k_tokens_grouped(const float *__restrict__ code_src, const int32_t *__restrict__ amap, const float *__restrict__ new_code,
+                                 int new_part, const float *__restrict__ noise, float *__restrict__ X, long long rows, int Kc, int Kn,
+                                 int Z, int J, int ND, float noise_scale) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int C = Z + ND;
+  if (t >= rows * J * C) return;
+  const int c = t % C, j = (t / C) % J;
+  const long long r = t / ((long long)C * J), g = r / Kc;
+  if (c >= Z) X[t] = noise[((size_t)g * Kn + r % Kc) * ND + (c - Z)] * noise_scale;
+  else if (new_code && j == new_part) X[t] = new_code[(size_t)g * Z + c];
+  else X[t] = code_src[((size_t)amap[(size_t)g * J + j] * Z + c) * J + j];
+}
+// the key mask of every candidate row: valid (G,J) -> (G K,J)
+__global__ void k_valid_rows(const float *__restrict__ valid, float *__restrict__ out, long long rows, int K, int J) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= rows * J) return;
+  out[t] = valid[(size_t)(t / J / K) * J + t % J];
+}
+
 inline int nblk(long long n, int bs = 256) { return (int)((n + bs - 1) / bs); }
 
 }  // namespace
@@ -286,9 +311,9 @@ namespace {
 template <int EPI>
 void lin(hipStream_t st, int groups, const LinArgs &a) { dfx::lin::launch<EPI>(st, groups, a); }
 
-// SequentialFlow(reverse=True) for all parts at once on X (J, S, Z) (blockIdx.z = part).
-void run_flows(const dfx_latents *h, float *X, float *H1, float *H2, int S, hipStream_t st) {
-  const int Z = h->Z, Hd = h->flow_hidden, d = Z / 2, J = h->J;
+// SequentialFlow(reverse=True) for all parts at once on X (J, S, Z) (blockIdx.z = part); part >= 0: that part's flow alone on X (S, Z).
+void run_flows(const dfx_latents *h, float *X, float *H1, float *H2, int S, hipStream_t st, int part = -1) {
+  const int Z = h->Z, Hd = h->flow_hidden, d = Z / 2, J = part < 0 ? h->J : 1, p0 = part < 0 ? 0 : part;
   const float *W = h->wbuf;
   for (int l = h->flow_depth - 1; l >= 0; --l) {
     const bool swap = (l % 2 == 0);          // flow.py:78
@@ -297,29 +322,27 @@ void run_flows(const dfx_latents *h, float *X, float *H1, float *H2, int S, hipS
     LinArgs a{};
     a.M = S;
     a.X = X + co, a.x_gs = (long long)S * Z, a.ldx = Z, a.K = d;
-    a.W = W + f.w0, a.w_gs = (long long)Hd * d, a.b = W + f.b0, a.b_gs = Hd;
+    a.W = W + f.w0 + (size_t)p0 * Hd * d, a.w_gs = (long long)Hd * d, a.b = W + f.b0 + (size_t)p0 * Hd, a.b_gs = Hd;
     a.Y = H1, a.y_gs = (long long)S * Hd, a.ldy = Hd, a.N = Hd;
     lin<EPI_RELU>(st, J, a);
     a.X = H1, a.x_gs = (long long)S * Hd, a.ldx = Hd, a.K = Hd;
-    a.W = W + f.w1, a.w_gs = (long long)Hd * Hd, a.b = W + f.b1;
+    a.W = W + f.w1 + (size_t)p0 * Hd * Hd, a.w_gs = (long long)Hd * Hd, a.b = W + f.b1 + (size_t)p0 * Hd;
     a.Y = H2;
     lin<EPI_RELU>(st, J, a);
     a.X = H2;
-    a.W = W + f.w2, a.w_gs = (long long)2 * d * Hd, a.b = W + f.b2, a.b_gs = 2 * d;
+    a.W = W + f.w2 + (size_t)p0 * 2 * d * Hd, a.w_gs = (long long)2 * d * Hd, a.b = W + f.b2 + (size_t)p0 * 2 * d, a.b_gs = 2 * d;
     a.Y = X + to, a.y_gs = (long long)S * Z, a.ldy = Z, a.N = d;
     lin<EPI_COUPLING>(st, J, a);
   }
 }
 
-// PartAlignerTransformer on B shapes; code (B,Z,J), valid (B,J), noise (B,nd) device pointers.  ws layout is
-// carved by the caller.  Writes mean / logvar / params (any may be null).
-int run_aligner(dfx_latents *h, const float *code, const float *valid, const float *noise, float *mean,
-                float *logvar, float *params, int B, float *ws, hipStream_t st) {
+// PartAlignerTransformer on B shapes whose token rows (B J, in_ch) are at the start of ws; valid (B,J) device pointer.  ws layout
+// is carved by the caller.  Writes mean / logvar / params (any may be null).
+int run_aligner_tokens(dfx_latents *h, const float *valid, float *mean, float *logvar, float *params, int B, float *ws, hipStream_t st) {
   const int J = h->J, M = B * J, C = h->inner, IC = h->in_ch;
   float *X0 = ws, *X = X0 + (size_t)M * IC, *Xn = X + (size_t)M * C, *QKV = Xn + (size_t)M * C,
         *O = QKV + (size_t)M * 3 * C, *G = O + (size_t)M * C, *Ho = G + (size_t)M * 4 * C;
   const float *W = h->wbuf;
-  k_tokens<<<nblk((long long)M * IC), 256, 0, st>>>(code, noise, X0, B, h->Z, J, h->cimle ? h->nd : 0, h->noise_scale);
   LinArgs a{};
   a.M = M;
   a.X = X0, a.ldx = IC, a.K = IC, a.W = W + h->proj_in_w, a.b = W + h->proj_in_b, a.Y = X, a.ldy = C, a.N = C;
@@ -355,6 +378,13 @@ int run_aligner(dfx_latents *h, const float *code, const float *valid, const flo
   lin<EPI_NONE>(st, 1, a);
   k_split<<<nblk((long long)B * 6 * J), 256, 0, st>>>(Ho, mean, logvar, params, B, J, h->lsv);
   return dfx::check_launch("part_aligner");
+}
+
+// The same from code (B,Z,J) and noise (B,nd).
+int run_aligner(dfx_latents *h, const float *code, const float *valid, const float *noise, float *mean,
+                float *logvar, float *params, int B, float *ws, hipStream_t st) {
+  k_tokens<<<nblk((long long)B * h->J * h->in_ch), 256, 0, st>>>(code, noise, ws, B, h->Z, h->J, h->cimle ? h->nd : 0, h->noise_scale);
+  return run_aligner_tokens(h, valid, mean, logvar, params, B, ws, st);
 }
 
 size_t aligner_ws_floats(const dfx_latents *h, int B) {
@@ -607,6 +637,98 @@ int dfx_compose_latents(dfx_latents *h, const float *code_src, int S, const int3
     k_finish_mode<<<nblk((long long)R * npoints), 256, 0, st>>>(valid, mean, logvar, seg_mode, seg_src, seg_row ? smap : nullptr,
                                                                seg, mean_per_point, logvar_per_point, R, J, npoints, h->lsv);
   return dfx::check_launch("compose_latents");
+}
+
+int dfx_flow_reverse_part(dfx_latents *h, int part, const float *w, int scale_prior, float *code, int R, dfx_stream_t stream) {
+  DFX_REQUIRE(h && R >= 0, "flow_reverse_part: bad argument");
+  DFX_REQUIRE(part >= 0 && part < h->J, "flow_reverse_part: part %d outside [0,%d)", part, h->J);
+  if (R == 0) return DFX_OK;
+  DFX_REQUIRE(w && code, "flow_reverse_part: null pointer");
+  DFX_REQUIRE(h->wbuf, "flow_reverse_part: the handle holds no weights");
+  hipStream_t st = dfx::as_stream(stream);
+  const size_t nX = (size_t)R * h->Z, nH = (size_t)R * (h->flow_hidden > 0 ? h->flow_hidden : 1);
+  if (int e = h->reserve(nX + 2 * nH)) return e;
+  float *X = h->ws, *H1 = X + nX, *H2 = H1 + nH;
+  k_flow_in<<<nblk((long long)nX), 256, 0, st>>>(w, X, R, h->Z, 1, scale_prior ? h->prior_std : 1.0f);
+  if (h->flow_depth > 0) run_flows(h, X, H1, H2, R, st, part);
+  k_flow_out<<<nblk((long long)nX), 256, 0, st>>>(X, code, R, h->Z, 1);
+  return dfx::check_launch("flow_reverse_part");
+}
+
+int dfx_part_search(dfx_latents *h, const float *code_src, int S, const int32_t *code_a, const float *new_code, int new_part,
+                    const float *valid, const float *noise, int G, int K, int mode, int P, const float *target_mean,
+                    const float *target_logvar, const float *weight, const float *stats, uint64_t seed, long long row0, int n_draws,
+                    int row_budget, int32_t *idx, float *noise_sel, float *mean_sel, float *logvar_sel, float *scores, int32_t *n_bad,
+                    dfx_stream_t stream) {
+  // every check runs on the host before the first HIP call (code_a is a host array)
+  DFX_REQUIRE(h, "part_search: null handle");
+  const int J = h->J, Z = h->Z;
+  if (int rc = dfx::psel::check_shape("part_search", G, K, J)) return rc;
+  DFX_REQUIRE(h->cimle, "part_search: the aligner was built without cimle: there are no candidates to search");
+  DFX_REQUIRE(mode >= DFX_SEARCH_FIT && mode <= DFX_SEARCH_DIVERSE, "part_search: mode %d not in {0 fit, 1 first, 2 diverse}", mode);
+  DFX_REQUIRE(P >= 1 && P <= K, "part_search: P = %d outside [1,K = %d]", P, K);
+  DFX_REQUIRE(mode != DFX_SEARCH_FIT || P == 1, "part_search: the fit selection picks one candidate (P = %d)", P);
+  DFX_REQUIRE(S >= 1 && code_src && code_a, "part_search: code_src / code_a required (S = %d)", S);
+  DFX_REQUIRE(valid && noise && idx && noise_sel && mean_sel && logvar_sel && n_bad, "part_search: null pointer");
+  DFX_REQUIRE(new_part >= -1 && new_part < J, "part_search: new_part %d outside [-1,%d)", new_part, J);
+  DFX_REQUIRE((new_code != nullptr) == (new_part >= 0), "part_search: new_code and new_part are given together");
+  DFX_REQUIRE(mode != DFX_SEARCH_FIT || (target_mean && target_logvar && weight), "part_search: the fit selection needs targets and weights");
+  DFX_REQUIRE(row_budget == 0 || row_budget >= K, "part_search: row_budget %d below one group of K = %d rows", row_budget, K);
+  if (mode == DFX_SEARCH_DIVERSE && !stats) {   // the draws of dfx_part_draw_stats, per chunk into the workspace
+    DFX_REQUIRE(row0 >= 0, "part_search: row0 = %lld is negative", row0);
+    DFX_REQUIRE(n_draws >= 4 && n_draws % 4 == 0 && n_draws <= dfx::psel::MAX_DRAWS, "part_search: n_draws = %d must be a multiple of 4 in [4,%d]",
+                n_draws, dfx::psel::MAX_DRAWS);
+  }
+  for (long long i = 0; i < (long long)G * J; ++i)
+    DFX_REQUIRE(code_a[i] >= 0 && code_a[i] < S, "part_search: code_a[%lld] = %d outside [0,%d)", i, code_a[i], S);
+  DFX_REQUIRE(h->wbuf, "part_search: the handle holds no weights");
+
+  hipStream_t st = dfx::as_stream(stream);
+  const int ND = h->nd;
+  // FIRST reads candidates 0 .. P-1 only: the aligner runs on those (Kc rows per group), not on all K
+  const int Kc = mode == DFX_SEARCH_FIRST ? P : K;
+  const bool draw = mode == DFX_SEARCH_DIVERSE && !stats;
+  const int budget = row_budget == 0 ? (DFX_SEARCH_DEFAULT_ROWS >= K ? DFX_SEARCH_DEFAULT_ROWS : K) : row_budget;
+  const int gc0 = budget / Kc < G ? budget / Kc : G;
+  const size_t rows0 = (size_t)gc0 * Kc;
+  auto pad = [](size_t n) { return (n + 3) & ~(size_t)3; };
+  const size_t n_map = pad((size_t)G * J), n_valid = pad(rows0 * J), n_par = pad(rows0 * 3 * J),
+               n_sc = mode == DFX_SEARCH_DIVERSE && !scores ? pad(rows0 * 6 * J) : 0, n_st = draw ? pad(rows0 * 12 * J) : 0;
+  if (int e = h->reserve(n_map + n_valid + 2 * n_par + n_sc + n_st + aligner_ws_floats(h, (int)rows0))) return e;
+  int32_t *amap = reinterpret_cast<int32_t *>(h->ws);
+  float *validr = h->ws + n_map, *mean_c = validr + n_valid, *logvar_c = mean_c + n_par, *sc_c = logvar_c + n_par, *st_c = sc_c + n_sc,
+        *al = st_c + n_st;
+  // pageable host -> device: the call returns once the host array is staged
+  DFX_HIP_TRY(hipMemcpyAsync(amap, code_a, (size_t)G * J * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  DFX_HIP_TRY(hipMemsetAsync(n_bad, 0, sizeof(int32_t), st));
+  for (int g0 = 0; g0 < G; g0 += gc0) {
+    const int gc = G - g0 < gc0 ? G - g0 : gc0;
+    const long long rows = (long long)gc * Kc;
+    const size_t r0 = (size_t)g0 * K;   // the chunk's first candidate row (of K per group)
+    k_tokens_grouped<<<nblk(rows * J * h->in_ch), 256, 0, st>>>(code_src, amap + (size_t)g0 * J, new_code ? new_code + (size_t)g0 * Z : nullptr,
+                                                               new_part, noise + r0 * ND, al, rows, Kc, K, Z, J, ND, h->noise_scale);
+    k_valid_rows<<<nblk(rows * J), 256, 0, st>>>(valid + (size_t)g0 * J, validr, rows, Kc, J);
+    if (int e = run_aligner_tokens(h, validr, mean_c, logvar_c, nullptr, (int)rows, al, st)) return e;
+    int32_t *idx_c = idx + (size_t)g0 * P;
+    if (mode == DFX_SEARCH_DIVERSE) {
+      float *sc = scores ? scores + r0 * 6 * J : sc_c;
+      const float *stp = stats ? stats + r0 * 12 * J : st_c;
+      if (draw)
+        if (int e = dfx::psel::launch_draw_stats(seed, row0 + (long long)r0, rows, J, n_draws, st_c, st)) return e;
+      if (int e = dfx::psel::launch_scores(mean_c, logvar_c, valid + (size_t)g0 * J, stp, gc, K, J, sc, st)) return e;
+      if (int e = dfx::psel::launch_diverse(sc, valid + (size_t)g0 * J, gc, K, J, P, idx_c, n_bad, st)) return e;
+    } else if (mode == DFX_SEARCH_FIT) {
+      if (int e = dfx::psel::launch_fit(mean_c, logvar_c, target_mean + (size_t)g0 * 3 * J, target_logvar + (size_t)g0 * 3 * J,
+                                        weight + (size_t)g0 * J, gc, K, J, idx_c, scores ? scores + r0 : nullptr, n_bad, st))
+        return e;
+    } else {
+      if (int e = dfx::psel::launch_first(gc, P, idx_c, st)) return e;
+    }
+    if (int e = dfx::psel::launch_gather(idx_c, noise + r0 * ND, mean_c, logvar_c, gc, K, Kc, P, ND, J, noise_sel + (size_t)g0 * P * ND,
+                                         mean_sel + (size_t)g0 * P * 3 * J, logvar_sel + (size_t)g0 * P * 3 * J, st))
+      return e;
+  }
+  return DFX_OK;
 }
 
 // A handle with the sizes of a real one and no device memory: lets the argument checks of dfx_compose_latents run on a

@@ -18,6 +18,13 @@ problem, all of them optimized by ONE ``dfx_noise_opt_run`` call, then one ``dfx
     out = reconfigure_part(encoder, diffusion, codes, ref_mean, ref_var, edit_part=0, new_var=v, fix_parts=[0, 1, 1, 1])
     out = invert_noise(encoder, codes, ref_mean, ref_var)                           # the noise that reproduces a configuration
 
+Part-level sampling (the reference's tools/run_sample_one_part.py: AnchorDiffAE.sample_one_part, anchor_gen.py:307-337) is
+``sample_part``: new styles for one part of every shape, a search over K aligner noises per style for configurations in which the
+other parts stay where they were (or for the first / the most diverse configurations), ONE ``dfx_part_search`` call for all shapes,
+one ``dfx_compose_latents`` for the picked rows and one chain launch.
+
+    out = sample_part(encoder, diffusion, codes, valid_id, ref_mean, ref_logvar, part_id=1, how_many_each=50)
+
 The recipe builders below are host-side index bookkeeping (no GPU): rows are ``r = b * K + k`` like the reference's
 ``repeat_interleave(K, dim=0)``.
 """
@@ -174,6 +181,103 @@ def drift_anchors(encoder, diffusion, codes, scale, parts=(0, 2), axis=1, valid_
                                           mean_scale=s.to(device), logvar_shift=l.to(device), **seg_kw)
     return {"pred": pred.reshape(B, K, npoints, 3), "seg_mask": seg.reshape(B, K, npoints),
             "anchors": mean_pp.transpose(1, 2).reshape(B, K, npoints, 3)}
+
+
+# ---------------------------------------------------------------------------------------------------- part-level sampling
+def part_sampling_recipe(S, E, P, n_class, part_id):
+    """Rows r = (s*E + e)*P + p of the final ``dfx_compose_latents`` call over the source rows [the S shapes | the S*E new styles]:
+    every part from shape s except ``part_id``, which is new style s*E + e.  -> code_a (S*E*P, n_class), shape_row (S*E*P,)."""
+    group = np.repeat(np.arange(S * E, dtype=np.int32), P)
+    shape_row = (group // E).astype(np.int32)
+    code_a = np.repeat(shape_row[:, None], n_class, axis=1)
+    code_a[:, part_id] = S + group
+    return code_a, shape_row
+
+
+def sample_part_latents(encoder, codes, valid_id, ref_mean, ref_logvar, part_id, how_many_each, fix_size=True, param_sample_num=1,
+                        selective=False, K=100, seg_mask=None, npoints=2048, noise=None, seed=None, generator=None, row_budget=0):
+    """``sample_part`` up to the chain: the draws, the new styles, the candidate search and the composed rows.  Returns
+    (``encoder.compose_latents``' 6-tuple, search dict with idx (S,E,P), scores, n_bad, P)."""
+    from .encoders import _unsupported
+    al = encoder.part_aligner
+    if al is None or not al.cimle:
+        _unsupported("part-level sampling without a cIMLE part aligner (there are no candidate noises to search)")
+    device, codes, valid_id = _setup(encoder, codes, valid_id)
+    S, J, E, K = codes.shape[0], encoder.n_class, int(how_many_each), int(K)
+    if not 0 <= int(part_id) < J:
+        raise ValueError(f"sample_part: part_id {part_id} outside [0, {J})")
+    if fix_size:                                                          # part_encoders.py:661-663
+        param_sample_num, selective = 1, False
+    P = int(param_sample_num)
+    if not 1 <= P <= K:
+        raise ValueError(f"sample_part: param_sample_num {P} outside [1, K = {K}]")
+    if noise is None:                                                     # the reference's order: w (:655), then per shape (:669)
+        w = torch.randn(S * E, encoder.zdim, generator=generator)
+        z = torch.cat([torch.randn(E * K, al.noise_dim, generator=generator) for _ in range(S)])
+    else:
+        w, z = noise
+    w, z = w.to(device=device, dtype=torch.float32), z.to(device=device, dtype=torch.float32)
+    sampler = encoder.sampler()
+    new_code = sampler.flow_reverse_part(part_id, w, scale_prior=False) if encoder.use_flow else w.contiguous()      # :656-659
+    G = S * E
+    group_shape = repeat_rows(S, E)
+    valid_g = valid_id.repeat_interleave(E, 0)
+    kw = {}
+    if fix_size:
+        mode = "fit"
+        f32 = lambda t: torch.as_tensor(t).to(device=device, dtype=torch.float32).reshape(S, 3, J).repeat_interleave(E, 0)
+        weight = valid_g.clone()
+        weight[:, part_id] = 0.0                                          # :680
+        kw = {"target_mean": f32(ref_mean), "target_logvar": f32(ref_logvar), "weight": weight}
+    elif selective:
+        mode = "diverse"
+        kw = {"seed": int(seed) if seed is not None else int(torch.randint(0, 2 ** 62, (), generator=generator))}
+    else:
+        mode = "first"
+    found = sampler.part_search(codes, np.repeat(group_shape[:, None], J, 1), valid_g, z, K, mode, P=P, new_code=new_code,
+                                new_part=int(part_id), row_budget=row_budget, return_scores=True, **kw)
+    # the S*E*P final rows: the new styles as extra source rows, the picked noises as noise_src, the shapes' own segmentation
+    extra = codes.new_zeros(G, encoder.zdim, J)
+    extra[:, :, part_id] = new_code
+    code_a, shape_row = part_sampling_recipe(S, E, P, J, int(part_id))
+    seg_kw = {} if seg_mask is None else {"seg_mode": 2, "seg_src": seg_mask, "seg_row": shape_row}
+    lat = encoder.compose_latents(torch.cat([codes, extra]), code_a, valid_g.repeat_interleave(P, 0), npoints, noise_src=found["noise"],
+                                  **seg_kw)
+    found["idx"] = found["idx"].reshape(S, E, P)
+    return lat, found, P
+
+
+@torch.no_grad()
+def sample_part(encoder, diffusion, codes, valid_id, ref_mean, ref_logvar, part_id, how_many_each, fix_size=True, param_sample_num=1,
+                selective=False, K=100, seg_mask=None, npoints=2048, noise=None, seed=None, generator=None, row_budget=0):
+    """Keep every shape of ``codes`` (S,zdim,J), draw ``how_many_each`` = E new styles for part ``part_id`` and let the aligner find
+    configurations for them among K noises per style (AnchorDiffAE.sample_one_part, anchor_gen.py:307-337;
+    PartEncoder.sample_with_fixed_latents, part_encoders.py:623-710):
+
+    * ``fix_size=True`` (P = 1): the noise whose parameters of the OTHER present parts are closest to the shape's own ``ref_mean`` /
+      ``ref_logvar`` (S,3,J): the untouched parts stay where they were (:677-682);
+    * ``fix_size=False``: P = ``param_sample_num`` configurations per style: the first P noises, or with ``selective`` the P most
+      diverse ones by the greedy rule of ``subsample_params`` (:545-589; its 512 unit draws per candidate come from Philox keyed by
+      ``seed``, or by a key drawn from ``generator``).
+
+    Deviations from the reference's letter: K is a parameter (hard-coded 100 at :664); the two ``fix_size=False`` branches raise in
+    the reference (a boolean mask / a Python list where ``gather_operation`` needs indices, :685-690) and follow their evident intent
+    here, the selective one with each shape's own validity mask (the reference passes column 0 of the batch's).
+
+    The host draws come in the reference's order (w (S*E,zdim), then (E*K,noise_dim) per shape), so one ``torch.manual_seed``
+    reproduces its latents; ``noise`` = (w, z (S*E*K,noise_dim)) supplies them instead.  ``seg_mask`` (S,npoints) ids: the shapes' own
+    segmentation (default: npoints // J points per present part).  ``row_budget``: candidate rows the aligner sees at once (0 = the
+    library's default).  Returns the keys of ``LatentSampler.sample_latents`` over the S*E*P rows r = (s*E + e)*P + p, and 'pred'
+    (S,E,P,npoints,3), 'idx' (S,E,P) the picked noise of every row, 'scores' ((S*E,K) fit sums / (S*E*K,6,J) diverse scores / None),
+    'n_bad' (candidates with a non-finite score)."""
+    lat, found, P = sample_part_latents(encoder, codes, valid_id, ref_mean, ref_logvar, part_id, how_many_each, fix_size, param_sample_num,
+                                        selective, K, seg_mask, npoints, noise, seed, generator, row_budget)
+    ctx, mean_pp, logvar_pp, seg, valid, (part_code, mean, logvar, z) = lat
+    pred = decode(diffusion, ctx, seg, valid_id=valid, seed=seed, generator=generator)["pred"]
+    S, E = found["idx"].shape[:2]
+    return {"part_code": part_code, "valid_id": valid, "noise": z, "mean": mean, "logvar": logvar, "params": ctx[1], "seg_mask": seg,
+            "mean_per_point": mean_pp, "logvar_per_point": logvar_pp, "pred": pred.reshape(S, E, P, npoints, 3), "idx": found["idx"],
+            "scores": found["scores"], "n_bad": found["n_bad"]}
 
 
 # ---------------------------------------------------------------------------------------------------- aligner-noise optimization

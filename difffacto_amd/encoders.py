@@ -557,6 +557,24 @@ class PartEncoderForTransformerDecoder(nn.Module):
         return (ctx, out["mean_per_point"], out["logvar_per_point"], out["seg_mask"], out["valid_id"],
                 [out["part_code"], out["mean"], out["logvar"], out["noise"]])
 
+    @torch.no_grad()
+    def sample_with_fixed_latents(self, codes, valid_id, gt_mean, gt_logvar, seg_mask, sample_part_id, how_many_each, fix_size,
+                                  param_sample_num, selective_param_sample, K=100):
+        """part_encoders.py:623-710: new styles for part ``sample_part_id`` of every shape and, per style, the aligner noise(s) picked
+        among K (``editing.sample_part_latents``: one candidate search and one compose call).  ``fix_size`` forces
+        param_sample_num = 1 and no selective sampling (:661-663).  Returns the reference's 6-tuple (ctx, mean_per_point,
+        logvar_per_point, seg_mask, valid_id, [codes, noises, means, logvars]) over how_many * how_many_each * param_sample_num
+        rows; like the reference's, logvar_per_point is gathered WITHOUT log_scale_var (:707) while ctx carries it (:708).
+        Deviations: K is a parameter (100 at :664); the fix_size=False branches raise in the reference and follow their intent
+        here (``editing.sample_part``)."""
+        from . import editing
+        S, N = seg_mask.shape
+        lat, found, P = editing.sample_part_latents(self, codes, valid_id, gt_mean, gt_logvar, sample_part_id, how_many_each, fix_size,
+                                                    param_sample_num, selective_param_sample, K, seg_mask, N)
+        ctx, mean_pp, logvar_pp, _seg, valid, (part_code, mean, logvar, noise) = lat
+        seg = seg_mask.to(mean_pp.device).reshape(S, 1, N).expand(-1, int(how_many_each) * P, -1).reshape(-1, N)        # :706
+        return ctx, mean_pp, logvar_pp - self.log_scale_var, seg, valid, [part_code, noise, mean, logvar]
+
 
 @torch.no_grad()
 def generate(encoder, diffusion, sample_num, npoints, valid_id=None, fixed_id=None, K=10, epoch=0, seed=None,

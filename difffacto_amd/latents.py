@@ -204,6 +204,55 @@ class LatentSampler:
         _ffi.check(rc, "dfx_compose_latents")
         return out
 
+    def flow_reverse_part(self, part, w, scale_prior=True):
+        """flow[part](w, reverse=True) (part_encoders.py:655-659): w (R,zdim) standard normal -> (R,zdim) codes of that part.
+        ``scale_prior``: scale w by sqrt(prior_var) first, as ``flow_reverse`` does (the reference's :655 does not)."""
+        w = self._f(w)
+        R = w.shape[0]
+        assert tuple(w.shape) == (R, self.zdim)
+        out = torch.empty_like(w)
+        with torch.cuda.device(self.device):
+            rc = _ffi.lib().dfx_flow_reverse_part(self._h, int(part), _ffi.ptr(w), int(bool(scale_prior)), _ffi.ptr(out), R,
+                                                  _ffi.current_stream())
+        _ffi.check(rc, "dfx_flow_reverse_part")
+        return out
+
+    def part_search(self, code_src, code_a, valid, noise, K, mode, P=1, new_code=None, new_part=-1, target_mean=None,
+                    target_logvar=None, weight=None, stats=None, seed=0, row0=0, n_draws=512, row_budget=0, return_scores=False):
+        """``dfx_part_search``: for G groups of K aligner noises each, the aligner over chunks of whole groups of at most ``row_budget``
+        candidate rows (0 = the library's default), the selection ``mode`` ('fit' / 'first' / 'diverse') and the P picks per group.
+
+        code_src (S,zdim,J) + code_a (G,J) host ints: the source row of every part of a group; new_code (G,zdim) replaces part
+        ``new_part``; valid (G,J); noise (G K,noise_dim); fit: target_mean / target_logvar (G,3,J), weight (G,J); diverse: stats
+        (G K,4,3,J) or None (Philox from ``seed``, global rows from ``row0``).  Returns dict: idx (G,P) int32, noise (G P,noise_dim),
+        mean / logvar (G P,3,J), scores ((G K,6,J) diverse, (G,K) fit; None unless ``return_scores``), n_bad (1,) int32."""
+        from . import part_sampling
+        mode = part_sampling.MODES[mode] if isinstance(mode, str) else int(mode)
+        code_a = np.ascontiguousarray((code_a.detach().cpu().numpy() if isinstance(code_a, torch.Tensor) else np.asarray(code_a)).astype(np.int32))
+        code_src, valid, noise, new_code, target_mean, target_logvar, weight, stats = map(
+            self._f, (code_src, valid, noise, new_code, target_mean, target_logvar, weight, stats))
+        J, Z, ND = self.n_class, self.zdim, self.noise_dim
+        S, G, K, P = code_src.shape[0], code_a.shape[0], int(K), int(P)
+        assert tuple(code_src.shape) == (S, Z, J) and code_a.shape == (G, J) and tuple(valid.shape) == (G, J)
+        assert tuple(noise.shape) == (G * K, ND)
+        assert new_code is None or tuple(new_code.shape) == (G, Z)
+        for t, shape in ((target_mean, (G, 3, J)), (target_logvar, (G, 3, J)), (weight, (G, J)), (stats, (G * K, 4, 3, J))):
+            assert t is None or tuple(t.shape) == shape
+        e = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=self.device)
+        scores = None
+        if return_scores and mode != part_sampling.MODES["first"]:
+            scores = e(G * K, 6, J) if mode == part_sampling.MODES["diverse"] else e(G, K)
+        out = {"idx": e(G, P, dtype=torch.int32), "noise": e(G * P, ND), "mean": e(G * P, 3, J), "logvar": e(G * P, 3, J), "scores": scores,
+               "n_bad": e(1, dtype=torch.int32)}
+        with torch.cuda.device(self.device):
+            rc = _ffi.lib().dfx_part_search(
+                self._h, _ffi.ptr(code_src), S, code_a.ctypes.data_as(ctypes.c_void_p), _ffi.ptr(new_code), int(new_part), _ffi.ptr(valid),
+                _ffi.ptr(noise), G, K, mode, P, _ffi.ptr(target_mean), _ffi.ptr(target_logvar), _ffi.ptr(weight), _ffi.ptr(stats), int(seed),
+                int(row0), int(n_draws), int(row_budget), _ffi.ptr(out["idx"]), _ffi.ptr(out["noise"]), _ffi.ptr(out["mean"]),
+                _ffi.ptr(out["logvar"]), _ffi.ptr(scores), _ffi.ptr(out["n_bad"]), _ffi.current_stream())
+        _ffi.check(rc, "dfx_part_search")
+        return out
+
     def optimize_noise(self, part_code, valid, z0, problem, max_iter, trace=False):
         """``dfx_noise_opt_run``: R independent gradient descents on the aligner noise (tools/shape_edit.py:80-129 per row), enqueued
         without host round trips.  part_code (R,zdim,J), valid (R,J), z0 (R,noise_dim); ``problem``: dict with the (R,3,J) targets

@@ -114,6 +114,22 @@ class AnchorDiffAE(nn.Module):
                                ret_interval=self.ret_interval, seed=seed, generator=generator, x_T_noise=x_T_noise,
                                step_noise=step_noise, save_pred_xstart=self.save_pred_xstart, x_T=noise)
 
+    @torch.no_grad()
+    def sample_one_part(self, code, valid_id, mean, logvar, seg_mask, part_id, sample_num_each, fix_size, param_sample_num,
+                        selective_param_sample, K=100):
+        """anchor_gen.py:307-337 (tools/run_sample_one_part.py): new styles for one part of every shape, decoded.  Returns the
+        reference's 7-tuple (pred (bs,E,P,np,3), seg_mask (bs,E,P,np), valid_id (bs,E,P,J), codes (bs,E,P,zdim,J), noise_latents
+        (bs*E*P,noise_dim), means, logvars (bs,E,P,3,J)); P = 1 under ``fix_size`` whatever ``param_sample_num`` says.  K and the
+        repaired fix_size=False branches: ``PartEncoderForTransformerDecoder.sample_with_fixed_latents``."""
+        bs, n = code.shape[0], seg_mask.shape[1]
+        ctx, mean_pp, logvar_pp, seg, valid, (codes, noises, means, logvars) = self.encoder.sample_with_fixed_latents(
+            code, valid_id, mean, logvar, seg_mask, part_id, sample_num_each, fix_size, param_sample_num, selective_param_sample, K=K)
+        E, P = int(sample_num_each), codes.shape[0] // (bs * int(sample_num_each))
+        pred = self.decode(mean_pp, ctx=ctx, variance=torch.exp(logvar_pp), anchor_assignments=seg.to(torch.int32), valid_id=valid)["pred"]
+        J, Z = self.num_anchors, self.encoder.zdim
+        return (pred.reshape(bs, E, P, n, 3), seg.reshape(bs, E, P, n), valid.reshape(bs, E, P, J), codes.reshape(bs, E, P, Z, J), noises,
+                means.reshape(bs, E, P, 3, J), logvars.reshape(bs, E, P, 3, J))
+
     def sample(self, sample_num, fixed_id, valid_id, device, epoch, K=10):
         """anchor_gen.py:798-801 (K is ignored there as well: cimle_sample_num rows per shape)."""
         return self.encoder.sample_latents(sample_num, self.npoints, device, fixed_id=torch.as_tensor(fixed_id).to(device),

@@ -12,6 +12,12 @@ Writes interpolate.npy (shapes, steps, N, 3), mix.npy (shapes, 1, N, 3), drift.n
 re-configures instead: part --part of every shape is made 1.2 / 1.5 times larger along z (two candidate edits) and the other parts re-arrange
 themselves, by gradient descent on the aligner noise from --starts random starts per edit; all shapes x edits x starts rows are ONE
 dfx_noise_opt_run call and one chain launch (editing.reconfigure_part).  Writes reconfigure.npy (shapes, edits, N, 3): the best start per edit.
+
+    python examples/edit.py --resample-part 1 --each 5 [--free-size --params 3 [--selective]] [--candidates 100]
+
+samples new styles instead (the reference's tools/run_sample_one_part.py): --each new styles of part --resample-part per shape; among --candidates
+aligner noises per style the one that keeps the other parts where they were, or with --free-size the first / the --params most diverse ones
+(--selective); one dfx_part_search call for all shapes, one chain launch (editing.sample_part).  Writes resample.npy (shapes, each, params, N, 3).
 """
 import argparse
 import os
@@ -40,6 +46,12 @@ def main():
     ap.add_argument("--reconfigure", action="store_true", help="edit the size of --part and let the other parts re-arrange (noise optimization)")
     ap.add_argument("--starts", type=int, default=3, help="--reconfigure: random noise starts per candidate edit")
     ap.add_argument("--max-iter", type=int, default=300, help="--reconfigure: iterations of the noise optimization")
+    ap.add_argument("--resample-part", type=int, default=None, help="sample new styles of this part, the other parts kept")
+    ap.add_argument("--each", type=int, default=5, help="--resample-part: new styles per shape")
+    ap.add_argument("--free-size", action="store_true", help="--resample-part: do not fit the other parts to where they were")
+    ap.add_argument("--params", type=int, default=1, help="--resample-part --free-size: configurations per new style")
+    ap.add_argument("--selective", action="store_true", help="--resample-part --free-size: the most diverse configurations instead of the first")
+    ap.add_argument("--candidates", type=int, default=100, help="--resample-part: aligner noises searched per new style")
     a = ap.parse_args()
 
     enc, diff = build(a.config, a.timesteps, a.precision, 0)
@@ -59,6 +71,19 @@ def main():
     g = torch.Generator().manual_seed(a.seed)
     codes = enc.sampler().flow_reverse(torch.randn(B, enc.zdim, enc.n_class, generator=g).cuda())   # part codes from the flow prior
     os.makedirs(a.out_dir, exist_ok=True)
+    if a.resample_part is not None:
+        # the shapes' own configuration: the aligner's parameters under one noise draw per shape
+        valid = torch.ones(B, enc.n_class)
+        mean, logvar = enc.sampler().part_aligner(codes, valid, torch.randn(B, enc.part_aligner.noise_dim, generator=g))
+        out = editing.sample_part(enc, diff, codes, valid, mean, logvar, a.resample_part, a.each, fix_size=not a.free_size,
+                                  param_sample_num=a.params, selective=a.selective, K=a.candidates, npoints=N, seed=a.seed, generator=g)
+        pred = out["pred"]
+        np.save(os.path.join(a.out_dir, "resample.npy"), pred.cpu().numpy())
+        np.save(os.path.join(a.out_dir, "resample_seg.npy"), out["seg_mask"].reshape(*pred.shape[:3], N).cpu().numpy())
+        print(f"resample part {a.resample_part}: {B * a.each * a.candidates} candidate rows in one search call, picked noises {out['idx'].reshape(B, -1)[0].tolist()} "
+              f"(shape 0), non-finite candidates {int(out['n_bad'])}, clouds {tuple(pred.shape)}, finite: {bool(torch.isfinite(pred).all())} "
+              f"-> {a.out_dir}/resample.npy")
+        return
     if a.reconfigure:
         # the shapes' own configuration: the aligner's parameters under one noise draw per shape
         valid = torch.ones(B, enc.n_class)

@@ -436,6 +436,67 @@ int dfx_compose_latents(dfx_latents *h, const float *code_src, int S, const int3
                         float *logvar, float *params, int32_t *seg, float *mean_per_point, float *logvar_per_point,
                         dfx_stream_t stream);
 
+/* ---- Part-level sampling (AnchorDiffAE.sample_one_part, anchor_gen.py:307-337; PartEncoder.sample_with_fixed_latents,
+ * part_encoders.py:623-710; subsample_params :545-589): new styles for one part, and a search over K aligner noises
+ * per style for configurations to go with them.  Candidate row g K + k is candidate k of group g; all data pointers are device
+ * pointers; n_bad (one int32, device) counts the candidates whose score is not finite: such a candidate is never picked while a
+ * finite one remains. ---- */
+
+/* flow[part](w, reverse=True) (part_encoders.py:655-659): w (R,zdim) standard normal -> code (R,zdim), the flow of that part alone.
+ * scale_prior != 0: w is scaled by sqrt(prior_var) first, which gives column `part` of dfx_flow_reverse; 0: w as it is (the
+ * reference's :655 does not scale; the same at the shipped prior_var = 1). */
+int dfx_flow_reverse_part(dfx_latents *h, int part, const float *w, int scale_prior, float *code, int R, dfx_stream_t stream);
+
+/* Statistics of the unit draws of subsample_params :555 without storing them: for the global candidate rows row0 .. row0+rows-1,
+ * n_draws (a multiple of 4; the reference draws 512) standard normals per (axis, part) from Philox keyed by (seed, global row,
+ * axis, part, draw), reduced in draw order in fp64 to stats (rows,4,3,n_class) = mean, unbiased std, min, max.  A call split over
+ * row0 gives the same numbers. */
+int dfx_part_draw_stats(uint64_t seed, long long row0, long long rows, int n_class, int n_draws, float *stats, dfx_stream_t stream);
+
+/* Greedy diverse selection (subsample_params): mean, logvar (G K,3,n_class), valid (G,n_class) {0,1} floats.
+ *   scores (G K,6,n_class), an output: the reference's param_score in closed form, fp64 rounded once.  With sigma = exp(logvar / 2)
+ *     and the draw statistics (ubar, ustd, umin, umax): hi_c = max over valid j of mu + sigma umax, lo_c = min of mu + sigma umin,
+ *     shift_c = (hi_c + lo_c) / 2, scale = max_c (hi_c - lo_c) / 2, scores[:3] = (mu + sigma ubar - shift) / scale,
+ *     scores[3:] = 2 log(sigma ustd / scale).
+ *   stats (G K,4,3,n_class) as dfx_part_draw_stats writes them (or the statistics of draws of the caller's own).
+ *   idx (G,P) int32, 1 <= P <= K <= 4096: the group's lowest finite candidate (candidate 0 in the reference), then repeatedly the
+ *     unselected candidate whose smallest distance to the selected ones is largest, distance = sum over c < 6 and valid j of
+ *     (s_i - s_k)^2 / sum(valid), fp64 in (c, j) order; of equal ones the lowest index (torch.argmax).  A group without any valid
+ *     part has nothing to compare: every distance is 0 and the picks are 0 .. P-1. */
+int dfx_select_diverse(const float *mean, const float *logvar, const float *valid, const float *stats, int G, int K, int n_class, int P,
+                       int32_t *idx, float *scores, int32_t *n_bad, dfx_stream_t stream);
+
+/* Fit selection (part_encoders.py:678-682): idx (G) int32 = arg-min over k of sum_j weight[g,j] sum_c [(mean - target_mean)^2 +
+ * (logvar - target_logvar)^2], fp64 in that order, the lowest index of equal ones.  mean, logvar (G K,3,n_class); target_mean,
+ * target_logvar (G,3,n_class); weight (G,n_class) = the validity mask with the resampled part zeroed (a part of weight 0 is not
+ * read); fit (G,K) or NULL: the sums, rounded once. */
+int dfx_select_fit(const float *mean, const float *logvar, const float *target_mean, const float *target_logvar, const float *weight, int G,
+                   int K, int n_class, int32_t *idx, float *fit, int32_t *n_bad, dfx_stream_t stream);
+
+#define DFX_SEARCH_FIT 0     /* dfx_select_fit; P = 1 */
+#define DFX_SEARCH_FIRST 1   /* candidates 0 .. P-1 (the intent of part_encoders.py:687); the aligner runs on those only */
+#define DFX_SEARCH_DIVERSE 2 /* dfx_select_diverse */
+#define DFX_SEARCH_DEFAULT_ROWS 16384
+
+/* The candidate search of sample_with_fixed_latents (:664-695) for G groups (one per shape and new style) of K aligner noises each,
+ * without materialising the G K candidate codes: the aligner runs over chunks of whole groups of at most row_budget candidate rows
+ * (0 = DFX_SEARCH_DEFAULT_ROWS; at least K), each chunk is reduced by the selection, and only the P winners per group are kept.
+ *   the codes of group g: part j from code_src[code_a[g,j]][:, j] (code_src (S,zdim,n_class) device, code_a HOST int32 (G,n_class),
+ *     as dfx_compose_latents), except part new_part, which is new_code[g] (new_code (G,zdim) device; NULL with new_part -1)
+ *   valid (G,n_class): the key mask of every candidate of the group; noise (G K,noise_dim): the aligner noises, an input
+ *   mode DFX_SEARCH_*; target_mean / target_logvar / weight: dfx_select_fit's (FIT only, else NULL);
+ *   stats (G K,4,3,n_class): dfx_select_diverse's, or NULL: dfx_part_draw_stats(seed, row0 + row, n_draws) per chunk (DIVERSE only)
+ *   outputs: idx (G,P) int32; noise_sel (G P,noise_dim), mean_sel / logvar_sel (G P,3,n_class): the picked candidates' rows;
+ *     scores or NULL: (G K,6,n_class) for DIVERSE, (G,K) for FIT.
+ * The result does not depend on row_budget when the fp32 products keep one grouping of their K sums (dfx_debug_lin_split_k(1));
+ * with the automatic grouping the parameters can differ in the last bits between budgets.  Every argument, code_a included, is
+ * checked before the first HIP call. */
+int dfx_part_search(dfx_latents *h, const float *code_src, int S, const int32_t *code_a, const float *new_code, int new_part,
+                    const float *valid, const float *noise, int G, int K, int mode, int P, const float *target_mean,
+                    const float *target_logvar, const float *weight, const float *stats, uint64_t seed, long long row0, int n_draws,
+                    int row_budget, int32_t *idx, float *noise_sel, float *mean_sel, float *logvar_sel, float *scores, int32_t *n_bad,
+                    dfx_stream_t stream);
+
 /* Training forward / backward of the part aligner (stage 2: configs/train_*_stage2.py and gen_*.py with train_aligner; replaces torch autograd through
  * PartAlignerTransformer, part_encoders.py:88-143, for the shipped options: cimle with cond_noise_type 0, class_cond + add_class_cond, single_attn,
  * mask_out_unreferenced_code, dropout 0).  Exact fp32, no atomics (aligner_train.hip).  `w` holds the parameter pointers (flow fields unused), `grads` the

@@ -108,6 +108,17 @@ int dfx_debug_batch_build_host(const float *points, const int32_t *labels, const
                                int part_scale_mode, int clip, double dropout_part, int augment_shift, int augment_scale, float *ref,
                                float *input, int64_t *seg, int64_t *attn_map, float *present, float *dp_present, float *part_shift,
                                float *part_scale, float *shift, float *scale, int32_t *n_bad);
+/* The normals dfx_part_draw_stats reduces, for global rows row0 .. row0+rows-1: normals (rows,n_draws,3,n_class) device. */
+int dfx_debug_part_draw_normals(uint64_t seed, long long row0, int rows, int n_class, int n_draws, float *normals, dfx_stream_t stream);
+/* Host-side runs (no GPU) of the selection routines of csrc/part_sampling.hip, compiled from the kernels' own functions, on HOST
+ * pointers, groups one after the other: the scores of dfx_select_diverse from given stats; its greedy selection on given scores
+ * (G K,6,n_class), with pick_dist (G,P) float64 or NULL = every pick's smallest distance to the picks before it; dfx_select_fit. */
+int dfx_debug_part_scores_host(const float *mean, const float *logvar, const float *valid, const float *stats, int G, int K, int n_class,
+                               float *scores);
+int dfx_debug_select_diverse_host(const float *scores, const float *valid, int G, int K, int n_class, int P, int32_t *idx, double *pick_dist,
+                                  int32_t *n_bad);
+int dfx_debug_select_fit_host(const float *mean, const float *logvar, const float *target_mean, const float *target_logvar,
+                              const float *weight, int G, int K, int n_class, int32_t *idx, float *fit, int32_t *n_bad);
 
 #ifdef __cplusplus
 }
