@@ -139,6 +139,10 @@ SIGNATURES = {
     "dfx_select_fit": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "dfx_part_search": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _U64, ctypes.c_longlong, _I, _I,
                              _P, _P, _P, _P, _P, _P, _P]),
+    "dfx_select_diverse_global_workspace_bytes": (_SZ, [ctypes.c_longlong]),
+    "dfx_select_diverse_global": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
+    "dfx_part_search_global": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _U64, ctypes.c_longlong, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "dfx_debug_select_diverse_global_host": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "dfx_debug_part_draw_normals": (_I, [_U64, ctypes.c_longlong, _I, _I, _I, _P, _P]),
     "dfx_debug_part_scores_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "dfx_debug_select_diverse_host": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
@@ -175,6 +179,7 @@ SIGNATURES = {
     "dfx_debug_last_train_path": (ctypes.c_char_p, []),
     "dfx_debug_train_streams": (None, [_I]),
     "dfx_debug_lin_split_k": (None, [_I]),
+    "dfx_debug_diverse_global_path": (None, [_I]),
     "dfx_debug_bn_fused_stats": (None, [_I]),
     "dfx_debug_stats_merge": (None, [_P, _I, _I, _P]),
     "dfx_debug_rowmap": (None, [_I, _P, _P]),

@@ -731,6 +731,63 @@ int dfx_part_search(dfx_latents *h, const float *code_src, int S, const int32_t 
   return DFX_OK;
 }
 
+int dfx_part_search_global(dfx_latents *h, const float *code_src, int S, const int32_t *code_a, const float *valid, const float *noise,
+                           int G, int K, int P, int rule, const float *stats, uint64_t seed, long long row0, int n_draws, int row_budget,
+                           int32_t *idx, float *noise_sel, float *mean_sel, float *logvar_sel, float *scores, int32_t *n_bad,
+                           dfx_stream_t stream) {
+  // every check runs on the host before the first HIP call (code_a is a host array)
+  DFX_REQUIRE(h, "part_search_global: null handle");
+  const int J = h->J, Z = h->Z;
+  if (int rc = dfx::psel::check_shape_global("part_search_global", G, K, J, P, rule)) return rc;
+  DFX_REQUIRE(h->cimle, "part_search_global: the aligner was built without cimle: there are no candidates to search");
+  DFX_REQUIRE(S >= 1 && code_src && code_a, "part_search_global: code_src / code_a required (S = %d)", S);
+  DFX_REQUIRE(valid && noise && idx && noise_sel && mean_sel && logvar_sel && n_bad, "part_search_global: null pointer");
+  DFX_REQUIRE(row_budget == 0 || row_budget >= K, "part_search_global: row_budget %d below one group of K = %d rows", row_budget, K);
+  if (!stats) {   // the draws of dfx_part_draw_stats, per chunk into the workspace
+    DFX_REQUIRE(row0 >= 0, "part_search_global: row0 = %lld is negative", row0);
+    DFX_REQUIRE(n_draws >= 4 && n_draws % 4 == 0 && n_draws <= dfx::psel::MAX_DRAWS,
+                "part_search_global: n_draws = %d must be a multiple of 4 in [4,%d]", n_draws, dfx::psel::MAX_DRAWS);
+  }
+  for (long long i = 0; i < (long long)G * J; ++i)
+    DFX_REQUIRE(code_a[i] >= 0 && code_a[i] < S, "part_search_global: code_a[%lld] = %d outside [0,%d)", i, code_a[i], S);
+  DFX_REQUIRE(h->wbuf, "part_search_global: the handle holds no weights");
+
+  hipStream_t st = dfx::as_stream(stream);
+  const int ND = h->nd;
+  const size_t R = (size_t)G * K;
+  const int budget = row_budget == 0 ? (DFX_SEARCH_DEFAULT_ROWS >= K ? DFX_SEARCH_DEFAULT_ROWS : K) : row_budget;
+  const int gc0 = budget / K < G ? budget / K : G;
+  const size_t rows0 = (size_t)gc0 * K;
+  auto pad = [](size_t n) { return (n + 3) & ~(size_t)3; };
+  // kept for all R rows: mean, logvar, scores and the selection's state; per chunk: the key masks, the draw statistics, the aligner's buffers
+  const size_t n_state = dfx::psel::diverse_global_state_bytes((long long)R) / sizeof(float), n_map = pad((size_t)G * J), n_par = pad(R * 3 * J),
+               n_sc = scores ? 0 : pad(R * 6 * J), n_valid = pad(rows0 * J), n_st = stats ? 0 : pad(rows0 * 12 * J);
+  if (int e = h->reserve(n_state + n_map + 2 * n_par + n_sc + n_valid + n_st + aligner_ws_floats(h, (int)rows0))) return e;
+  float *state = h->ws;   // first: fp64 inside, and the block is aligned
+  int32_t *amap = reinterpret_cast<int32_t *>(state + n_state);
+  float *mean_all = state + n_state + n_map, *logvar_all = mean_all + n_par, *sc_all = scores ? scores : logvar_all + n_par,
+        *validr = logvar_all + n_par + n_sc, *st_c = validr + n_valid, *al = st_c + n_st;
+  // pageable host -> device: the call returns once the host array is staged
+  DFX_HIP_TRY(hipMemcpyAsync(amap, code_a, (size_t)G * J * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  DFX_HIP_TRY(hipMemsetAsync(n_bad, 0, sizeof(int32_t), st));
+  for (int g0 = 0; g0 < G; g0 += gc0) {
+    const int gc = G - g0 < gc0 ? G - g0 : gc0;
+    const long long rows = (long long)gc * K;
+    const size_t r0 = (size_t)g0 * K;   // the chunk's first candidate row
+    float *mean_c = mean_all + r0 * 3 * J, *logvar_c = logvar_all + r0 * 3 * J;
+    k_tokens_grouped<<<nblk(rows * J * h->in_ch), 256, 0, st>>>(code_src, amap + (size_t)g0 * J, nullptr, -1, noise + r0 * ND, al, rows, K, K, Z,
+                                                               J, ND, h->noise_scale);
+    k_valid_rows<<<nblk(rows * J), 256, 0, st>>>(valid + (size_t)g0 * J, validr, rows, K, J);
+    if (int e = run_aligner_tokens(h, validr, mean_c, logvar_c, nullptr, (int)rows, al, st)) return e;
+    const float *stp = stats ? stats + r0 * 12 * J : st_c;
+    if (!stats)
+      if (int e = dfx::psel::launch_draw_stats(seed, row0 + (long long)r0, rows, J, n_draws, st_c, st)) return e;
+    if (int e = dfx::psel::launch_scores(mean_c, logvar_c, valid + (size_t)g0 * J, stp, gc, K, J, sc_all + r0 * 6 * J, st)) return e;
+  }
+  if (int e = dfx::psel::launch_diverse_global(sc_all, valid, G, K, J, P, rule, idx, n_bad, state, st)) return e;
+  return dfx::psel::launch_gather_rows(idx, noise, mean_all, logvar_all, P, ND, J, noise_sel, mean_sel, logvar_sel, st);
+}
+
 // A handle with the sizes of a real one and no device memory: lets the argument checks of dfx_compose_latents run on a
 // machine without a GPU.  Free it with dfx_latents_destroy.
 int dfx_debug_latents_stub(dfx_latents **out, int n_class, int zdim, int cimle, int noise_dim) {

@@ -8,20 +8,23 @@
 //   fit       arg-min of the masked squared parameter distance to a target (:678-682)
 //
 // Mapping: draws and scores are one thread per (row, axis, part) / per row (fp64 arithmetic, one rounding to fp32); the selections
-// are one 256-thread workgroup per group with the per-candidate state in LDS.  Everything discrete is decided by score_row /
-// diverse_group / fit_group, written once over an execution context: BlockCtx (the kernels) and SerialCtx (the dfx_debug_*_host twins:
+// are one 256-thread workgroup per group with the per-candidate state in LDS; the selection over all rows of a call
+// (dfx_select_diverse_global) is one 512-thread workgroup up to 512 rows and one launch per pick above.  Everything discrete is decided by score_row /
+// diverse_group / diverse_global / fit_group, written once over an execution context: BlockCtx (the kernels) and SerialCtx (the dfx_debug_*_host twins:
 // one "thread", plain loops).  A candidate's distance is an fp64 sum in a fixed (c, j) order inside one thread, so the host twin and the
 // kernel compute the same bits; the reductions across threads only compare.  Compiled with -ffp-contract=off (build.py).
 #include "part_sampling.h"
 #include "dfx_dropout.h"
 
 #include <cmath>
+#include <cstdint>
 #include <vector>
 
 namespace {
 
 using dfx::psel::MAX_DRAWS;
 using dfx::psel::MAX_K;
+using dfx::psel::MAX_GLOBAL_ROWS;
 
 constexpr int NT = 256;
 constexpr int NW = NT / 64;
@@ -49,17 +52,20 @@ struct SerialCtx {
   __host__ __device__ void add(int32_t *p, int v) { *p += v; }
 };
 
-struct BlockCtx {
+// a workgroup of NWV wavefronts
+template <int NWV>
+struct BlockCtxT {
   int tid, nt;
-  Best *red_b;   // NW
-  int *red_i;    // NW
+  Best *red_b;   // NWV
+  int *red_i;    // NWV
   __device__ void sync() { __syncthreads(); }
   __device__ int sum_i(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
     if ((tid & 63) == 0) red_i[tid >> 6] = v;
     __syncthreads();
-    const int r = (red_i[0] + red_i[1]) + (red_i[2] + red_i[3]);
+    int r = 0;
+    for (int w = 0; w < NWV; ++w) r += red_i[w];
     __syncthreads();
     return r;
   }
@@ -73,12 +79,13 @@ struct BlockCtx {
     if ((tid & 63) == 0) red_b[tid >> 6] = b;
     __syncthreads();
     b = red_b[0];
-    for (int w = 1; w < NW; ++w)
+    for (int w = 1; w < NWV; ++w)
       if (better(red_b[w], b)) b = red_b[w];
     __syncthreads();
   }
   __device__ void add(int32_t *p, int v) { atomicAdd(p, v); }
 };
+using BlockCtx = BlockCtxT<NW>;
 
 // ---- scores of one candidate (part_encoders.py:555-560 in closed form) ----
 // mean, logvar (3,J); valid (J); st (4,3,J) = mean, unbiased std, min, max of the candidate's unit draws; out (6,J).
@@ -167,6 +174,92 @@ __host__ __device__ void diverse_group(Ctx &cx, const float *sc, const float *va
       if (pick_dist) pick_dist[p] = b.v;
     }
     last = b.cls == 1 ? b.idx : -1;
+    cx.sync();
+  }
+}
+
+// ---- greedy diverse selection over all rows of a call (subsample_params_global, part_encoders.py:591-621, as intended) ----
+// sc (R,6,J), valid (G,J): the mask of row i is valid[i / K].  Two rows are compared on the parts valid in both:
+//   n(i,s) = sum_j m_i[j] m_s[j],  d(i,s) = sum over c < 6, j valid in both of (s_i - s_s)^2 / n(i,s), fp64 in (c, j) order.
+// A pair without a common part (n = 0; the reference divides 0 by 0 there and its arg-max goes to NaN) puts no constraint on the
+// candidate: it is skipped in the minimum, so a candidate that shares no part with any pick keeps mind = +inf and is picked next.
+// mind (R), state (R) as in diverse_group; a row is finite when it has a valid part and every score on its valid parts is finite.
+// cur (7 J) is staging for the newest pick's scores and mask, written once per step and read by every thread.
+// rule 0 (farthest): mind follows every pick; rule 1 (first pick): mind follows pick 0 only, which is what the reference executes
+// (its out_score is never appended to, :603-619) when all rows share one mask.  A row is never picked twice (the reference can
+// repeat a row once every distance is 0).  pick_dist (P) or null: the winner's mind; 0 for pick 0 and for a non-finite pick.
+// The pieces below are shared by diverse_global (one context runs the whole call: the host twin and the one-workgroup kernel) and
+// k_select_diverse_global_step (one launch per pick).
+
+// a row is finite when it has a valid part and every score on its own valid parts is finite
+__host__ __device__ inline bool global_row_ok(const float *sc, const float *valid, int i, int K, int J) {
+  const float *m = valid + (size_t)(i / K) * J;
+  bool any = false, fin = true;
+  for (int j = 0; j < J; ++j) any = any || m[j] != 0.0f;
+  for (int c = 0; c < 6; ++c)
+    for (int j = 0; j < J; ++j)
+      if (m[j] != 0.0f && !__builtin_isfinite(sc[((size_t)i * 6 + c) * J + j])) fin = false;
+  return any && fin;
+}
+// free finite row i as a candidate of step p; with `fresh`, mind[i] first follows the pick staged in cur (scores, then mask)
+__host__ __device__ inline Best global_candidate(const float *sc, const float *valid, int i, int K, int J, int p, bool fresh, const float *cur,
+                                                 double *mind) {
+  if (fresh) {
+    const float *a = sc + (size_t)i * 6 * J, *m = valid + (size_t)(i / K) * J, *ms = cur + 6 * J;
+    double n = 0.0;
+    for (int j = 0; j < J; ++j) n += (double)(m[j] * ms[j]);
+    if (n != 0.0) {
+      double acc = 0.0;
+      for (int c = 0; c < 6; ++c)
+        for (int j = 0; j < J; ++j) {
+          const float w = m[j] * ms[j];
+          if (w == 0.0f) continue;
+          const double d = (double)a[c * J + j] - (double)cur[c * J + j];
+          acc += (double)w * (d * d);
+        }
+      const double d = acc / n;
+      if (d < mind[i]) mind[i] = d;
+    }
+  }
+  return Best{1, p == 0 ? 0.0 : mind[i], i};
+}
+// does mind follow the pick b of step p?
+__host__ __device__ inline bool global_fresh(const Best &b, int rule, int p) { return b.cls == 1 && (rule == DFX_DIVERSE_FARTHEST || p == 0); }
+// stage pick `row` for the next step
+template <class Ctx>
+__host__ __device__ inline void global_stage(Ctx &cx, const float *sc, const float *valid, int row, int K, int J, float *cur) {
+  for (int t = cx.tid; t < 7 * J; t += cx.nt) cur[t] = t < 6 * J ? sc[(size_t)row * 6 * J + t] : valid[(size_t)(row / K) * J + (t - 6 * J)];
+}
+
+template <class Ctx>
+__host__ __device__ void diverse_global(Ctx &cx, const float *sc, const float *valid, int R, int K, int J, int P, int rule, double *mind,
+                                        unsigned char *state, float *cur, int32_t *idx, double *pick_dist, int32_t *n_bad) {
+  int bad = 0;
+  for (int i = cx.tid; i < R; i += cx.nt) {
+    const bool ok = global_row_ok(sc, valid, i, K, J);
+    state[i] = ok ? 0 : 2;
+    mind[i] = INFINITY;
+    bad += !ok;
+  }
+  cx.sync();
+  bad = cx.sum_i(bad);
+  if (cx.tid == 0 && bad) cx.add(n_bad, bad);
+  bool fresh = false;   // cur holds a finite pick that mind has not seen yet
+  for (int p = 0; p < P; ++p) {
+    Best b{-1, 0.0, -1};
+    for (int i = cx.tid; i < R; i += cx.nt) {
+      const unsigned char s = state[i];
+      if (s == 1 || s == 3) continue;
+      const Best cand = s == 0 ? global_candidate(sc, valid, i, K, J, p, fresh, cur, mind) : Best{0, 0.0, i};
+      if (better(cand, b)) b = cand;
+    }
+    cx.best(b);
+    fresh = global_fresh(b, rule, p);
+    if (cx.tid == 0) {
+      idx[p] = b.idx, state[b.idx] = b.cls == 1 ? 1 : 3;
+      if (pick_dist) pick_dist[p] = b.v;
+    }
+    if (fresh) global_stage(cx, sc, valid, b.idx, K, J, cur);
     cx.sync();
   }
 }
@@ -325,6 +418,94 @@ __global__ void __launch_bounds__(NT) k_gather_picks(const int32_t *__restrict__
   }
 }
 
+// One workgroup for the whole call, for at most GLOBAL_ONE_WG_ROWS rows (one per thread): no launch between picks, per-row state
+// (mind fp64, one state byte) in LDS.
+constexpr int GLOBAL_ONE_WG_ROWS = 512;
+constexpr int GNT = GLOBAL_ONE_WG_ROWS;
+constexpr int GNW = GNT / 64;
+__global__ void __launch_bounds__(GNT) k_select_diverse_global(const float *__restrict__ scores, const float *__restrict__ valid, int R, int K,
+                                                               int J, int P, int rule, int32_t *__restrict__ idx, int32_t *__restrict__ n_bad) {
+  __shared__ double mind[GLOBAL_ONE_WG_ROWS];
+  __shared__ unsigned char state[GLOBAL_ONE_WG_ROWS];
+  __shared__ Best red_b[GNW];
+  __shared__ int red_i[GNW];
+  __shared__ float cur[7 * MAX_J];
+  BlockCtxT<GNW> cx{(int)threadIdx.x, GNT, red_b, red_i};
+  diverse_global(cx, scores, valid, R, K, J, P, rule, mind, state, cur, idx, nullptr, n_bad);
+}
+
+// The same selection with one stream-ordered launch per pick, for more rows than one workgroup handles well: launch p first reduces
+// the per-block bests of launch p - 1 (every block, redundantly, with the same total order: one result) into pick p - 1, then lets
+// mind follow it and writes its own per-block best of step p.  A row always belongs to the same thread of the same block, which alone
+// writes its mind and state (in the workspace), the previous pick's state included; blk holds two sets of gridDim.x bests, used in
+// turn.  Launch P only reduces and writes the last pick.  No workgroup waits for another one inside a launch.
+constexpr int GLOBAL_GRID_BLOCKS = 256;
+__global__ void __launch_bounds__(NT) k_select_diverse_global_step(const float *__restrict__ scores, const float *__restrict__ valid, int R, int K,
+                                                                    int J, int P, int p, int rule, double *__restrict__ mind,
+                                                                    unsigned char *__restrict__ state, Best *__restrict__ blk,
+                                                                    int32_t *__restrict__ idx, int32_t *__restrict__ n_bad) {
+  __shared__ Best red_b[NW];
+  __shared__ int red_i[NW];
+  __shared__ float cur[7 * MAX_J];
+  BlockCtx cx{(int)threadIdx.x, NT, red_b, red_i};
+  const int nb = gridDim.x;
+  Best prev{-1, 0.0, -1};
+  bool fresh = false;
+  if (p > 0) {
+    const Best *src = blk + (size_t)((p - 1) & 1) * nb;
+    for (int k = cx.tid; k < nb; k += NT)
+      if (better(src[k], prev)) prev = src[k];
+    cx.best(prev);
+    fresh = global_fresh(prev, rule, p - 1);
+    if (blockIdx.x == 0 && cx.tid == 0) idx[p - 1] = prev.idx;
+    if (fresh) global_stage(cx, scores, valid, prev.idx, K, J, cur);
+    cx.sync();
+  }
+  if (p == P) return;
+  Best b{-1, 0.0, -1};
+  int bad = 0;
+  for (int i = blockIdx.x * NT + cx.tid; i < R; i += nb * NT) {
+    unsigned char s;
+    if (p == 0) {
+      const bool ok = global_row_ok(scores, valid, i, K, J);
+      s = ok ? 0 : 2;
+      state[i] = s, mind[i] = INFINITY;
+      bad += !ok;
+    } else {
+      s = state[i];
+      if (i == prev.idx) state[i] = s = prev.cls == 1 ? 1 : 3;
+    }
+    if (s == 1 || s == 3) continue;
+    const Best cand = s == 0 ? global_candidate(scores, valid, i, K, J, p, fresh, cur, mind) : Best{0, 0.0, i};
+    if (better(cand, b)) b = cand;
+  }
+  cx.best(b);
+  if (cx.tid == 0) blk[(size_t)(p & 1) * nb + blockIdx.x] = b;
+  if (p == 0) {
+    bad = cx.sum_i(bad);
+    if (cx.tid == 0 && bad) cx.add(n_bad, bad);
+  }
+}
+
+// idx (P) holds global rows in [0,R): written by k_select_diverse_global of the same call
+__global__ void __launch_bounds__(NT) k_gather_rows(const int32_t *__restrict__ idx, const float *__restrict__ noise,
+                                                    const float *__restrict__ mean, const float *__restrict__ logvar, long long P, int ND, int J,
+                                                    float *__restrict__ noise_o, float *__restrict__ mean_o, float *__restrict__ logvar_o) {
+  const int per = ND + 6 * J;
+  const long long t = (long long)blockIdx.x * NT + threadIdx.x;
+  if (t >= P * per) return;
+  const long long o = t / per;
+  const int e = (int)(t % per);
+  const size_t src = (size_t)idx[o];
+  if (e < ND) {
+    noise_o[(size_t)o * ND + e] = noise[src * ND + e];
+  } else if (e < ND + 3 * J) {
+    mean_o[(size_t)o * 3 * J + (e - ND)] = mean[src * 3 * J + (e - ND)];
+  } else {
+    logvar_o[(size_t)o * 3 * J + (e - ND - 3 * J)] = logvar[src * 3 * J + (e - ND - 3 * J)];
+  }
+}
+
 inline unsigned grid_of(long long n) { return (unsigned)((n + NT - 1) / NT); }
 
 int check_draws(const char *who, long long row0, long long R, int J, int n_draws) {
@@ -384,6 +565,44 @@ int launch_gather(const int32_t *idx, const float *noise, const float *mean, con
   return check_launch("gather_picks");
 }
 
+int check_shape_global(const char *who, long long G, int K, int J, int P, int rule) {
+  if (int rc = check_shape(who, G, K, J)) return rc;
+  DFX_REQUIRE(G * K <= MAX_GLOBAL_ROWS, "%s: %lld candidate rows above %d", who, G * K, MAX_GLOBAL_ROWS);
+  DFX_REQUIRE(P >= 1 && P <= G * K, "%s: P = %d outside [1,G K = %lld]", who, P, G * K);
+  DFX_REQUIRE(rule == DFX_DIVERSE_FARTHEST || rule == DFX_DIVERSE_FIRST_PICK, "%s: rule %d not in {0 farthest, 1 first pick}", who, rule);
+  return DFX_OK;
+}
+
+// mind (rows fp64) | two sets of per-block bests | state (rows bytes)
+size_t diverse_global_state_bytes(long long rows) {
+  return ((size_t)rows * 8 + 2 * GLOBAL_GRID_BLOCKS * sizeof(Best) + (size_t)rows + 15) & ~(size_t)15;
+}
+
+bool g_diverse_global_launches = false;   // dfx_debug_diverse_global_path
+
+int launch_diverse_global(const float *scores, const float *valid, int G, int K, int J, int P, int rule, int32_t *idx, int32_t *n_bad,
+                          void *state, hipStream_t st) {
+  const int R = G * K;
+  // one workgroup up to GLOBAL_ONE_WG_ROWS rows; above that one launch per pick over many CUs (where the two meet)
+  if (R <= GLOBAL_ONE_WG_ROWS && !g_diverse_global_launches) {
+    k_select_diverse_global<<<1, GNT, 0, st>>>(scores, valid, R, K, J, P, rule, idx, n_bad);
+    return check_launch("select_diverse_global");
+  }
+  double *mind = static_cast<double *>(state);
+  Best *blk = reinterpret_cast<Best *>(mind + R);
+  unsigned char *state_b = reinterpret_cast<unsigned char *>(blk + 2 * GLOBAL_GRID_BLOCKS);
+  const int need = (R + NT - 1) / NT, nb = need < GLOBAL_GRID_BLOCKS ? need : GLOBAL_GRID_BLOCKS;
+  for (int p = 0; p <= P; ++p)
+    k_select_diverse_global_step<<<nb, NT, 0, st>>>(scores, valid, R, K, J, P, p, rule, mind, state_b, blk, idx, n_bad);
+  return check_launch("select_diverse_global (one launch per pick)");
+}
+
+int launch_gather_rows(const int32_t *idx, const float *noise, const float *mean, const float *logvar, int P, int ND, int J, float *noise_o,
+                       float *mean_o, float *logvar_o, hipStream_t st) {
+  k_gather_rows<<<grid_of((long long)P * (ND + 6 * J)), NT, 0, st>>>(idx, noise, mean, logvar, P, ND, J, noise_o, mean_o, logvar_o);
+  return check_launch("gather_rows");
+}
+
 }  // namespace psel
 }  // namespace dfx
 
@@ -413,6 +632,29 @@ int dfx_select_diverse(const float *mean, const float *logvar, const float *vali
   if (int rc = dfx::psel::launch_scores(mean, logvar, valid, stats, G, K, n_class, scores, st)) return rc;
   return dfx::psel::launch_diverse(scores, valid, G, K, n_class, P, idx, n_bad, st);
 }
+
+size_t dfx_select_diverse_global_workspace_bytes(long long rows) {
+  if (rows <= 0) return 0;
+  return dfx::psel::diverse_global_state_bytes(rows) + (size_t)rows * 6 * MAX_J * sizeof(float);
+}
+
+int dfx_select_diverse_global(const float *mean, const float *logvar, const float *valid, const float *stats, int G, int K, int n_class, int P,
+                              int rule, int32_t *idx, float *scores, int32_t *n_bad, void *workspace, size_t workspace_bytes,
+                              dfx_stream_t stream) {
+  if (int rc = dfx::psel::check_shape_global("select_diverse_global", G, K, n_class, P, rule)) return rc;
+  DFX_REQUIRE(mean && logvar && valid && stats && idx && n_bad && workspace, "select_diverse_global: null pointer");
+  const long long R = (long long)G * K;
+  DFX_REQUIRE(workspace_bytes >= dfx_select_diverse_global_workspace_bytes(R), "select_diverse_global: workspace of %zu bytes, %zu needed",
+              workspace_bytes, dfx_select_diverse_global_workspace_bytes(R));
+  DFX_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "select_diverse_global: workspace is not 16-byte aligned");
+  hipStream_t st = dfx::as_stream(stream);
+  float *sc = scores ? scores : reinterpret_cast<float *>(static_cast<char *>(workspace) + dfx::psel::diverse_global_state_bytes(R));
+  DFX_HIP_TRY(hipMemsetAsync(n_bad, 0, sizeof(int32_t), st));
+  if (int rc = dfx::psel::launch_scores(mean, logvar, valid, stats, G, K, n_class, sc, st)) return rc;
+  return dfx::psel::launch_diverse_global(sc, valid, G, K, n_class, P, rule, idx, n_bad, workspace, st);
+}
+
+void dfx_debug_diverse_global_path(int path) { dfx::psel::g_diverse_global_launches = path == 1; }
 
 int dfx_select_fit(const float *mean, const float *logvar, const float *target_mean, const float *target_logvar, const float *weight, int G,
                    int K, int n_class, int32_t *idx, float *fit, int32_t *n_bad, dfx_stream_t stream) {
@@ -447,6 +689,20 @@ int dfx_debug_select_diverse_host(const float *scores, const float *valid, int G
     diverse_group(cx, scores + g * K * 6 * n_class, valid + g * n_class, K, n_class, P, mind.data(), state.data(), idx + g * P,
                   pick_dist ? pick_dist + g * P : nullptr, n_bad);
   }
+  return DFX_OK;
+}
+
+int dfx_debug_select_diverse_global_host(const float *scores, const float *valid, int G, int K, int n_class, int P, int rule, int32_t *idx,
+                                         double *pick_dist, int32_t *n_bad) {
+  if (int rc = dfx::psel::check_shape_global("debug_select_diverse_global_host", G, K, n_class, P, rule)) return rc;
+  DFX_REQUIRE(scores && valid && idx && n_bad, "debug_select_diverse_global_host: null pointer");
+  const int R = G * K;
+  std::vector<double> mind((size_t)R);
+  std::vector<unsigned char> state((size_t)R);
+  float cur[7 * MAX_J];
+  *n_bad = 0;
+  SerialCtx cx;
+  diverse_global(cx, scores, valid, R, K, n_class, P, rule, mind.data(), state.data(), cur, idx, pick_dist, n_bad);
   return DFX_OK;
 }
 

@@ -334,7 +334,8 @@ class PartEncoderForTransformerDecoder(nn.Module):
         if not (gen and include_part_code and include_params) or include_z or encode_ref or per_part_encoder:
             _unsupported("PartEncoder needs gen, include_part_code, include_params and no include_z / encode_ref / per_part_encoder")
         if selective_noise_sampling or selective_noise_sampling_global:
-            _unsupported("selective_noise_sampling")
+            _unsupported("selective_noise_sampling / selective_noise_sampling_global as constructor flags: pass selective='shape' or "
+                         "selective='global' to sample_latents / generate at call time")
         if use_gt_params and part_aligner is not None:
             _unsupported("use_gt_params together with a part_aligner (stage 1 trains without one, train_chair_stage1.py)")
         if not use_gt_params and part_aligner is None:
@@ -524,16 +525,30 @@ class PartEncoderForTransformerDecoder(nn.Module):
 
     @torch.no_grad()
     def sample_latents(self, sample_num, sample_points, device, fixed_id=None, valid_id=None, epoch=0, K=None,
-                       part_code=None, **kwargs):
+                       part_code=None, selective=None, selective_keep=10, selective_rule="farthest", seed=None, selective_stats=None,
+                       return_selection=False, **kwargs):
         """part_encoders.py:1052-1110.  Returns (ctx, mean_per_point, logvar_per_point, seg_mask, valid_id,
-        [part_code, mean, logvar, noise]); rows = sample_num * K."""
+        [part_code, mean, logvar, noise]); rows = sample_num * K.
+
+        ``selective``: the reference's selective noise sampling (its constructor flags, a call-time keyword here): 'shape' keeps the
+        ``selective_keep`` most different of K = 100 aligner noises of every shape (:1089-1094), 'global' the sample_num *
+        selective_keep most different of all candidates (:1095-1100; ``selective_rule`` 'farthest' = the intent, 'first_pick' = what
+        the reference executes); rows = sample_num * selective_keep, shape-major / in pick order, and ``noise`` holds the selected rows
+        (``LatentSampler.sample_latents_selective``).  ``seed`` keys the unit draws of the scores (None: from torch's host generator);
+        ``selective_stats`` replaces them by given statistics (``part_sampling.draw_stats``' layout).  ``return_selection``: a seventh
+        element, the dict of what was kept: idx ((S,keep) candidates in [0,K) for 'shape', (S keep,) global rows for 'global'),
+        source_row (S keep,) the shape behind every row, n_bad; None without ``selective``."""
+        if selective not in (None, "shape", "global"):
+            raise ValueError(f"sample_latents: selective={selective!r} not in (None, 'shape', 'global')")
         al = self.part_aligner
+        if selective is not None and (al is None or not al.cimle):
+            _unsupported("selective noise sampling without a cIMLE part aligner (there are no candidate noises to search)")
         w = None
         if part_code is None:
             w = torch.randn(sample_num, self.zdim, self.n_class).to(device)               # :1054 — drawn on the HOST like the reference
             #                                                                               (one torch.manual_seed -> the same latents in both); scaled in-kernel
         if al.cimle:
-            K = 10 if K is None else K                                                    # :1062
+            K = (100 if selective else 10) if K is None else K                            # :1062, :1064
             noise = torch.randn(sample_num * K, al.noise_dim).to(device)                  # :1065 (host draw as well)
             if al.cimle_start_epoch > epoch:
                 noise = torch.zeros_like(noise)
@@ -542,10 +557,20 @@ class PartEncoderForTransformerDecoder(nn.Module):
         if valid_id is None:
             valid_id = torch.ones(sample_num, self.n_class, device=device)
         fid = [0] * self.n_class if fixed_id is None else [int(v) for v in (fixed_id.tolist() if torch.is_tensor(fixed_id) else fixed_id)]
-        out = self.sampler().sample_latents(w, noise, valid_id, fixed_id=fid, K=K, npoints=sample_points, part_code=part_code)
+        if selective is None:
+            out = self.sampler().sample_latents(w, noise, valid_id, fixed_id=fid, K=K, npoints=sample_points, part_code=part_code)
+        else:
+            if seed is None and selective_stats is None:
+                seed = int(torch.randint(0, 2 ** 62, ()))
+            out = self.sampler().sample_latents_selective(w, noise, valid_id, selective, K=K, keep=selective_keep, rule=selective_rule,
+                                                          fixed_id=fid, npoints=sample_points, part_code=part_code, stats=selective_stats,
+                                                          seed=0 if seed is None else int(seed))
         ctx = [out["part_code"], out["params"]]                                            # prepare_ctx :1317-1326
-        return (ctx, out["mean_per_point"], out["logvar_per_point"], out["seg_mask"], out["valid_id"],
-                [out["part_code"], out["mean"], out["logvar"], out["noise"]])
+        res = (ctx, out["mean_per_point"], out["logvar_per_point"], out["seg_mask"], out["valid_id"],
+               [out["part_code"], out["mean"], out["logvar"], out["noise"]])
+        if return_selection:
+            res += (None if selective is None else {k: out[k] for k in ("idx", "source_row", "n_bad")},)
+        return res
 
     @torch.no_grad()
     def compose_latents(self, code_src, code_a, valid, sample_points, **recipe):
@@ -577,18 +602,25 @@ class PartEncoderForTransformerDecoder(nn.Module):
 
 
 @torch.no_grad()
-def generate(encoder, diffusion, sample_num, npoints, valid_id=None, fixed_id=None, K=10, epoch=0, seed=None,
-             ret_traj=False, ret_interval=20, generator=None):
+def generate(encoder, diffusion, sample_num, npoints, valid_id=None, fixed_id=None, K=None, epoch=0, seed=None,
+             ret_traj=False, ret_interval=20, generator=None, selective=None, selective_keep=10, selective_rule="farthest"):
     """anchor_gen.py:1034-1084 (gen branch) without the batch bookkeeping: latents once per batch, then the fused reverse chain.
-    Returns decode's dict + 'pred_seg_mask', 'anchors' (rows, npoints, 3), 'present'.  ``seed=None``: fresh noise per call
-    (engine.resolve_seed).  The reference's full output dict is ``networks.AnchorDiffAE.forward``."""
+    Returns decode's dict + 'pred_seg_mask', 'anchors' (rows, npoints, 3), 'present' (+ 'source_row', 'selected' with ``selective``).  ``seed=None``: fresh noise per call
+    (engine.resolve_seed).  K = None: 10 rows per shape (part_encoders.py:1062).  ``selective`` 'shape' / 'global' (with
+    ``selective_keep`` / ``selective_rule``): diverse generation, ``sample_latents``' selective noise sampling; sample_num *
+    selective_keep rows, K = 100 candidates per shape unless given.  The reference's full output dict is
+    ``networks.AnchorDiffAE.forward``."""
     device = next(encoder.parameters()).device
-    ctx, mean_pp, logvar_pp, seg, valid, latents = encoder.sample_latents(sample_num, npoints, device, fixed_id=fixed_id,
-                                                                          valid_id=valid_id, epoch=epoch, K=K)
+    sel = {} if selective is None else dict(selective=selective, selective_keep=selective_keep, selective_rule=selective_rule, seed=seed)
+    ctx, mean_pp, logvar_pp, seg, valid, latents, kept = encoder.sample_latents(sample_num, npoints, device, fixed_id=fixed_id, valid_id=valid_id,
+                                                                                epoch=epoch, K=K, return_selection=True, **sel)
     pred = decode(diffusion, ctx, seg, valid_id=valid, ret_traj=ret_traj, ret_interval=ret_interval, seed=seed, generator=generator)
     pred["pred_seg_mask"] = seg
     pred["anchors"] = mean_pp.transpose(1, 2)
     pred["present"] = valid
+    if kept is not None:
+        pred["source_row"] = kept["source_row"]        # the shape behind every row
+        pred["selected"] = kept["idx"]
     return pred
 
 

@@ -253,6 +253,71 @@ class LatentSampler:
         _ffi.check(rc, "dfx_part_search")
         return out
 
+    def part_search_global(self, code_src, code_a, valid, noise, K, P, rule="farthest", stats=None, seed=0, row0=0, n_draws=512, row_budget=0,
+                           return_scores=False):
+        """``dfx_part_search_global``: ``part_search``'s chunked aligner pass over G groups of K noises, then ONE diverse selection over all
+        G K rows (``part_sampling.select_diverse_global``: 'farthest' or 'first_pick').  Arguments as ``part_search`` (no new part).
+        Returns dict: idx (P,) int32 global rows, noise (P,noise_dim), mean / logvar (P,3,J), scores ((G K,6,J) or None), n_bad."""
+        from . import part_sampling
+        rule = part_sampling.rule_id(rule)
+        code_a = np.ascontiguousarray((code_a.detach().cpu().numpy() if isinstance(code_a, torch.Tensor) else np.asarray(code_a)).astype(np.int32))
+        code_src, valid, noise, stats = map(self._f, (code_src, valid, noise, stats))
+        J, Z, ND = self.n_class, self.zdim, self.noise_dim
+        S, G, K, P = code_src.shape[0], code_a.shape[0], int(K), int(P)
+        assert tuple(code_src.shape) == (S, Z, J) and code_a.shape == (G, J) and tuple(valid.shape) == (G, J)
+        assert tuple(noise.shape) == (G * K, ND) and (stats is None or tuple(stats.shape) == (G * K, 4, 3, J))
+        e = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=self.device)
+        scores = e(G * K, 6, J) if return_scores else None
+        out = {"idx": e(max(P, 0), dtype=torch.int32), "noise": e(max(P, 0), ND), "mean": e(max(P, 0), 3, J), "logvar": e(max(P, 0), 3, J),
+               "scores": scores, "n_bad": e(1, dtype=torch.int32)}
+        with torch.cuda.device(self.device):
+            rc = _ffi.lib().dfx_part_search_global(
+                self._h, _ffi.ptr(code_src), S, code_a.ctypes.data_as(ctypes.c_void_p), _ffi.ptr(valid), _ffi.ptr(noise), G, K, P, rule,
+                _ffi.ptr(stats), int(seed), int(row0), int(n_draws), int(row_budget), _ffi.ptr(out["idx"]), _ffi.ptr(out["noise"]),
+                _ffi.ptr(out["mean"]), _ffi.ptr(out["logvar"]), _ffi.ptr(scores), _ffi.ptr(out["n_bad"]), _ffi.current_stream())
+        _ffi.check(rc, "dfx_part_search_global")
+        return out
+
+    def sample_latents_selective(self, w_noise, aligner_noise, valid_id, mode, K=100, keep=10, rule="farthest", fixed_id=None, npoints=2048,
+                                 part_code=None, stats=None, seed=0, row0=0, n_draws=512, row_budget=0):
+        """``sample_latents`` with the reference's selective noise sampling (part_encoders.py:1052-1110 with selective_noise_sampling /
+        selective_noise_sampling_global): K aligner noises per shape, of which ``keep`` per shape survive.
+
+        mode 'shape': the ``keep`` most different configurations of every shape (``part_search`` 'diverse'); rows shape-major.
+        mode 'global': the S keep most different of all S K candidates, whatever shape they belong to (``part_search_global`` with
+        ``rule``); rows in pick order.  w_noise (S,zdim,J) or part_code (S,zdim,J); aligner_noise (S K,noise_dim); valid_id (S,J);
+        fixed_id as ``sample_latents`` (:1071-1081: a fixed part takes shape 0's code and is valid, and with any fixed part every
+        shape uses shape 0's K noises).  The candidates' codes are never materialised; the kept rows go through one
+        ``dfx_compose_latents`` call.  Returns ``sample_latents``' dict over S keep rows plus idx ((S,keep) candidates in [0,K) for
+        'shape', (S keep,) global rows for 'global'), source_row (S keep,) int64 (the shape behind every row) and n_bad.
+        Deviation: ``noise`` holds the SELECTED rows (the reference returns all S K)."""
+        if mode not in ("shape", "global"):
+            raise ValueError(f"sample_latents_selective: mode {mode!r} not in ('shape', 'global')")
+        if (w_noise is None) == (part_code is None):
+            raise ValueError("sample_latents_selective: give exactly one of w_noise / part_code")
+        valid_id, aligner_noise = self._f(valid_id), self._f(aligner_noise)
+        S, J, K, keep = valid_id.shape[0], self.n_class, int(K), int(keep)
+        code = self.flow_reverse(w_noise) if part_code is None else self._f(part_code)
+        assert tuple(code.shape) == (S, self.zdim, J) and tuple(aligner_noise.shape) == (S * K, self.noise_dim)
+        fid = np.zeros(J, np.int32) if fixed_id is None else np.asarray([int(v) != 0 for v in fixed_id], np.int32)
+        code_a = np.where(fid[None, :] != 0, 0, np.arange(S, dtype=np.int32)[:, None]).astype(np.int32)            # :1074
+        valid = valid_id
+        if fid.any():
+            f = torch.as_tensor(fid, dtype=torch.float32, device=self.device)
+            valid = valid_id * (1 - f) + f * (valid_id[:1] + f).clamp(0, 1)                                           # :1072-1075
+            aligner_noise = aligner_noise[:K].repeat(S, 1)                                                            # :1076-1081
+        kw = dict(stats=stats, seed=seed, row0=row0, n_draws=n_draws, row_budget=row_budget)
+        if mode == "shape":
+            found = self.part_search(code, code_a, valid, aligner_noise, K, "diverse", P=keep, **kw)
+            source = torch.arange(S, device=self.device).repeat_interleave(keep)
+        else:
+            found = self.part_search_global(code, code_a, valid, aligner_noise, K, S * keep, rule=rule, **kw)
+            source = found["idx"].long() // K
+        src_host = source.cpu().numpy()
+        out = self.compose_latents(code, code_a[src_host], valid[source].contiguous(), noise_src=found["noise"], npoints=npoints)
+        out.update(idx=found["idx"], source_row=source, n_bad=found["n_bad"])
+        return out
+
     def optimize_noise(self, part_code, valid, z0, problem, max_iter, trace=False):
         """``dfx_noise_opt_run``: R independent gradient descents on the aligner noise (tools/shape_edit.py:80-129 per row), enqueued
         without host round trips.  part_code (R,zdim,J), valid (R,J), z0 (R,noise_dim); ``problem``: dict with the (R,3,J) targets

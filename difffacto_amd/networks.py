@@ -130,10 +130,13 @@ class AnchorDiffAE(nn.Module):
         return (pred.reshape(bs, E, P, n, 3), seg.reshape(bs, E, P, n), valid.reshape(bs, E, P, J), codes.reshape(bs, E, P, Z, J), noises,
                 means.reshape(bs, E, P, 3, J), logvars.reshape(bs, E, P, 3, J))
 
-    def sample(self, sample_num, fixed_id, valid_id, device, epoch, K=10):
-        """anchor_gen.py:798-801 (K is ignored there as well: cimle_sample_num rows per shape)."""
+    def sample(self, sample_num, fixed_id, valid_id, device, epoch, K=10, **selective):
+        """anchor_gen.py:798-801 (K is ignored there as well: cimle_sample_num rows per shape).  With ``selective='shape' | 'global'``
+        (and ``selective_keep``, ``selective_rule``, ``seed``, ``return_selection``: the keywords of the encoder's ``sample_latents``):
+        its selective noise sampling, 100 candidates per shape of which ``selective_keep`` per shape are kept."""
+        K = None if selective.get("selective") is not None else self.cimle_sample_num
         return self.encoder.sample_latents(sample_num, self.npoints, device, fixed_id=torch.as_tensor(fixed_id).to(device),
-                                           valid_id=valid_id, epoch=epoch, K=self.cimle_sample_num, part_code=None)
+                                           valid_id=valid_id, epoch=epoch, K=K, part_code=None, **selective)
 
     @torch.no_grad()
     def cache_noise(self, pcds, device, eval_whole=False):
@@ -219,7 +222,11 @@ class AnchorDiffAE(nn.Module):
 
     # ------------------------------------------------------------------------------------------------------------------
     def forward(self, pcds, device="cuda", epoch=0, **kwargs):
-        """anchor_gen.py:970-1136."""
+        """anchor_gen.py:970-1136.  The gen branch takes ``selective='shape' | 'global'`` (+ ``selective_keep``, ``selective_rule``, ``seed``):
+        the encoder's selective noise sampling.  'shape': the reference's dict with ``selective_keep`` samples per shape in place of
+        ``cimle_sample_num`` ("pred_sample i" = kept row i of every shape).  'global': the B * selective_keep rows in pick order, one
+        entry per row ("pred", "sample prior", "pred_seg_mask", "anchors", "present" = the row's own mask); the batch's own entries
+        ("input", "shift", ...) stay per shape.  Both add "source_row" (the shape behind every kept row) and "selected"."""
         inp = pcds["input"].to(device)
         ref = pcds["ref"].to(device)
         input_seg_mask = pcds["seg_mask"].to(device)
@@ -249,11 +256,19 @@ class AnchorDiffAE(nn.Module):
                 fixed_id = [0] * self.num_anchors
                 for i in (self.fix_part_ids or ()):
                     fixed_id[i] = 1
-                ctx, mean_pp, logvar_pp, _seg, _valid, _lat = self.sample(B, fixed_id, valid_id, device, epoch, K=10)
+                selective, kept = kwargs.get("selective"), None
+                if selective is not None:
+                    keys = ("selective", "selective_keep", "selective_rule", "seed")
+                    ctx, mean_pp, logvar_pp, _seg, _valid, _lat, kept = self.sample(B, fixed_id, valid_id, device, epoch, return_selection=True,
+                                                                                    **{k: kwargs[k] for k in keys if k in kwargs})
+                    h = int(kwargs.get("selective_keep", 10))                                  # rows per shape instead of cimle_sample_num
+                else:
+                    ctx, mean_pp, logvar_pp, _seg, _valid, _lat = self.sample(B, fixed_id, valid_id, device, epoch, K=10)
                 var_pp = torch.exp(logvar_pp)
                 _pred = self.decode(mean_pp, ctx=ctx, device=device, variance=var_pp, anchor_assignments=_seg.to(torch.int32), valid_id=_valid)
                 priors = torch.randn_like(var_pp.transpose(1, 2)) * torch.sqrt(var_pp.transpose(1, 2)) + mean_pp.transpose(1, 2)
-                if self.cimle:
+                present = valid_id
+                if self.cimle and selective != "global":
                     pred = {}
                     for i in range(h):
                         for k, v in _pred.items():
@@ -264,12 +279,18 @@ class AnchorDiffAE(nn.Module):
                     pred["pred_seg_mask"] = _fold(_seg, h)[:, 0]
                     pred["anchors"] = _fold(mean_pp, h)[:, 0].transpose(1, 2)
                 else:
+                    # one entry per row.  selective='global': the B * selective_keep rows come in pick order and a shape owns any number of
+                    # them, so nothing is folded by shape: 'present' is every row's own mask and 'source_row' names its shape
                     pred = _pred
                     pred["sample prior"] = priors
                     pred["pred_seg_mask"] = _seg
                     pred["anchors"] = mean_pp.transpose(1, 2)
+                    if selective == "global":
+                        present = _valid
+                if kept is not None:
+                    pred["source_row"], pred["selected"] = kept["source_row"], kept["idx"]
                 pred.update({"input": inp, "input_ref": ref, "ref_seg_mask": pcds["ref_seg_mask"], "seg_mask": input_seg_mask,
-                             "present": valid_id, "shift": pcds["shift"], "scale": pcds["scale"]})
+                             "present": present, "shift": pcds["shift"], "scale": pcds["scale"]})
                 pred = {k: v.detach().cpu() for k, v in pred.items()}
                 return [(pred, "gen_fixed" + "".join(str(i) for i in fixed_id))]
             # ---- reconstruction ("sample") mode :1085-1134 ----

@@ -11,6 +11,15 @@ import torch
 from . import _ffi
 
 MODES = {"fit": 0, "first": 1, "diverse": 2}   # DFX_SEARCH_*
+RULES = {"farthest": 0, "first_pick": 1}       # DFX_DIVERSE_*
+
+
+def rule_id(rule):
+    if isinstance(rule, str):
+        if rule not in RULES:
+            raise ValueError(f"rule {rule!r} not in {sorted(RULES)}")
+        return RULES[rule]
+    return int(rule)
 
 
 def _f(t, device=None):
@@ -58,6 +67,30 @@ def select_diverse(mean, logvar, valid, K, P, stats=None, seed=0, row0=0, n_draw
     with torch.cuda.device(mean.device):
         rc = _ffi.lib().dfx_select_diverse(_ffi.ptr(mean), _ffi.ptr(logvar), _ffi.ptr(valid), _ffi.ptr(stats), G, K, J, P, _ffi.ptr(idx), _ffi.ptr(scores), _ffi.ptr(n_bad), _ffi.current_stream())
     _ffi.check(rc, "dfx_select_diverse")
+    return {"idx": idx, "scores": scores, "n_bad": n_bad}
+
+
+def select_diverse_global(mean, logvar, valid, K, P, rule="farthest", stats=None, seed=0, row0=0, n_draws=512):
+    """Greedy diverse selection over all G K rows of the call (``dfx_select_diverse_global``): mean, logvar (G K,3,J),
+    valid (G,J) -> dict idx (P,) int32 GLOBAL rows, scores (G K,6,J), n_bad.  Two rows are compared on the parts valid in both; a pair
+    without a common part is skipped.  ``rule``: 'farthest' (farthest-point selection, the reference's intent) or 'first_pick' (distance
+    to pick 0 only, what the reference's subsample_params_global executes).  ``stats`` as ``select_diverse``."""
+    _need_gpu(mean)
+    mean, logvar, valid, stats = _f(mean), _f(logvar, mean.device), _f(valid, mean.device), _f(stats, mean.device)
+    G, J = valid.shape
+    K, P, rule = int(K), int(P), rule_id(rule)
+    if stats is None:
+        stats = draw_stats(G * K, J, seed, row0=row0, n_draws=n_draws, device=mean.device)
+    assert tuple(mean.shape) == (G * K, 3, J) == tuple(logvar.shape) and tuple(stats.shape) == (G * K, 4, 3, J)
+    idx = torch.empty(P, dtype=torch.int32, device=mean.device)
+    scores = torch.empty(G * K, 6, J, dtype=torch.float32, device=mean.device)
+    n_bad = torch.empty(1, dtype=torch.int32, device=mean.device)
+    nbytes = _ffi.lib().dfx_select_diverse_global_workspace_bytes(G * K)
+    ws = torch.empty(nbytes + 16, dtype=torch.uint8, device=mean.device)
+    with torch.cuda.device(mean.device):
+        rc = _ffi.lib().dfx_select_diverse_global(_ffi.ptr(mean), _ffi.ptr(logvar), _ffi.ptr(valid), _ffi.ptr(stats), G, K, J, P, rule, _ffi.ptr(idx),
+                                                  _ffi.ptr(scores), _ffi.ptr(n_bad), (ws.data_ptr() + 15) & ~15, nbytes, _ffi.current_stream())
+    _ffi.check(rc, "dfx_select_diverse_global")
     return {"idx": idx, "scores": scores, "n_bad": n_bad}
 
 

@@ -4,6 +4,10 @@ configs/gen_*.py, anchor_gen.py:1034-1084): latent sampler -> fused reverse chai
 
     python examples/generate.py --config gen_chair --shapes 32 --K 2 --timesteps 100 [--checkpoint pretrained/chair.pth]
                                 [--ddim 25] [--metrics [--jsd]] [--out clouds.npy]
+                                [--selective {shape,global} [--keep 10] [--rule first_pick]]
+
+--selective: diverse generation (the reference's selective noise sampling): 100 aligner noises per shape unless --K says otherwise,
+of which --keep per shape survive: the most different ones of every shape, or of the whole batch ('global').
 
 Without a checkpoint the networks are random-init (synthetic weights): the clouds are noise-shaped, the timings are real.
 """
@@ -46,7 +50,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="gen_chair", choices=sorted(NOISE_SCALE))
     ap.add_argument("--shapes", type=int, default=32, help="shapes drawn from the flow prior")
-    ap.add_argument("--K", type=int, default=2, help="aligner noises per shape (the reference's val pass uses 10)")
+    ap.add_argument("--K", type=int, default=None, help="aligner noises per shape (default 2; 100 with --selective; the reference's val pass uses 10)")
+    ap.add_argument("--selective", default=None, choices=["shape", "global"], help="keep the most different configurations: per shape, or of the whole batch")
+    ap.add_argument("--keep", type=int, default=10, help="with --selective: rows kept per shape")
+    ap.add_argument("--rule", default="farthest", choices=["farthest", "first_pick"],
+                    help="with --selective global: farthest-point selection, or the distance to the first pick only (what the reference executes)")
     ap.add_argument("--timesteps", type=int, default=100)
     ap.add_argument("--ddim", type=int, default=0, help="DDIM with this many steps ('quad' list) instead of DDPM")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "f32"])
@@ -78,7 +86,9 @@ def main():
     generate(enc, diff, 2, N, valid_id=valid[:2], K=1, seed=a.seed)   # warm-up (library load, handles)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    out = generate(enc, diff, a.shapes, N, valid_id=valid, fixed_id=[0, 0, 0, 0], K=a.K, seed=a.seed)
+    K = a.K if a.K is not None else (100 if a.selective else 2)
+    out = generate(enc, diff, a.shapes, N, valid_id=valid, fixed_id=[0, 0, 0, 0], K=K, seed=a.seed, selective=a.selective,
+                   selective_keep=a.keep, selective_rule=a.rule)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     pred = out["pred"]
@@ -86,6 +96,9 @@ def main():
     steps = len(diff.steps)
     print(f"{a.config}: {n} clouds x {N} points, {steps} {'DDIM' if a.ddim else 'DDPM'} steps ({a.precision}) in {dt * 1e3:.1f} ms = {n / dt:.1f} shapes/s; "
           f"finite: {bool(torch.isfinite(pred).all())}")
+    if a.selective:
+        per_shape = torch.bincount(out["source_row"], minlength=a.shapes)
+        print(f"selective {a.selective} ({a.rule}): {K} candidates per shape, {n} rows kept; rows per shape min {int(per_shape.min())} max {int(per_shape.max())}")
     if a.out:
         np.save(a.out, pred.cpu().numpy())
     if a.metrics:

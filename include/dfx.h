@@ -473,6 +473,31 @@ int dfx_select_diverse(const float *mean, const float *logvar, const float *vali
 int dfx_select_fit(const float *mean, const float *logvar, const float *target_mean, const float *target_logvar, const float *weight, int G,
                    int K, int n_class, int32_t *idx, float *fit, int32_t *n_bad, dfx_stream_t stream);
 
+/* Greedy diverse selection over ALL rows of a call (the intent of subsample_params_global, part_encoders.py:591-621):
+ * P picks out of the R = G K candidate rows, whatever group they belong to.  Layouts are dfx_select_diverse's: candidate row
+ * r = g K + k, valid (G,n_class) with the mask of row r = valid[r / K], stats (R,4,3,n_class); scores (R,6,n_class) is an output and
+ * may be NULL (it then lives in the workspace); idx (P) int32 holds GLOBAL row numbers.  1 <= P <= R, K <= 4096, R <= 262144.
+ *   scores: dfx_select_diverse's, each row with its own mask.
+ *   distance: rows i and s are compared on the parts valid in both: n = sum_j m_i[j] m_s[j],
+ *     d(i,s) = sum over c < 6 and j valid in both of (s_i - s_s)^2 / n, fp64 in (c, j) order (part_encoders.py:611-612).  A pair
+ *     without a common part (n = 0) puts no constraint on the candidate: it is skipped in the minimum (the reference divides 0 by 0
+ *     and its arg-max goes to NaN), so a candidate that shares no part with any pick keeps mind = +inf and is picked next.
+ *   selection: a row is finite when it has a valid part and every score on its own valid parts is finite; n_bad counts the others.
+ *     Pick 0 is the lowest finite row, every later pick the free finite row whose smallest distance to the picks (mind) is largest,
+ *     of equal ones the lowest index; non-finite rows by ascending index, only when no finite row is free.  A row is never picked
+ *     twice (the reference can repeat a row once every distance is 0).
+ *   rule DFX_DIVERSE_FARTHEST: mind follows every pick (farthest-point selection).  DFX_DIVERSE_FIRST_PICK: mind follows pick 0
+ *     only: what the reference executes, because its out_score is never appended to (:603-619), when all rows share one mask.
+ *   workspace: dfx_select_diverse_global_workspace_bytes(R) device bytes (sized for n_class = 8 and scores = NULL), 16-byte aligned.
+ * No host round trip between picks and no workgroup that waits for another: up to 512 rows one workgroup runs the whole call;
+ * above, one stream-ordered launch per pick spreads the rows over many workgroups and the next launch reduces their bests. */
+#define DFX_DIVERSE_FARTHEST 0
+#define DFX_DIVERSE_FIRST_PICK 1
+size_t dfx_select_diverse_global_workspace_bytes(long long rows);
+int dfx_select_diverse_global(const float *mean, const float *logvar, const float *valid, const float *stats, int G, int K, int n_class, int P,
+                              int rule, int32_t *idx, float *scores, int32_t *n_bad, void *workspace, size_t workspace_bytes,
+                              dfx_stream_t stream);
+
 #define DFX_SEARCH_FIT 0     /* dfx_select_fit; P = 1 */
 #define DFX_SEARCH_FIRST 1   /* candidates 0 .. P-1 (the intent of part_encoders.py:687); the aligner runs on those only */
 #define DFX_SEARCH_DIVERSE 2 /* dfx_select_diverse */
@@ -496,6 +521,17 @@ int dfx_part_search(dfx_latents *h, const float *code_src, int S, const int32_t 
                     const float *target_logvar, const float *weight, const float *stats, uint64_t seed, long long row0, int n_draws,
                     int row_budget, int32_t *idx, float *noise_sel, float *mean_sel, float *logvar_sel, float *scores, int32_t *n_bad,
                     dfx_stream_t stream);
+
+/* dfx_part_search with the global selection: the same chunked aligner pass over G groups of K noises (no new part; the G K candidate
+ * codes are never held), but mean, logvar and scores of ALL R = G K rows stay in the handle's workspace (R x 12 n_class floats),
+ * dfx_select_diverse_global runs once after the last chunk, and the P winners' rows are gathered: idx (P) int32 global rows,
+ * noise_sel (P,noise_dim), mean_sel / logvar_sel (P,3,n_class); scores (R,6,n_class) or NULL.  stats / seed / row0 / n_draws /
+ * row_budget as dfx_part_search (DIVERSE); rule DFX_DIVERSE_*.  The result does not depend on row_budget under
+ * dfx_debug_lin_split_k(1).  Every argument, code_a included, is checked before the first HIP call. */
+int dfx_part_search_global(dfx_latents *h, const float *code_src, int S, const int32_t *code_a, const float *valid, const float *noise,
+                           int G, int K, int P, int rule, const float *stats, uint64_t seed, long long row0, int n_draws, int row_budget,
+                           int32_t *idx, float *noise_sel, float *mean_sel, float *logvar_sel, float *scores, int32_t *n_bad,
+                           dfx_stream_t stream);
 
 /* Training forward / backward of the part aligner (stage 2: configs/train_*_stage2.py and gen_*.py with train_aligner; replaces torch autograd through
  * PartAlignerTransformer, part_encoders.py:88-143, for the shipped options: cimle with cond_noise_type 0, class_cond + add_class_cond, single_attn,

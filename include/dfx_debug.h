@@ -119,6 +119,14 @@ int dfx_debug_select_diverse_host(const float *scores, const float *valid, int G
                                   int32_t *n_bad);
 int dfx_debug_select_fit_host(const float *mean, const float *logvar, const float *target_mean, const float *target_logvar,
                               const float *weight, int G, int K, int n_class, int32_t *idx, float *fit, int32_t *n_bad);
+/* The same for dfx_select_diverse_global's selection on given scores (G K,6,n_class): idx (P) global rows, pick_dist (P) float64 or
+ * NULL = the winner's smallest distance to the picks before it (0 for pick 0 and for a non-finite pick, +inf for a pick that shares
+ * no part with any earlier one). */
+int dfx_debug_select_diverse_global_host(const float *scores, const float *valid, int G, int K, int n_class, int P, int rule, int32_t *idx,
+                                         double *pick_dist, int32_t *n_bad);
+/* Debug / A-B switch: 1 makes dfx_select_diverse_global (and dfx_part_search_global) run their selection as one launch per pick at every
+ * size; any other value: automatic (default: one workgroup for the whole call up to 512 rows).  The picks are the same. */
+void dfx_debug_diverse_global_path(int path);
 
 #ifdef __cplusplus
 }
