@@ -1288,415 +1288,6 @@ __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe(const KParams p) {
 }
 
 // ----------------------------------------------------------------------------------------------
-// k_denoise_pipe2: the bf16 chain with TWO point tiles (64 points) per wavefront — VERDICT r2 item 1(a).
-//
-// The pipelined kernel above reads every A (weight) fragment from LDS once per 32 points: eight wavefronts x 24 KiB per record,
-// ~10 % of the energy of a record on a chip that sits on its power cap (profiles/r02_energy_budget.txt).  Here a workgroup is four
-// wavefronts of 64 points (the same 256-point tile, LDS map and ring), ONE wavefront per SIMD with the whole 512-entry register
-// file: every fragment read feeds two MFMAs (tile 0, tile 1), and the b1 accumulator initialisers are read once and enter both
-// tiles' first MFMA as its C operand (dst != src C), so the LDS -> register traffic per point halves.  There is no partner
-// wavefront to run the VALU work beside the MFMAs, so the feed-forward is software-pipelined inside the wave (the r02 DFX_SWP
-// experiment, now with two tiles): for FF record j
-//     stage A   GEMM1 of chunk j   (16 fragments x 2 tiles = 32 MFMAs)  with the packed-fp16 GELU of chunk j-1 behind them (5 v_pk per MFMA)
-//     stage B   GEMM2 of chunk j-1 (8 x 2 = 16 MFMAs)                   with (a, g) of chunk j -> packed fp16 and b1 of chunk j+1 -> registers
-// Same device functions and the same MFMA order per accumulator as k_denoise_pipe: bit-identical results (tested).
-constexpr int P2_NW = 4;
-constexpr int P2_LDS = PipeCfg<P2_NW>::L_PSTATE + PSTATE_FIELDS * 256 * 4;   // the 4-wave ring map (6 DMA pieces per wave) with 256 point slots
-struct GeluRegs {
-  h2 y[8], z[8], r[8];
-};
-// operation K = stage * 8 + pair of gelu16_f16_math (same instructions in the same order per pair)
-template <int K>
-__device__ __forceinline__ void gelu_op(GeluRegs &t, const h2 (&aa)[8], const h2 (&gg)[8]) {
-  constexpr int st = K / 8, i = K % 8;
-  if (st == 0) t.z[i] = __builtin_elementwise_fma(gg[i], gg[i], h2c(-1.62f));
-  if (st == 1) t.y[i] = aa[i] * gg[i];
-  if (st == 2) t.z[i] = __builtin_elementwise_min(t.z[i], h2c(1.62f));
-  if (st == 3) t.r[i] = __builtin_elementwise_fma(t.z[i], h2c(-0.0011402554f), h2c(0.0057853916f));
-  if (st == 4) t.r[i] = __builtin_elementwise_fma(t.r[i], t.z[i], h2c(-0.0158536041f));
-  if (st == 5) t.r[i] = __builtin_elementwise_fma(t.r[i], t.z[i], h2c(0.0409006897f));
-  if (st == 6) t.r[i] = __builtin_elementwise_fma(t.r[i], t.z[i], h2c(-0.1098130657f));
-  if (st == 7) t.r[i] = __builtin_elementwise_fma(t.r[i], t.z[i], h2c(0.3885767652f));
-  if (st == 8) asm("v_pk_fma_f16 %0, %1, %2, 0.5 op_sel_hi:[1,1,0] clamp" : "=v"(t.z[i]) : "v"(gg[i]), "v"(t.r[i]));   // Phi
-  if (st == 9) t.y[i] = t.y[i] * t.z[i];
-}
-template <int K0, int N>
-__device__ __forceinline__ void gelu_ops(GeluRegs &t, const h2 (&aa)[8], const h2 (&gg)[8]) {
-  if constexpr (N > 0) {
-    gelu_op<K0>(t, aa, gg);
-    gelu_ops<K0 + 1, N - 1>(t, aa, gg);
-  }
-}
-__device__ __forceinline__ void hid_from(const GeluRegs &t, HidAct &hid) {
-  hid.f[0] = make_uint4(__builtin_bit_cast(unsigned, t.y[0]), __builtin_bit_cast(unsigned, t.y[1]), __builtin_bit_cast(unsigned, t.y[2]),
-                        __builtin_bit_cast(unsigned, t.y[3]));
-  hid.f[1] = make_uint4(__builtin_bit_cast(unsigned, t.y[4]), __builtin_bit_cast(unsigned, t.y[5]), __builtin_bit_cast(unsigned, t.y[6]),
-                        __builtin_bit_cast(unsigned, t.y[7]));
-}
-// fragment order of this kernel's records: the 16 W1 fragments (GEMM1 MFMA e: half e >> 3, index e & 7), then the 8 W2 fragments
-enum { P2_NEXT_W1 = 0, P2_NEXT_W2 = 1, P2_NEXT_AS = 2 };
-template <int NEXT>
-__device__ __forceinline__ constexpr int p2_next_frag(int i) { return NEXT == P2_NEXT_W1 ? w1_frag(i, 0) : NEXT == P2_NEXT_W2 ? w2_frag(i) : as_frag(i); }
-
-// b1 of one chunk -> registers (the C operand of both tiles' first GEMM1 MFMAs)
-__device__ __forceinline__ void load_b1(v16f &b1a, v16f &b1g, const float *b1) {
-  typedef __attribute__((address_space(3))) const float lds_cf;
-  unsigned addr = (unsigned)(uintptr_t)(lds_cf *)b1;
-  asm volatile("" : "+v"(addr));   // one base register, immediate offsets
-  const float *src = (const float *)(lds_cf *)(uintptr_t)addr;
-  load16(b1a, src);
-  load16(b1g, src + 32);
-}
-
-// GEMM1 accumulators (a, g) in ARCHITECTURAL registers.  With a 512-register budget hipcc selects the accumulator-file form for
-// every MFMA builtin, and the GELU's conversions would then pay one v_accvgpr_read per value (64 per record: a third more VALU
-// instructions).  The C/D file of an MFMA is chosen per instruction (A and B independently), so these — and only these — MFMAs are
-// inline asm: D / C = VGPRs, A = the fragment from LDS (VGPR), B = the LayerNorm output (accumulator file: nothing else reads it).
-// Hazards (guide §5.7 item 2): the inputs are written long before (ds_read + the compiler's lgkmcnt wait; xn one record earlier); D is
-// read only by the NEXT MFMA on the same accumulator as its whole C (0 states) and by the conversions of stage B, at least three
-// MFMA issues (> 96 cycles) after the accumulator's last MFMA (8-pass XDL: 12 states).
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void mfma_v_init(v16f &acc, const uint4 &A, const v8bf &B, const v16f &C) {
-  asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(acc) : "v"(__builtin_bit_cast(v4u, A)), "a"(B), "v"(C));
-}
-__device__ __forceinline__ void mfma_v_acc(v16f &acc, const uint4 &A, const v8bf &B) {
-  asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(__builtin_bit_cast(v4u, A)), "a"(B));
-}
-template <int E>   // the ten operations behind the E-th fragment of stage A: tile 0's GELU rides on fragments 0..7, tile 1's on 8..15
-__device__ __forceinline__ void gelu_slot(GeluRegs &t, const h2 (&aa)[2][8], const h2 (&gg)[2][8], int half_slot) {
-  constexpr int tl = E >> 3, base = (E & 7) * 10;
-  if (half_slot == 0) gelu_ops<base, 5>(t, aa[tl], gg[tl]);
-  else gelu_ops<base + 5, 5>(t, aa[tl], gg[tl]);
-}
-
-// The wave's DMA duty for the record three ahead: FF records (24 contiguous KiB) are issued one piece at a time from inside the
-// MFMA stream (two scalar bases, immediate offsets); the irregular attention record at once behind its barrier.
-struct Issuer2 {
-  const char *src;   // nullptr: nothing deferred
-  unsigned dst;
-  unsigned voff;
-  template <int Q>
-  __device__ __forceinline__ void piece() const {
-    if (src) {
-      if (Q < 4) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 offset:%3" ::"v"(voff), "s"(src), "s"(dst), "i"(Q * 1024) : "memory");
-      else asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 offset:%3" ::"v"(voff), "s"(src + 4096), "s"(dst + 4096), "i"((Q - 4) * 1024) : "memory");
-    }
-  }
-};
-
-// One FF record for both tiles.  FIRST: record F0 (GEMM1 of chunk 0 only); LAST: record F16 (GELU + GEMM2 of chunk 15 only).
-// P enters with the record's first eight fragments and leaves with the next record's (tail prefetch, as in k_denoise_pipe).
-template <bool FIRST, bool LAST, int NEXT>
-__device__ __forceinline__ void ff2(v16f (&h)[2][4], const Act<DFX_PREC_BF16> (&xn)[2][4], v16f (&a)[2], v16f (&g)[2], h2 (&aa)[2][8],
-                                    h2 (&gg)[2][8], v16f &b1a, v16f &b1g, const uint4 *ck, uint4 (&P)[8], const uint4 *ck_next,
-                                    const float *b1_next, const Issuer2 &dma, Tracer &tr) {
-  GeluRegs t;
-  HidAct hid[2];
-  __builtin_amdgcn_sched_barrier(0);
-  tr.stamp(30);
-  if constexpr (!LAST) {
-    auto stage_a = [&](auto ec) {
-      constexpr int e = decltype(ec)::value;
-      constexpr int k = e & 7, half = e >> 3;
-#pragma unroll
-      for (int tl = 0; tl < 2; ++tl) {
-        v16f &acc = (k & 1) ? g[tl] : a[tl];
-        if (e < 2) mfma_v_init(acc, P[k], xn[tl][2 * half + (k >> 2)].f[(k >> 1) & 1], (k & 1) ? b1g : b1a);
-        else mfma_v_acc(acc, P[k], xn[tl][2 * half + (k >> 2)].f[(k >> 1) & 1]);
-        if (tl == 1) P[k] = e + 8 < 16 ? ck[w1_frag((e + 8) & 7, (e + 8) >> 3)] : FIRST ? ck_next[p2_next_frag<NEXT>(e + 8 - 16)] : ck[w2_frag(e + 8 - 16)];
-        if constexpr (!FIRST) gelu_slot<e>(t, aa, gg, tl);
-        if constexpr (!FIRST && e == 7) {
-          if (tl == 1) hid_from(t, hid[0]);
-        }
-        if (tl == 0 && e % 3 == 0 && e / 3 < 6) {   // DMA pieces behind fragments 0, 3, 6, 9, 12, 15
-          if (e == 0) dma.piece<0>();
-          if (e == 3) dma.piece<1>();
-          if (e == 6) dma.piece<2>();
-          if (e == 9) dma.piece<3>();
-          if (e == 12) dma.piece<4>();
-          if (e == 15) dma.piece<5>();
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    };
-    stage_a(std::integral_constant<int, 0>{});  stage_a(std::integral_constant<int, 1>{});  stage_a(std::integral_constant<int, 2>{});
-    stage_a(std::integral_constant<int, 3>{});  stage_a(std::integral_constant<int, 4>{});  stage_a(std::integral_constant<int, 5>{});
-    stage_a(std::integral_constant<int, 6>{});  stage_a(std::integral_constant<int, 7>{});  stage_a(std::integral_constant<int, 8>{});
-    stage_a(std::integral_constant<int, 9>{});  stage_a(std::integral_constant<int, 10>{}); stage_a(std::integral_constant<int, 11>{});
-    stage_a(std::integral_constant<int, 12>{}); stage_a(std::integral_constant<int, 13>{}); stage_a(std::integral_constant<int, 14>{});
-    stage_a(std::integral_constant<int, 15>{});
-    if constexpr (!FIRST) hid_from(t, hid[1]);
-    tr.stamp(31);
-  } else {
-    gelu_ops<0, 80>(t, aa[0], gg[0]);
-    hid_from(t, hid[0]);
-    gelu_ops<0, 80>(t, aa[1], gg[1]);
-    hid_from(t, hid[1]);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  if constexpr (!FIRST) {
-    const float *b1q = nullptr;
-    if (!LAST && b1_next) {   // one opaque base register, immediate offsets
-      typedef __attribute__((address_space(3))) const float lds_cf;
-      unsigned addr = (unsigned)(uintptr_t)(lds_cf *)b1_next;
-      asm volatile("" : "+v"(addr));
-      b1q = (const float *)(lds_cf *)(uintptr_t)addr;
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-#pragma unroll
-      for (int tl = 0; tl < 2; ++tl) {
-        h[tl][i & 3] = mma_hid(P[i], hid[tl].f[i >> 2], h[tl][i & 3]);
-        if (tl == 1) P[i] = ck_next[p2_next_frag<NEXT>(i)];
-        if constexpr (!LAST) {   // (a, g) of this chunk -> packed fp16: a got its last MFMA before g did
-          if (i < 4) {
-#pragma unroll
-            for (int q = 2 * i; q < 2 * i + 2; ++q) aa[tl][q] = pk_f16(a[tl][2 * q], a[tl][2 * q + 1]);
-          } else {
-#pragma unroll
-            for (int q = 2 * (i - 4); q < 2 * (i - 4) + 2; ++q) gg[tl][q] = pk_f16(g[tl][2 * q], g[tl][2 * q + 1]);
-          }
-        }
-        if constexpr (!LAST) {   // b1 of the next chunk -> registers, a quarter per fragment (landed long before the next record's first MFMA)
-          if (tl == 1 && b1q) {
-            const v4f q4 = *reinterpret_cast<const v4f *>(b1q + (i < 4 ? 4 * i : 32 + 4 * (i - 4)));
-            v16f &dst = i < 4 ? b1a : b1g;
-#pragma unroll
-            for (int e4 = 0; e4 < 4; ++e4) dst[4 * (i & 3) + e4] = q4[e4];
-          }
-        }
-        if constexpr (LAST) {
-          if (tl == 0 && i < 6) {
-            if (i == 0) dma.piece<0>();
-            if (i == 1) dma.piece<1>();
-            if (i == 2) dma.piece<2>();
-            if (i == 3) dma.piece<3>();
-            if (i == 4) dma.piece<4>();
-            if (i == 5) dma.piece<5>();
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  } else {
-    // Stage A's MFMAs are inline asm writing VGPRs: the hazard recogniser does not see them, and on this path no stage B sits
-    // between the last MFMA (e = 15, tile 1 -> g[1]) and the conversions that read a / g.  An 8-pass XDL write needs 11 wait states
-    // before a VALU read (18 for 16 passes): 24 explicit ones, once per block, whatever order the scheduler gives the conversions.
-    asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int tl = 0; tl < 2; ++tl) gelu16_f16_cvt(a[tl], g[tl], aa[tl], gg[tl]);
-    __builtin_amdgcn_sched_barrier(0);
-    if (b1_next) load_b1(b1a, b1g, b1_next);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  tr.stamp(32);
-}
-
-__global__ void __launch_bounds__(P2_NW * 64, 1) k_denoise_pipe2(const KParams p) {
-  constexpr int PREC = DFX_PREC_BF16;
-  constexpr int NW = P2_NW, PTS = PipeCfg<NW>::PTS * 2;
-  static_assert(PTS == 256 && P2_LDS <= 160 * 1024, "LDS budget");
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int hf = lane >> 5, pj = lane & 31;
-  const int wpg = (p.N + PTS - 1) / PTS;
-  int bid = blockIdx.x;
-  {
-    const int per = 8 * wpg;
-    const int full = ((int)gridDim.x / per) * per;
-    if (bid < full) {
-      const int x = bid & 7, q = (bid % per) >> 3;
-      bid = (bid / per) * per + x * wpg + q;
-    }
-  }
-  const int s = __builtin_amdgcn_readfirstlane(bid / wpg);
-  const int depth = p.d.depth;
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane(
-      (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)pipe_smem);
-  const unsigned voff = lane * 16;
-  // the wave's two tiles are tiles 2 wave and 2 wave + 1 of the workgroup's eight (the point slots of k_denoise_pipe<8>'s waves)
-  int nn[2], ptv[2];
-  bool lv[2];
-  unsigned long long gidv[2];
-#pragma unroll
-  for (int tl = 0; tl < 2; ++tl) {
-    int n0 = __builtin_amdgcn_readfirstlane((bid - s * wpg) * PTS + (2 * wave + tl) * 32);
-    lv[tl] = n0 < p.N;
-    if (!lv[tl]) n0 = p.N - 32;
-    nn[tl] = n0 + pj;
-    ptv[tl] = (2 * wave + tl) * 32 + pj;
-    gidv[tl] = ((unsigned long long)p.shape0 + (unsigned)s) * (unsigned)p.N + (unsigned)nn[tl];
-  }
-
-  DmaState dma{0, 0, 0, 0, 0, nullptr};
-  issue_record<NW>(p, dma, wave, voff, lds0, s);
-  issue_record<NW>(p, dma, wave, voff, lds0, s);
-  issue_record<NW>(p, dma, wave, voff, lds0, s);
-  {
-    float4 *winx = reinterpret_cast<float4 *>(pipe_smem + L_WINX);
-    float2 *pregb = reinterpret_cast<float2 *>(pipe_smem + L_PREGB);
-    float4 *wout = reinterpret_cast<float4 *>(pipe_smem + L_WOUT);
-    float *cp = reinterpret_cast<float *>(pipe_smem + L_CPART);
-    const int tid = threadIdx.x;
-    if (tid < 128) {
-      winx[tid] = p.d.win_x[tid];
-      pregb[tid] = p.d.pre_gb[tid];
-      wout[tid] = p.d.wout[tid];
-    }
-    for (int i = tid; i < NCLS * INNER; i += NW * 64) cp[i] = p.cpart[(size_t)s * NCLS * INNER + i];
-  }
-  unsigned vmask = 0;
-  float *ps_lds = reinterpret_cast<float *>(pipe_smem + PipeCfg<NW>::L_PSTATE);
-#pragma unroll
-  for (int tl = 0; tl < 2; ++tl) {
-    PointState ps0;
-    ps0.live = lv[tl];
-    point_init(p, ps0, s, nn[tl], gidv[tl], vmask);
-    pstate_store(ps_lds, ptv[tl], PTS, ps0, true);
-  }
-  __syncthreads();
-  const float4 *winx = reinterpret_cast<const float4 *>(pipe_smem + L_WINX) + hf * 64;
-  const float2 *pregb = reinterpret_cast<const float2 *>(pipe_smem + L_PREGB) + hf * 64;
-  const float4 *wout = reinterpret_cast<const float4 *>(pipe_smem + L_WOUT) + hf * 64;
-
-  // `defer`: the record that follows is an FF record with an MFMA stream to hide the DMA pieces in
-  Issuer2 isr{nullptr, 0u, voff};
-#ifdef DFX_TRACE
-  Tracer tr{(p.trace != nullptr && bid == 0 && wave == 0) ? p.trace : nullptr, p.trace_cap, 0};
-#else
-  Tracer tr;
-#endif
-#define DFX_RECORD2(defer)                                                              \
-  do {                                                                                  \
-    __builtin_amdgcn_sched_barrier(0);                                                  \
-    /* the (scalar) bookkeeping of a deferred FF record runs AHEAD of the barrier: with one wavefront per SIMD nobody */ \
-    /* covers what sits between the barrier and the first MFMA */                      \
-    isr.src = nullptr;                                                                  \
-    const bool deferred_ = (defer) && dma.k > 0 && dma.step < p.nsteps;                 \
-    if (deferred_) {                                                                    \
-      isr.src = pin_ptr(dma.ff_src);                                                    \
-      isr.dst = (unsigned)__builtin_amdgcn_readfirstlane(lds0 + L_RING + dma.slot * SLOT_BYTES + wave * PipeCfg<NW>::CALLS * 1024); \
-      dma.ff_src += SLOT_BYTES;                                                         \
-      advance_record(p, dma);                                                           \
-    }                                                                                   \
-    ck = reinterpret_cast<const uint4 *>(pipe_smem + L_RING + cur * SLOT_BYTES) + lane; \
-    cur = cur + 1 == NSLOT ? 0 : cur + 1;                                               \
-    __builtin_amdgcn_sched_barrier(0);                                                  \
-    tr.stamp(1);                                                                        \
-    wait_vmcnt<PipeCfg<NW>::CALLS>();                                                   \
-    __builtin_amdgcn_s_barrier();                                                       \
-    tr.stamp(2);                                                                        \
-    if (!deferred_) issue_record<NW>(p, dma, wave, voff, lds0, s);                      \
-    __builtin_amdgcn_sched_barrier(0);                                                  \
-  } while (0)
-#define DFX_PEEK2() (reinterpret_cast<const uint4 *>(pipe_smem + L_RING + cur * SLOT_BYTES) + lane)
-
-  uint4 P[8];
-  int cur = 0, seq = 0;
-  v16f h[2][4];
-  bool done = false;
-  for (int step = 0; step <= p.nsteps && !done; ++step) {
-    for (int b = 0; b < depth; ++b, ++seq) {
-      const uint4 *ck;
-      Act<PREC> xn[2][4];
-#pragma unroll
-      for (int tl = 0; tl < 2; ++tl) {
-        if (seq > 0)
-          add_cvec(h[tl], reinterpret_cast<const float *>(pipe_smem + L_BCONST + ((seq - 1) & 1) * BCONST_BYTES) + BCONST_B2_OFF + hf * 64);
-        if (b == 0) {
-          PointState ps;
-          ps.s = s, ps.n = nn[tl], ps.gid = gidv[tl], ps.live = lv[tl];
-          pstate_load(ps_lds, ptv[tl], PTS, ps, step > 0);
-          bool dn = false;
-          if (step > 0) {
-            float eps[3];
-            post_eps<true>(h[tl], wout, p.d.bout, eps);
-            dn = step_epilogue(p, ps, eps, step - 1, step_t(p, step - 1, s));
-            if (!dn) pstate_store(ps_lds, ptv[tl], PTS, ps, false);
-          }
-          if (step == p.nsteps) dn = true;
-          if (!dn) proj_in_prenorm<true>(h[tl], ps.x, reinterpret_cast<const float *>(pipe_smem + L_CPART) + ps.sg * INNER + hf * 64, winx, pregb);
-          done = dn;   // (wave-uniform and the same for both tiles: mode / step count)
-        }
-        if (!done) ln_to_act<PREC>(h[tl], xn[tl]);
-      }
-      if (done) break;
-      // ---- attention record ----
-      DFX_RECORD2(false);
-      const uint4 *rec = ck;
-      {
-        if (seq == 0) {
-#pragma unroll
-          for (int i = 0; i < 8; ++i) P[i] = rec[as_frag(i)];
-        }
-        v16f sb, sim[2];
-        load16(sb, reinterpret_cast<const float *>(rec - lane + 1024) + hf * 16);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-#pragma unroll
-          for (int tl = 0; tl < 2; ++tl)
-            sim[tl] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(P[i]), xn[tl][i >> 1].f[i & 1], i == 0 ? sb : sim[tl], 0, 0, 0);
-          P[i] = rec[ms_frag(i)];
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        tr.stamp(21);
-        Act<PREC> pa[2];
-#pragma unroll
-        for (int tl = 0; tl < 2; ++tl) attn_softmax(sim[tl], pa[tl], vmask);
-        __builtin_amdgcn_sched_barrier(0);
-        tr.stamp(22);
-        const uint4 *nx = DFX_PEEK2();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-#pragma unroll
-          for (int tl = 0; tl < 2; ++tl)
-            h[tl][i & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(P[i]), pa[tl].f[i >> 2], h[tl][i & 3], 0, 0, 0);
-          P[i] = nx[w1_frag(i, 0)];
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        tr.stamp(23);
-      }
-#pragma unroll
-      for (int tl = 0; tl < 2; ++tl) {
-        add_cvec(h[tl], reinterpret_cast<const float *>(rec - lane + 1088) + hf * 64);
-        ln_to_act<PREC>(h[tl], xn[tl]);
-        bias_slot_one(xn[tl], hf);
-        // LN3's output is read by GEMM1's MFMAs only: into the accumulator file HERE, once per block (an "a" operand whose value
-        // lives in VGPRs is otherwise copied in front of every asm MFMA: 64 v_accvgpr_write per record)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          asm volatile("" : "+a"(xn[tl][c].f[0]));
-          asm volatile("" : "+a"(xn[tl][c].f[1]));
-        }
-      }
-      // ---- feed-forward ----
-      v16f a[2], g[2], b1a, b1g;
-      h2 aa[2][8], gg[2][8];
-      // b1' rides on the constant-one K slot: the first MFMA's C operand is zero for every chunk.  The zeros are made opaque so that they
-      // stay in registers: a rematerialised v_mov right in front of an asm MFMA is a VALU-write -> SrcC hazard the compiler does not see
-      b1a = zero16(), b1g = zero16();
-      asm volatile("" : "+v"(b1a), "+v"(b1g));
-      DFX_RECORD2(true);
-      ff2<true, false, P2_NEXT_W1>(h, xn, a, g, aa, gg, b1a, b1g, ck, P, DFX_PEEK2(), nullptr, isr, tr);
-#pragma unroll 1
-      for (int j = 1; j < FF_CHUNKS - 1; ++j) {
-        DFX_RECORD2(true);
-        ff2<false, false, P2_NEXT_W1>(h, xn, a, g, aa, gg, b1a, b1g, ck, P, DFX_PEEK2(), nullptr, isr, tr);
-      }
-      DFX_RECORD2(true);
-      ff2<false, false, P2_NEXT_W2>(h, xn, a, g, aa, gg, b1a, b1g, ck, P, DFX_PEEK2(), nullptr, isr, tr);
-      DFX_RECORD2(true);
-      ff2<false, true, P2_NEXT_AS>(h, xn, a, g, aa, gg, b1a, b1g, ck, P, DFX_PEEK2(), nullptr, isr, tr);
-    }
-  }
-#undef DFX_RECORD2
-#undef DFX_PEEK2
-  wait_vmcnt<0>();
-}
-
-// ----------------------------------------------------------------------------------------------
 // LDS-pipelined kernel, exact fp32 (v_mfma_f32_32x32x2_f32): the reference-precision sampler.  The reference computes in
 // fp32 end to end (attention.py:296-306, anchored_diffusion.py:227-395); this is that arithmetic at the structure of the bf16
 // chain kernel — one workgroup = NW wavefronts x 32 points of one shape, the residual stream in registers for the whole chain,
@@ -2036,28 +1627,193 @@ __device__ __forceinline__ void proj_in_prenorm_tiles(v16f (&h)[4], const float 
   }
 }
 
+// ---- Shared by k_denoise_coop and k_denoise_coop2: what happens inside a phase.  Each kernel keeps its own schedule (its barriers, which wave does
+// what, where W2 lives); what differs inside a phase comes in as an argument: an LDS pointer, a tile index, n.
 constexpr int COOP_NW = 8, COOP_TILES = 4;
 static_assert(FF_CHUNKS == 2 * COOP_NW, "two rounds of one chunk per wavefront");
-constexpr int COOP_W2_FIRST = 8;                                  // first W2 chunk staged in LDS (the LDS budget holds eight)
+constexpr int COOP_TSTRIDE = tile_units(DFX_PREC_BF16) * 64, COOP_AREC = asms_bytes(DFX_PREC_BF16) / 16;
+// chain-invariant operands in LDS (7 KiB): W_in x-columns (2 KiB) | pre_norm (1 KiB) | W_out (2 KiB) | cpart of the workgroup's shape (2 KiB)
+constexpr int CC_WINX = 0, CC_PREGB = 2048, CC_WOUT = 3072, CC_CPART = 5120, CC_BYTES = 7 * 1024;
+
+__device__ __forceinline__ void coop_stage_consts(unsigned char *cc, const KParams &p, int s) {   // (the caller's barrier publishes them)
+  float4 *c_winx = reinterpret_cast<float4 *>(cc + CC_WINX);
+  float2 *c_pregb = reinterpret_cast<float2 *>(cc + CC_PREGB);
+  float4 *c_wout = reinterpret_cast<float4 *>(cc + CC_WOUT);
+  float *c_cp = reinterpret_cast<float *>(cc + CC_CPART);
+  const int tid = threadIdx.x;
+  if (tid < 128) c_winx[tid] = p.d.win_x[tid], c_pregb[tid] = p.d.pre_gb[tid], c_wout[tid] = p.d.wout[tid];
+  c_cp[tid] = p.cpart[(size_t)s * NCLS * INNER + tid];
+}
+
+// The 32 points of tile (s, n - pj): initial chain state -> its LDS home between step boundaries
+// (the state would otherwise sit in scratch memory for the whole chain: a global-memory round trip per field at every step boundary)
+__device__ __forceinline__ void coop_point_init(const KParams &p, float *ps_lds, int s, int n, int pj, unsigned &vmask) {
+  PointState ps0;
+  point_init(p, ps0, s, n, ((unsigned long long)p.shape0 + (unsigned)s) * (unsigned)p.N + (unsigned)n, vmask);
+  pstate_store(ps_lds, pj, 32, ps0, true);
+}
+
+// GEMM1 fragments of chunk u -> R[base .. base + 15], in the accumulation order a(c,0) a(c,1) g(c,0) g(c,1), c = 0..3
+// (scalar base + lane offset: with the base pinned to SGPRs the sixteen loads share one address VGPR; left to itself hipcc keeps
+// 64-bit per-lane addresses, spills them, and every scratch reload — a vector-memory operation like the prefetches in flight —
+// drains the whole prefetch with s_waitcnt vmcnt(0))
+__device__ __forceinline__ void coop_load_w1(uint4 (&R)[32], int base, const uint4 *chunks, int u, int lane) {
+  constexpr int TSTRIDE = COOP_TSTRIDE;
+  const uint4 *ck = reinterpret_cast<const uint4 *>(pin_ptr(reinterpret_cast<const char *>(chunks + (size_t)u * CHUNK_TILES * TSTRIDE))) + lane;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    R[base + 4 * c + 0] = ck[(0 + c) * TSTRIDE], R[base + 4 * c + 1] = ck[(0 + c) * TSTRIDE + 64];
+    R[base + 4 * c + 2] = ck[(4 + c) * TSTRIDE], R[base + 4 * c + 3] = ck[(4 + c) * TSTRIDE + 64];
+  }
+}
+// W2 fragments of chunks first .. first + 7, output tile ct -> R[2 u], R[2 u + 1] (W2 of chunk u sits in FF record u + FF_SKEW, tiles 8..11)
+__device__ __forceinline__ void coop_load_w2(uint4 (&R)[32], int first, const uint4 *chunks, int ct, int lane) {
+  constexpr int TSTRIDE = COOP_TSTRIDE;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const uint4 *ck = reinterpret_cast<const uint4 *>(pin_ptr(reinterpret_cast<const char *>(chunks + (size_t)(first + c + FF_SKEW) * CHUNK_TILES * TSTRIDE + (8 + ct) * TSTRIDE))) + lane;
+    R[2 * (first + c)] = ck[0], R[2 * (first + c) + 1] = ck[64];
+  }
+}
+
+// h's LDS home of one 32-point tile (16 KiB): channel tile c, quad q of lane l at float4 index (4 c + q) * 64 + l.  `home` = the tile's home + lane,
+// `hc` = home + 256 c, one channel tile of it.
+__device__ __forceinline__ void hs_load(v16f &h, const v4f *hc) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const v4f x = hc[q * 64];
+    h[4 * q] = x[0], h[4 * q + 1] = x[1], h[4 * q + 2] = x[2], h[4 * q + 3] = x[3];
+  }
+}
+__device__ __forceinline__ void hs_store(v4f *hc, const v16f &h) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) hc[q * 64] = v4f{h[4 * q], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]};
+}
+__device__ __forceinline__ void hs_store_plus(v4f *hc, const v16f &h, const float *b) {   // h + b: the 16 values of b follow the accumulator's order
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const v4f bb = *reinterpret_cast<const v4f *>(b + 4 * q);
+    hc[q * 64] = v4f{h[4 * q] + bb[0], h[4 * q + 1] + bb[1], h[4 * q + 2] + bb[2], h[4 * q + 3] + bb[3]};
+  }
+}
+__device__ __forceinline__ void hs_load4(v16f (&h)[4], const v4f *home) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) hs_load(h[c], home + c * 256);
+}
+__device__ __forceinline__ void hs_store4(v4f *home, const v16f (&h)[4]) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) hs_store(home + c * 256, h[c]);
+}
+
+// Attention record of a block (`arec`: 17 pieces of 1 KiB) | its c_t row at time t (1) | its block constants (5) -> LDS by LDS-DMA: the 23 pieces go
+// round NWAVES issuing wavefronts, `slot` = this wave's place among them
+template <int NWAVES>
+__device__ __forceinline__ void coop_stage_block(const BlockPack &bp, const uint4 *arec, int t, int slot, unsigned voff, unsigned lds_at, unsigned lds_bc) {
+  constexpr int NA = asms_bytes(DFX_PREC_BF16) / 1024, NB = BCONST_BYTES / 1024;
+#pragma unroll
+  for (int i = 0; i < (NA + 1 + NB + NWAVES - 1) / NWAVES; ++i) {
+    const int k = i * NWAVES + slot;
+    if (k < NA) dma1k_pinned(reinterpret_cast<const char *>(arec) + k * 1024, voff, lds_at + k * 1024);
+    else if (k == NA) dma1k_pinned(reinterpret_cast<const char *>(bp.ct + (size_t)t * CT_ROW), voff, lds_at + NA * 1024);
+    else if (k < NA + 1 + NB) dma1k_pinned(reinterpret_cast<const char *>(bp.bconst) + (k - NA - 1) * 1024, voff, lds_bc + (k - NA - 1) * 1024);
+  }
+}
+
+// Phase A of one tile: attention and LayerNorm 3 on h (from its home and back), xn3 -> s_xn as the B operand of GEMM1 (k-th uint4: tile k >> 1, unit k & 1)
+__device__ __forceinline__ void coop_phase_a(v4f *home, const uint4 *s_at, uint4 (*s_xn)[64], int lane, unsigned vmask) {
+  constexpr int PREC = DFX_PREC_BF16;
+  const int hf = lane >> 5;
+  v16f h[4];
+  hs_load4(h, home);
+  attention<PREC>(h, s_at + lane, reinterpret_cast<const float *>(s_at + 8 * COOP_TSTRIDE) + hf * 16, reinterpret_cast<const float *>(s_at + COOP_AREC) + hf * 64, vmask);
+  Act<PREC> xo[4];
+  ln_to_act<PREC>(h, xo);
+  bias_slot_one(xo, hf);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) s_xn[2 * c][lane] = __builtin_bit_cast(uint4, xo[c].f[0]), s_xn[2 * c + 1][lane] = __builtin_bit_cast(uint4, xo[c].f[1]);
+  hs_store4(home, h);
+}
+
+// The step's noise for the tile's 32 points (n = this lane's) and the posterior table row -> s_z, ready for the step boundary: z[3][32] | row at float 128
+__device__ __forceinline__ void coop_draw_noise(const KParams &p, float *s_z, int step, int t, int s, int n, int lane) {
+  const int hf = lane >> 5, pj = lane & 31;
+  float z[3];
+  if (p.noise) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) z[i] = p.noise[(((size_t)step * p.B + s) * 3 + i) * p.N + n];
+  } else {
+    philox_normal3(p.seed, ((unsigned long long)p.shape0 + (unsigned)s) * (unsigned)p.N + (unsigned)n, (unsigned)t, 0u, z);
+  }
+  if (hf == 0) s_z[pj] = z[0], s_z[32 + pj] = z[1], s_z[64 + pj] = z[2];
+  if (lane < 8) s_z[128 + lane] = p.d.tab[(size_t)t * 8 + lane];
+}
+
+// GEMM1 of one chunk on one tile: (a, g) = W1 fragments R[cur .. cur + 15] (coop_load_w1's order) x xn3
+__device__ __forceinline__ void coop_gemm1(v16f &a, v16f &g, const uint4 (&R)[32], int cur, const uint4 (*s_xn)[64], int lane) {
+  a = zero16(), g = zero16();   // b1' rides on the constant-one K slot (bias_slot_one)
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const v8bf x0 = __builtin_bit_cast(v8bf, s_xn[2 * c][lane]), x1 = __builtin_bit_cast(v8bf, s_xn[2 * c + 1][lane]);
+    a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(R[cur + 4 * c + 0]), x0, a, 0, 0, 0);
+    g = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(R[cur + 4 * c + 2]), x0, g, 0, 0, 0);
+    a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(R[cur + 4 * c + 1]), x1, a, 0, 0, 0);
+    g = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(R[cur + 4 * c + 3]), x1, g, 0, 0, 0);
+  }
+}
+// ... and its GELU: hid = a gelu(g) -> the chunk's two uint4 rows of the GELU output
+__device__ __forceinline__ void coop_gelu_store(const v16f &a, const v16f &g, uint4 (*hid_u)[64], int lane) {
+  h2 aa[8], gg[8];
+  HidAct hid;
+  gelu16_f16_cvt(a, g, aa, gg);
+  gelu16_f16_math(aa, gg, hid);
+  hid_u[0][lane] = hid.f[0], hid_u[1][lane] = hid.f[1];
+}
+
+// Step boundary of one tile, on the wave that runs its phase A: eps from the last block's h ...
+__device__ __forceinline__ void coop_eps(float (&eps)[3], const v4f *home, const unsigned char *cc, const KParams &p, int lane) {
+  v16f h[4];
+  hs_load4(h, home);
+  post_eps_tiles(h, reinterpret_cast<const float4 *>(cc + CC_WOUT) + (lane >> 5) * 64, p.d.bout, eps);
+}
+// ... the posterior update of the chain state parked at ps_lds, with the noise coop_draw_noise left in s_z (true: the kernel is done) ...
+__device__ __forceinline__ bool coop_posterior(const KParams &p, PointState &ps, const float (&eps)[3], const float *ps_lds, const float *s_z, int s, int n,
+                                               int step, int t, int pj) {
+  ps.s = s, ps.n = n, ps.gid = 0;   // (gid: the noise was drawn by another wave)
+  pstate_load(ps_lds, pj, 32, ps, true);
+  const float zr[3] = {s_z[pj], s_z[32 + pj], s_z[64 + pj]};
+  const bool zok = p.mode != MODE_EPS;
+  return step_epilogue(p, ps, eps, step, t, zok ? zr : nullptr, zok ? s_z + 128 : nullptr);
+}
+// ... and proj_in + pre_norm of the new state -> h's home (also before the first step)
+__device__ __forceinline__ void coop_enter_step(const PointState &ps, v4f *home, const unsigned char *cc, int lane) {
+  const int hf = lane >> 5;
+  v16f h[4];
+  proj_in_prenorm_tiles(h, ps.x, reinterpret_cast<const float *>(cc + CC_CPART) + ps.sg * INNER + hf * 64, reinterpret_cast<const float4 *>(cc + CC_WINX) + hf * 64,
+                        reinterpret_cast<const float2 *>(cc + CC_PREGB) + hf * 64);
+  hs_store4(home, h);
+}
+
+// ---- k_denoise_coop: eight wavefronts on ONE 32-point tile
+constexpr int COOP_W2_FIRST = 8;                                  // first W2 chunk staged in LDS (the LDS budget holds eight; chunks 0..7: one coop_load_w2)
 constexpr int CL_XN = 0;                                          // 8 x 64 uint4: LN3 output as the B operand of GEMM1
 constexpr int CL_HID = CL_XN + 8 * 1024;                          // [16][2][64] uint4: GELU output of every chunk
 constexpr int CL_BC = CL_HID + FF_CHUNKS * 2048;                  // 2 x block constants (b1', b2), by block parity
 constexpr int CL_AT = CL_BC + 2 * BCONST_BYTES;                   // attention record (17 KiB) + c_t row (1 KiB)
 constexpr int CL_HS = CL_AT + asms_bytes(DFX_PREC_BF16) + 1024;   // home of the residual stream h: 4 tiles x 4 KiB, [tile][q][lane] float4
-constexpr int CL_CONST = CL_HS + 16 * 1024;                       // chain-invariant operands: W_in x-columns (2 KiB) | pre_norm (1 KiB) | W_out (2 KiB) | cpart (2 KiB)
-constexpr int CL_W2 = CL_CONST + 7 * 1024;                        // W2 tiles of chunks 8..15 (8 KiB each)
+constexpr int CL_CONST = CL_HS + 16 * 1024;                       // chain-invariant operands (CC_*)
+constexpr int CL_W2 = CL_CONST + CC_BYTES;                        // W2 tiles of chunks 8..15 (8 KiB each)
 constexpr int CL_Z = CL_W2 + (FF_CHUNKS - COOP_W2_FIRST) * 8192;   // this step's noise z[3][32] (384 B) | posterior table row (32 B at +512)
 constexpr int CL_PS = CL_Z + 1024;                                 // per-point chain state (x, anchor, variance, L, part id: 13 x 32 floats), home between step boundaries
 constexpr int CL_TOTAL = CL_PS + 2048;
 static_assert(CL_TOTAL <= 160 * 1024, "LDS budget of the co-operative kernel");
 
 __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams p) {
-  constexpr int PREC = DFX_PREC_BF16;
-  constexpr int TSTRIDE = tile_units(PREC) * 64, AREC = asms_bytes(PREC) / 16;
+  constexpr int TSTRIDE = COOP_TSTRIDE, AREC = COOP_AREC;
   uint4 (*s_xn)[64] = reinterpret_cast<uint4 (*)[64]>(pipe_smem + CL_XN);
   uint4 (*s_hid)[2][64] = reinterpret_cast<uint4 (*)[2][64]>(pipe_smem + CL_HID);
   uint4 *s_at = reinterpret_cast<uint4 *>(pipe_smem + CL_AT);
-  float *s_hs = reinterpret_cast<float *>(pipe_smem + CL_HS);
+  unsigned char *cc = pipe_smem + CL_CONST;
+  float *s_z = reinterpret_cast<float *>(pipe_smem + CL_Z);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int hf = lane >> 5, pj = lane & 31;
@@ -2067,26 +1823,12 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams 
   const int depth = p.d.depth;
   const bool w0 = wave == 0, tile_owner = wave < COOP_TILES;
   float *ps_lds = reinterpret_cast<float *>(pipe_smem + CL_PS);
+  v4f *home = reinterpret_cast<v4f *>(pipe_smem + CL_HS) + lane;
   unsigned vmask = 0;
-  if (w0) {   // (the state would otherwise sit in scratch memory for the whole chain: a global-memory round trip per field at every step boundary)
-    PointState ps0;
-    point_init(p, ps0, s, n, ((unsigned long long)p.shape0 + (unsigned)s) * (unsigned)p.N + (unsigned)n, vmask);
-    pstate_store(ps_lds, pj, 32, ps0, true);
-  }
+  if (w0) coop_point_init(p, ps_lds, s, n, pj, vmask);
   const uint4 *asms_s = p.as_ms + (size_t)s * depth * AREC;
-  {   // chain-invariant small operands -> LDS (wave 0 reads them at every step boundary)
-    float4 *c_winx = reinterpret_cast<float4 *>(pipe_smem + CL_CONST);
-    float2 *c_pregb = reinterpret_cast<float2 *>(pipe_smem + CL_CONST + 2048);
-    float4 *c_wout = reinterpret_cast<float4 *>(pipe_smem + CL_CONST + 3072);
-    float *c_cp = reinterpret_cast<float *>(pipe_smem + CL_CONST + 5120);
-    const int tid = threadIdx.x;
-    if (tid < 128) c_winx[tid] = p.d.win_x[tid], c_pregb[tid] = p.d.pre_gb[tid], c_wout[tid] = p.d.wout[tid];
-    c_cp[tid] = p.cpart[(size_t)s * NCLS * INNER + tid];
-    __syncthreads();
-  }
-  const float4 *winx = reinterpret_cast<const float4 *>(pipe_smem + CL_CONST) + hf * 64;
-  const float2 *pregb = reinterpret_cast<const float2 *>(pipe_smem + CL_CONST + 2048) + hf * 64;
-  const float4 *wout = reinterpret_cast<const float4 *>(pipe_smem + CL_CONST + 3072) + hf * 64;
+  coop_stage_consts(cc, p, s);   // (wave 0 reads them at every step boundary)
+  __syncthreads();
   const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)pipe_smem);
   const unsigned voff = lane * 16;
 
@@ -2095,39 +1837,16 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams 
   //           g(c,1), c = 0..3;   phase G (tile owners): W2 fragments of chunks 0..7 of the own tile, R[2 u + q]
   //   h[4]    wave 0, phase A only;   ht   tile owners, phase G only — in between h lives in LDS
   uint4 R[32];
-  // (scalar base + lane offset: with the base pinned to SGPRs the sixteen loads share one address VGPR; left to itself hipcc keeps
-  // 64-bit per-lane addresses, spills them, and every scratch reload — a vector-memory operation like the prefetches in flight —
-  // drains the whole prefetch with s_waitcnt vmcnt(0))
-  auto load_w1 = [&](int base, const uint4 *chunks, int u) {
-    const uint4 *ck = reinterpret_cast<const uint4 *>(pin_ptr(reinterpret_cast<const char *>(chunks + (size_t)u * CHUNK_TILES * TSTRIDE))) + lane;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      R[base + 4 * c + 0] = ck[(0 + c) * TSTRIDE], R[base + 4 * c + 1] = ck[(0 + c) * TSTRIDE + 64];
-      R[base + 4 * c + 2] = ck[(4 + c) * TSTRIDE], R[base + 4 * c + 3] = ck[(4 + c) * TSTRIDE + 64];
-    }
-  };
-  auto xn_frag = [&](int k) -> v8bf { return __builtin_bit_cast(v8bf, s_xn[k][lane]); };   // k-th uint4 of xn3 (tile k >> 1, unit k & 1)
-  // h's LDS home: tile c, quad q of lane l at float4 index (4 c + q) * 64 + l
-  auto hs_ptr = [&](int c, int q) -> v4f * { return reinterpret_cast<v4f *>(s_hs + ((c * 4 + q) * 64 + lane) * 4); };
 
 #ifdef DFX_TRACE   // phase stamps of wave 0 (row 0 of the trace buffer) and of wave 5 (row 1) of workgroup 0
   Tracer tr{(p.trace != nullptr && blockIdx.x == 0 && (wave == 0 || wave == 5)) ? p.trace + (size_t)(wave ? 1 : 0) * p.trace_cap : nullptr, p.trace_cap, 0};
 #else
   Tracer tr;
 #endif
-  // proj_in + pre_norm of the chain state -> h's LDS home (wave 0: before the first step and at every step boundary)
-  auto enter_step = [&](const PointState &ps) {
-    v16f h[4];
-    proj_in_prenorm_tiles(h, ps.x, reinterpret_cast<const float *>(pipe_smem + CL_CONST + 5120) + ps.sg * INNER + hf * 64, winx, pregb);
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) *hs_ptr(c, q) = v4f{h[c][4 * q], h[c][4 * q + 1], h[c][4 * q + 2], h[c][4 * q + 3]};
-  };
   if (w0) {
     PointState ps;
     pstate_load(ps_lds, pj, 32, ps, false);
-    enter_step(ps);
+    coop_enter_step(ps, home, cc, lane);
   }
   int seq = 0;
   for (int step = 0; step < p.nsteps; ++step) {
@@ -2137,17 +1856,10 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams 
       float *s_bc = reinterpret_cast<float *>(pipe_smem + CL_BC + (seq & 1) * BCONST_BYTES);
       // ---- top of the block: operands of phase A -> LDS (waves 4..7, which left phase G's barrier first), round-0 fragments requested
       if (!tile_owner) {
-        constexpr int NA = asms_bytes(PREC) / 1024, NB = BCONST_BYTES / 1024, NH = COOP_NW - COOP_TILES;   // 17 + 1 + 5 pieces over 4 waves
-#pragma unroll
-        for (int i = 0; i < (NA + 1 + NB + NH - 1) / NH; ++i) {
-          const int k = i * NH + wave - COOP_TILES;
-          if (k < NA) dma1k_pinned(reinterpret_cast<const char *>(asms_s + (size_t)b * AREC) + k * 1024, voff, lds0 + CL_AT + k * 1024);
-          else if (k == NA) dma1k_pinned(reinterpret_cast<const char *>(bp.ct + (size_t)t * CT_ROW), voff, lds0 + CL_AT + NA * 1024);
-          else if (k < NA + 1 + NB) dma1k_pinned(reinterpret_cast<const char *>(bp.bconst) + (k - NA - 1) * 1024, voff, lds0 + CL_BC + (seq & 1) * BCONST_BYTES + (k - NA - 1) * 1024);
-        }
+        coop_stage_block<COOP_NW - COOP_TILES>(bp, asms_s + (size_t)b * AREC, t, wave - COOP_TILES, voff, lds0 + CL_AT, lds0 + CL_BC + (seq & 1) * BCONST_BYTES);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
-      load_w1(0, bp.chunks, wave);   // round 0: in flight through phase A
+      coop_load_w1(R, 0, bp.chunks, wave, lane);   // round 0: in flight through phase A
       tr.stamp(10);
       __syncthreads();   // 0: attention record, c_t, block constants of this block are in LDS; h's home holds the previous block's result
       tr.stamp(11);
@@ -2160,38 +1872,10 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams 
             dma1k_pinned(reinterpret_cast<const char *>(bp.chunks + (size_t)(COOP_W2_FIRST + (k >> 3) + FF_SKEW) * CHUNK_TILES * TSTRIDE + 8 * TSTRIDE) + (k & 7) * 1024,
                          voff, lds0 + CL_W2 + k * 1024);
         }
-        if (wave == COOP_NW - 1 && b == depth - 1 && p.mode != MODE_EPS) {   // the step's noise and posterior coefficients, ready for wave 0's epilogue
-          float z[3];
-          if (p.noise) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) z[i] = p.noise[(((size_t)step * p.B + s) * 3 + i) * p.N + n];
-          } else {
-            philox_normal3(p.seed, ((unsigned long long)p.shape0 + (unsigned)s) * (unsigned)p.N + (unsigned)n, (unsigned)t, 0u, z);
-          }
-          float *s_z = reinterpret_cast<float *>(pipe_smem + CL_Z);
-          if (hf == 0) s_z[pj] = z[0], s_z[32 + pj] = z[1], s_z[64 + pj] = z[2];
-          if (lane < 8) s_z[128 + lane] = p.d.tab[(size_t)t * 8 + lane];
-        }
+        // the step's noise and posterior coefficients, ready for wave 0's epilogue
+        if (wave == COOP_NW - 1 && b == depth - 1 && p.mode != MODE_EPS) coop_draw_noise(p, s_z, step, t, s, n, lane);
       } else {           // ---- phase A: wave 0
-        v16f h[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const v4f x = *hs_ptr(c, q);
-            h[c][4 * q] = x[0], h[c][4 * q + 1] = x[1], h[c][4 * q + 2] = x[2], h[c][4 * q + 3] = x[3];
-          }
-        const uint4 *rec = s_at + lane;
-        attention<PREC>(h, rec, reinterpret_cast<const float *>(s_at + 8 * TSTRIDE) + hf * 16, reinterpret_cast<const float *>(s_at + AREC) + hf * 64, vmask);
-        Act<PREC> xo[4];
-        ln_to_act<PREC>(h, xo);
-        bias_slot_one(xo, hf);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) s_xn[2 * c][lane] = __builtin_bit_cast(uint4, xo[c].f[0]), s_xn[2 * c + 1][lane] = __builtin_bit_cast(uint4, xo[c].f[1]);
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) *hs_ptr(c, q) = v4f{h[c][4 * q], h[c][4 * q + 1], h[c][4 * q + 2], h[c][4 * q + 3]};
+        coop_phase_a(home, s_at, s_xn, lane, vmask);
       }
       tr.stamp(12);
       __syncthreads();   // 1: xn3 of this block and h are in LDS
@@ -2200,27 +1884,11 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams 
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
         const int u = r * COOP_NW + wave, cur = r * 16;
-        if (r == 0) load_w1(16, bp.chunks, u + COOP_NW);
-        else if (tile_owner) {   // round 0's registers are free: the own tile's W2 fragments of chunks 0..7 (W2 of chunk c sits in FF record c + FF_SKEW, tiles 8..11)
-#pragma unroll
-          for (int c = 0; c < COOP_W2_FIRST; ++c) {
-            const uint4 *ck = reinterpret_cast<const uint4 *>(pin_ptr(reinterpret_cast<const char *>(bp.chunks + (size_t)(c + FF_SKEW) * CHUNK_TILES * TSTRIDE + (8 + wave) * TSTRIDE))) + lane;
-            R[2 * c] = ck[0], R[2 * c + 1] = ck[64];
-          }
-        }
-        v16f a = zero16(), g = zero16();   // b1' rides on the constant-one K slot (bias_slot_one)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(R[cur + 4 * c + 0]), xn_frag(2 * c), a, 0, 0, 0);
-          g = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(R[cur + 4 * c + 2]), xn_frag(2 * c), g, 0, 0, 0);
-          a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(R[cur + 4 * c + 1]), xn_frag(2 * c + 1), a, 0, 0, 0);
-          g = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(R[cur + 4 * c + 3]), xn_frag(2 * c + 1), g, 0, 0, 0);
-        }
-        h2 aa[8], gg[8];
-        HidAct hid;
-        gelu16_f16_cvt(a, g, aa, gg);
-        gelu16_f16_math(aa, gg, hid);
-        s_hid[u][0][lane] = hid.f[0], s_hid[u][1][lane] = hid.f[1];
+        if (r == 0) coop_load_w1(R, 16, bp.chunks, u + COOP_NW, lane);
+        else if (tile_owner) coop_load_w2(R, 0, bp.chunks, wave, lane);   // round 0's registers are free: the own tile's W2 fragments of chunks 0..7
+        v16f a, g;
+        coop_gemm1(a, g, R, cur, s_xn, lane);
+        coop_gelu_store(a, g, s_hid[u], lane);
       }
       if (!w0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's W2 pieces have landed (long ago: loads complete in order)
       tr.stamp(14);
@@ -2229,11 +1897,7 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams 
       // ---- phase G: wave t accumulates tile t of h, chunk after chunk (the accumulation order of the pipelined kernel), + b2
       if (tile_owner) {
         v16f ht;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const v4f x = *hs_ptr(wave, q);
-          ht[4 * q] = x[0], ht[4 * q + 1] = x[1], ht[4 * q + 2] = x[2], ht[4 * q + 3] = x[3];
-        }
+        hs_load(ht, home + wave * 256);
         // hid / LDS-resident W2 fragments: a ring three chunks deep (one chunk = two dependent MFMAs = less than one LDS round trip),
         // fenced per chunk — left alone hipcc sinks every read next to its MFMA and the chain runs at LDS latency
         uint4 hq[4][2], wq[4][2];
@@ -2254,413 +1918,21 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams 
           ht = mma_hid(f1, hq[u & 3][1], ht);
           __builtin_amdgcn_sched_barrier(0);
         }
-        {
-          const float *b2 = s_bc + BCONST_B2_OFF + hf * 64 + wave * 16;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const v4f bb = *reinterpret_cast<const v4f *>(b2 + 4 * q);
-            *hs_ptr(wave, q) = v4f{ht[4 * q] + bb[0], ht[4 * q + 1] + bb[1], ht[4 * q + 2] + bb[2], ht[4 * q + 3] + bb[3]};
-          }
-        }
+        hs_store_plus(home + wave * 256, ht, s_bc + BCONST_B2_OFF + hf * 64 + wave * 16);
       }
     }
     tr.stamp(16);
     __syncthreads();   // the last block's tiles are in h's home
     tr.stamp(17);
     if (w0) {
-      v16f h[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const v4f x = *hs_ptr(c, q);
-          h[c][4 * q] = x[0], h[c][4 * q + 1] = x[1], h[c][4 * q + 2] = x[2], h[c][4 * q + 3] = x[3];
-        }
       float eps[3];
-      post_eps_tiles(h, wout, p.d.bout, eps);
+      coop_eps(eps, home, cc, p, lane);
       tr.stamp(18);
       PointState ps;
-      ps.s = s, ps.n = n, ps.gid = 0;   // (gid: the noise was drawn by wave 7)
-      pstate_load(ps_lds, pj, 32, ps, true);
-      const float *s_z = reinterpret_cast<const float *>(pipe_smem + CL_Z);
-      const float zr[3] = {s_z[pj], s_z[32 + pj], s_z[64 + pj]};
-      const bool zok = p.mode != MODE_EPS;
-      if (step_epilogue(p, ps, eps, step, t, zok ? zr : nullptr, zok ? s_z + 128 : nullptr)) break;   // (the other waves leave through the loop bound: nsteps = 1 in these modes)
+      if (coop_posterior(p, ps, eps, ps_lds, s_z, s, n, step, t, pj)) break;   // (the other waves leave through the loop bound: nsteps = 1 in these modes)
       tr.stamp(19);
       pstate_store(ps_lds, pj, 32, ps, false);
-      if (step + 1 < p.nsteps) enter_step(ps);
-      tr.stamp(20);
-    }
-  }
-}
-
-// ---- k_denoise_coop16 (round 5): the co-operative kernel on SIXTEEN-point tiles (v_mfma_f32_16x16x32_bf16 / _f16).
-// A 2048-point shape is 128 tiles of 16 points instead of 64 of 32: a single shape occupies 128 CUs, two shapes the whole chip, and every VALU phase of a
-// tile's critical path (LayerNorms, softmax, GELU, step boundary: 10.3 k of the 13.5 k cycles of a block in k_denoise_coop) works on half the values per
-// lane; an MFMA is 16 cycles instead of 32.  Same records in memory — no second pack: a 16 x 32 A fragment of this MFMA is TWO 8-byte pieces of the 32 x 32
-// tile the packs hold (the K order of those tiles is the accumulator order, whose groups of four consecutive channels stay together), gathered by address.
-// Layout: lane l = (point j = l & 15, group g = l >> 4); accumulator tile c (0..7), register r (0..3) = channel 16 c + 4 g + r; the B fragment of k-step s
-// (32 channels) is built in-lane from tiles 2 s, 2 s + 1 (element e = register e & 3 of tile 2 s + (e >> 2)), and the gathered A fragments follow that order.
-// The accumulation order over K differs from the 32 x 32 x 16 family (32 channels per MFMA instead of 16), so this variant is NOT bit-identical to the
-// others: it is gated against the exact-fp32 chain and the CPU oracle at the bf16 tolerances (tests/test_gpu_small_batch16.py).
-// Work of a block: phase A (wave 0: attention + LayerNorms), phase H (all 8 waves: chunks w and w + 8 of the hidden layer, both 16-unit halves of a chunk
-// on one wave so that the GELU output is a complete B fragment), phase G (all 8 waves: wave w owns accumulator tile w of h; its 16 W2 fragments sit in the
-// registers round 0 of phase H has freed).  The next block's attention record | c_t row | b2 are fetched by LDS-DMA during phase H into the other half of
-// a double buffer.  One workgroup per CU (128 fragment registers), LDS 77 KiB.
-constexpr int C16_NW = 8, C16_PTS = 16;
-constexpr int C16_XN = 0;                                            // 4 x 64 uint4: LN3 output, B fragments of the four k-steps
-constexpr int C16_HID = C16_XN + 4 * 1024;                           // 16 x 64 uint4: GELU output, B fragment of every 32-unit chunk
-constexpr int C16_AT = C16_HID + FF_CHUNKS * 1024;                   // 2 x [attention record 17 KiB | c_t row 1 KiB | b2 1 KiB]
-constexpr int C16_AT_BYTES = asms_bytes(DFX_PREC_BF16) + 2048;
-constexpr int C16_HS = C16_AT + 2 * C16_AT_BYTES;                    // home of h: [tile c (8)][lane] float4 = 8 KiB
-constexpr int C16_CONST = C16_HS + 8 * 1024;                         // chain-invariant operands (as k_denoise_coop): W_in x-columns | pre_norm | W_out | cpart
-constexpr int C16_Z = C16_CONST + 7 * 1024;                          // noise z[3][16] | posterior table row at +512
-constexpr int C16_PS = C16_Z + 1024;                                 // per-point chain state: 13 x 16 floats
-constexpr int C16_TOTAL = C16_PS + 1024;
-static_assert(C16_TOTAL <= 160 * 1024, "LDS budget of the 16-point co-operative kernel");
-static_assert(FF_CHUNKS == 2 * C16_NW && INNER == 128, "two chunks per wavefront, eight accumulator tiles");
-
-__global__ void __launch_bounds__(C16_NW * 64, 2) k_denoise_coop16(const KParams p) {
-  constexpr int PREC = DFX_PREC_BF16;
-  constexpr int TSTRIDE = tile_units(PREC) * 64, AREC = asms_bytes(PREC) / 16;
-  constexpr int TILE_B = TSTRIDE * 16;   // bytes per 32 x 32 tile
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int j = lane & 15, g = lane >> 4;
-  const long long g0 = (long long)blockIdx.x * C16_PTS;
-  const int s = __builtin_amdgcn_readfirstlane((int)(g0 / p.N));
-  const int n = (int)(g0 - (long long)s * p.N) + j;
-  const int depth = p.d.depth;
-  const bool w0 = wave == 0;
-  float *ps_lds = reinterpret_cast<float *>(pipe_smem + C16_PS);
-  float *s_hs = reinterpret_cast<float *>(pipe_smem + C16_HS);
-  uint4 *s_xn = reinterpret_cast<uint4 *>(pipe_smem + C16_XN);
-  uint4 *s_hid = reinterpret_cast<uint4 *>(pipe_smem + C16_HID);
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)pipe_smem);
-  const unsigned voff = lane * 16;
-  // byte offset of this lane's 8-byte piece inside unit 0 of a 32 x 32 tile, for the tile's rows 0..15 (half 0) / 16..31 (half 1); unit 1: + 1024
-  const unsigned aoff0 = (unsigned)((j + 32 * (g & 1)) * 16 + 8 * (g >> 1)), aoff1 = aoff0 + 16 * 16;
-  // index of this lane's four consecutive entries of a per-channel vector in cvec order, for accumulator tile c (channels 16 c + 4 g + 0..3)
-  auto cv = [&](int c) { return (g & 1) * 64 + (c >> 1) * 16 + (c & 1) * 8 + (g >> 1) * 4; };
-  // One 16 x 32 A fragment out of a 32 x 32 tile = two 8-byte pieces (elements 4 q .. 4 q + 3 of units 0 and 1, q = g >> 1).  From global memory every
-  // lane loads ONE whole 16-byte unit instead — groups 0 / 1 unit 0, groups 2 / 3 unit 1 of the same row — and the two half-waves trade the piece the other
-  // one needs with two v_permlane32_swap: the same bytes in half the load instructions (the first version issued 96 eight-byte loads per wavefront and block;
-  // the CU's address path, shared by its eight wavefronts, took 8 k cycles per block for them).  The address space is spelled out through an integer:
-  // behind pin_ptr's round trip hipcc would emit flat loads, which count against lgkmcnt as well.
-  const unsigned goff0 = (unsigned)((g >> 1) * 1024 + (j + 32 * (g & 1)) * 16), goff1 = goff0 + 16 * 16;
-  auto gather = [&](const char *tile, unsigned goff) -> uint4 {          // goff = goff0 (rows 0..15 of the tile) or goff1 (rows 16..31); the RAW unit: frag_fix() before use
-    typedef const __attribute__((address_space(1))) unsigned long long *gp64;
-    const gp64 q = (gp64)(unsigned long long)(uintptr_t)(tile + goff);
-    const unsigned long long lo = q[0], hi = q[1];
-    return make_uint4((unsigned)lo, (unsigned)(lo >> 32), (unsigned)hi, (unsigned)(hi >> 32));
-  };
-  auto frag_fix = [](uint4 &f) {   // (applied where the fragment is consumed: at the load site it would wait for the data)
-    const auto r0 = __builtin_amdgcn_permlane32_swap(f.x, f.z, false, false), r1 = __builtin_amdgcn_permlane32_swap(f.y, f.w, false, false);   // x, y of the upper half-wave <-> z, w of the lower
-    f = make_uint4(r0[0], r1[0], r0[1], r1[1]);
-  };
-  auto gather_lds = [&](const unsigned char *tile, unsigned aoff) -> uint4 {   // from the attention record's LDS copy
-    typedef const __attribute__((address_space(3))) unsigned long long *lp64;
-    const uintptr_t la = (uintptr_t)(const __attribute__((address_space(3))) unsigned char *)tile + aoff;
-    const unsigned long long a = *(lp64)la, b = *(lp64)(la + 1024);
-    return make_uint4((unsigned)a, (unsigned)(a >> 32), (unsigned)b, (unsigned)(b >> 32));
-  };
-  auto mfma_bf = [](const uint4 &a, const uint4 &b, v4f c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, a), __builtin_bit_cast(v8bf, b), c, 0, 0, 0);
-  };
-  auto mfma_h = [](const uint4 &a, const uint4 &b, v4f c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(v8h, a), __builtin_bit_cast(v8h, b), c, 0, 0, 0);
-  };
-  auto xg = [](float v) {   // sum over the four lane groups of a point
-    v += __shfl_xor(v, 16, 64);
-    return v + __shfl_xor(v, 32, 64);
-  };
-  auto hs_ptr = [&](int c) -> v4f * { return reinterpret_cast<v4f *>(s_hs + (c * 64 + lane) * 4); };
-  // LayerNorm statistics of h (32 values in-lane + the other three groups of the point): single pass like ln_stats_fast
-  auto ln16 = [&](const v4f (&h)[8], float &mean, float &rstd) {
-    float st = 0.f, qt = 0.f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) st += h[c][r], qt = fmaf(h[c][r], h[c][r], qt);
-    st = xg(st), qt = xg(qt);
-    mean = st * (1.0f / 128.0f);
-    rstd = __builtin_amdgcn_rsqf(fmaxf(fmaf(-mean, mean, qt * (1.0f / 128.0f)), 0.f) + 1e-5f);
-  };
-  // normalised (affine-free) h: the bf16 B fragment of k-step k
-  auto ln_frag = [&](const v4f (&h)[8], int k, float rstd, float nmr) -> uint4 {
-    v8f t;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) t[e] = fmaf(h[2 * k + (e >> 2)][e & 3], rstd, nmr);
-    return __builtin_bit_cast(uint4, __builtin_convertvector(t, v8bf));
-  };
-
-  unsigned vmask = 0;
-  if (w0) {
-    PointState ps0;
-    ps0.live = g == 0;   // the four groups of a point hold the same state; group 0 does the stores (point_init / step_epilogue test `live` and the half-wave)
-    point_init(p, ps0, s, n, ((unsigned long long)p.shape0 + (unsigned)s) * (unsigned)p.N + (unsigned)n, vmask);
-    pstate_store(ps_lds, j, C16_PTS, ps0, true);
-  }
-  {   // chain-invariant small operands -> LDS
-    float4 *c_winx = reinterpret_cast<float4 *>(pipe_smem + C16_CONST);
-    float2 *c_pregb = reinterpret_cast<float2 *>(pipe_smem + C16_CONST + 2048);
-    float4 *c_wout = reinterpret_cast<float4 *>(pipe_smem + C16_CONST + 3072);
-    float *c_cp = reinterpret_cast<float *>(pipe_smem + C16_CONST + 5120);
-    const int tid = threadIdx.x;
-    if (tid < 128) c_winx[tid] = p.d.win_x[tid], c_pregb[tid] = p.d.pre_gb[tid], c_wout[tid] = p.d.wout[tid];
-    c_cp[tid] = p.cpart[(size_t)s * NCLS * INNER + tid];
-    __syncthreads();
-  }
-  const float4 *winx = reinterpret_cast<const float4 *>(pipe_smem + C16_CONST);
-  const float2 *pregb = reinterpret_cast<const float2 *>(pipe_smem + C16_CONST + 2048);
-  const float4 *wout = reinterpret_cast<const float4 *>(pipe_smem + C16_CONST + 3072);
-  const uint4 *asms_s = p.as_ms + (size_t)s * depth * AREC;
-
-  // proj_in + pre_norm of the chain state -> h's LDS home (wave 0)
-  auto enter_step = [&](const PointState &ps) {
-    v4f h[8];
-    const float *cp = reinterpret_cast<const float *>(pipe_smem + C16_CONST + 5120) + ps.sg * INNER;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const v4f cpv = *reinterpret_cast<const v4f *>(cp + cv(c));
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float4 w = winx[cv(c) + r];
-        h[c][r] = fmaf(w.z, ps.x[2], fmaf(w.y, ps.x[1], fmaf(w.x, ps.x[0], cpv[r])));
-      }
-    }
-    float mean, rstd;
-    ln16(h, mean, rstd);
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      v4f o;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float2 gb = pregb[cv(c) + r];
-        o[r] = fmaf((h[c][r] - mean) * rstd, gb.x, gb.y);
-      }
-      *hs_ptr(c) = o;
-    }
-  };
-  // the operands of block b at timestep t -> half `buf` of the double buffer: 17 KiB record | c_t row | b2 (19 pieces over waves 1..7)
-  auto fetch_record = [&](int b, int t, int buf) {
-    const BlockPack bp = block_pack(p, b);
-    constexpr int NA = asms_bytes(PREC) / 1024;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const int k = i * (C16_NW - 1) + wave - 1;
-      const unsigned dst = lds0 + C16_AT + buf * C16_AT_BYTES + k * 1024;
-      if (k < NA) dma1k_pinned(reinterpret_cast<const char *>(asms_s + (size_t)b * AREC) + k * 1024, voff, dst);
-      else if (k == NA) dma1k_pinned(reinterpret_cast<const char *>(bp.ct + (size_t)t * CT_ROW), voff, dst);
-      else if (k == NA + 1) dma1k_pinned(reinterpret_cast<const char *>(bp.bconst + BCONST_B2_OFF), voff, dst);
-    }
-  };
-
-  if (w0) {
-    PointState ps;
-    pstate_load(ps_lds, j, C16_PTS, ps, false);
-    enter_step(ps);
-  } else {
-    fetch_record(0, step_t(p, 0, s), 0);
-  }
-  uint4 R[32];   // GEMM1 fragments of the wave's two chunks (16 each); phase G: the wave's sixteen W2 fragments in R[0..15]
-#ifdef DFX_TRACE   // phase stamps of wave 0 (row 0 of the trace buffer) and of wave 5 (row 1) of workgroup 0
-  Tracer tr{(p.trace != nullptr && blockIdx.x == 0 && (wave == 0 || wave == 5)) ? p.trace + (size_t)(wave ? 1 : 0) * p.trace_cap : nullptr, p.trace_cap, 0};
-#else
-  Tracer tr;
-#endif
-  int seq = 0;
-  for (int step = 0; step < p.nsteps; ++step) {
-    const int t = step_t(p, step, s);
-    for (int b = 0; b < depth; ++b, ++seq) {
-      const BlockPack bp = block_pack(p, b);
-      const unsigned char *at = pipe_smem + C16_AT + (seq & 1) * C16_AT_BYTES;
-      if (!w0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this block's record (requested a block ago) has landed
-      // GEMM1 fragments of chunks `wave` (R[0..15]) and `wave + 8` (R[16..31]): [a | g] x 4 k-steps x 2 halves, requested by every wavefront in front of
-      // barrier 0.  (The CU's address path takes ~16 cycles per wavefront-wide load and is shared by the eight wavefronts: 256 loads = 4 k cycles at the top
-      // of every block.  Requesting waves 1..7's behind the barrier, under wave 0's phase A, was tried: phase A then takes 12.6 k cycles instead of 3.8 k —
-      // its LDS reads and the returning load data share a path — 56 ms per chain instead of 31.8; profiles/r05_small_batch_sweep.txt.)
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const char *ck = pin_ptr(reinterpret_cast<const char *>(bp.chunks + (size_t)(r * C16_NW + wave) * CHUNK_TILES * TSTRIDE));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          R[16 * r + 4 * k + 0] = gather(ck + (0 + k) * TILE_B, goff0), R[16 * r + 4 * k + 1] = gather(ck + (4 + k) * TILE_B, goff0);
-          R[16 * r + 4 * k + 2] = gather(ck + (0 + k) * TILE_B, goff1), R[16 * r + 4 * k + 3] = gather(ck + (4 + k) * TILE_B, goff1);
-        }
-      }
-      tr.stamp(10);
-      __syncthreads();   // 0: this block's record is in LDS; h's home holds the previous block's result
-      tr.stamp(11);
-      if (w0) {          // ---- phase A
-        v4f h[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) h[c] = *hs_ptr(c);
-        // sim = A_s LN2(h) + sbias: rows 16 rt + 4 g + r = key r of head 4 rt + g; the B fragments are consumed as they are made
-        const float *sb = reinterpret_cast<const float *>(at + 8 * TILE_B);
-        v4f sim[2];
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt) sim[rt] = *reinterpret_cast<const v4f *>(sb + (g & 1) * 16 + 8 * rt + 4 * (g >> 1));
-        {
-          float mean, rstd;
-          ln16(h, mean, rstd);
-          const float nmr = -mean * rstd;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const uint4 xk = ln_frag(h, k, rstd, nmr);
-            sim[0] = mfma_bf(gather_lds(at + k * TILE_B, aoff0), xk, sim[0]);
-            sim[1] = mfma_bf(gather_lds(at + k * TILE_B, aoff1), xk, sim[1]);
-          }
-        }
-        v8f pf;
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt) {   // masked softmax over the four keys (attention.py:195-198), in-lane
-          float sj[4], e[4], sum = 0.f;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) sj[q] = (vmask >> q) & 1u ? sim[rt][q] : -3.402823466e38f;
-          const float m = fmaxf(fmaxf(sj[0], sj[1]), fmaxf(sj[2], sj[3]));
-#pragma unroll
-          for (int q = 0; q < 4; ++q) e[q] = __expf(sj[q] - m), sum += e[q];
-          const float inv = __builtin_amdgcn_rcpf(sum);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) pf[4 * rt + q] = e[q] * inv;
-        }
-        const uint4 pa = __builtin_bit_cast(uint4, __builtin_convertvector(pf, v8bf));
-        const float *ct = reinterpret_cast<const float *>(at + asms_bytes(PREC));
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {   // h += M_s P + c_t
-          h[c] = mfma_bf(gather_lds(at + (4 + (c >> 1)) * TILE_B, (c & 1) ? aoff1 : aoff0), pa, h[c]);
-          const v4f cc = *reinterpret_cast<const v4f *>(ct + cv(c));
-          h[c] += cc;
-        }
-#pragma unroll
-        for (int c = 0; c < 8; ++c) *hs_ptr(c) = h[c];
-        {
-          float mean, rstd;
-          ln16(h, mean, rstd);
-          const float nmr = -mean * rstd;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            uint4 xk = ln_frag(h, k, rstd, nmr);
-            if (k == 3 && p.d.w1_fold && g == 3) xk.w = (xk.w & 0x0000ffffu) | 0x3f800000u;   // channel 127 = tile 7, row 15: element 7 of k-step 3 carries the constant 1 (bias_slot_one)
-            s_xn[k * 64 + lane] = xk;
-          }
-        }
-      } else if (wave == C16_NW - 1 && b == depth - 1 && p.mode != MODE_EPS) {   // the step's noise and posterior coefficients, ready for wave 0's epilogue
-        float z[3];
-        if (p.noise) {
-#pragma unroll
-          for (int i = 0; i < 3; ++i) z[i] = p.noise[(((size_t)step * p.B + s) * 3 + i) * p.N + n];
-        } else {
-          philox_normal3(p.seed, ((unsigned long long)p.shape0 + (unsigned)s) * (unsigned)p.N + (unsigned)n, (unsigned)t, 0u, z);
-        }
-        float *s_z = reinterpret_cast<float *>(pipe_smem + C16_Z);
-        if (g == 0) s_z[j] = z[0], s_z[16 + j] = z[1], s_z[32 + j] = z[2];
-        if (lane < 8) s_z[128 + lane] = p.d.tab[(size_t)t * 8 + lane];
-      }
-      tr.stamp(12);
-      __syncthreads();   // 1: xn3 of this block and h are in LDS
-      tr.stamp(13);
-      // ---- phase H.  The next block's record travels meanwhile (into the other half of the double buffer: nobody reads that half before barrier 0)
-      if (!w0) {
-        const int nb = b + 1 < depth ? b + 1 : 0, nstep = b + 1 < depth ? step : step + 1;
-        if (nstep < p.nsteps) fetch_record(nb, step_t(p, nstep, s), (seq + 1) & 1);
-      }
-      uint4 xq[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) xq[k] = s_xn[k * 64 + lane];
-      const float *b1t = bp.bconst;   // [u][part][hf][16] in the 32-wide register order (read only by engines without the W1 bias fold)
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const int u = r * C16_NW + wave;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) frag_fix(R[16 * r + i]);
-        v4f a[2], gg[2];
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-          if (p.d.w1_fold) {
-            a[hh] = v4f{0.f, 0.f, 0.f, 0.f}, gg[hh] = a[hh];
-          } else {   // unit 16 hh + 4 g + q of the chunk = entry (g & 1) * 16 + 8 hh + 4 (g >> 1) + q of the [hf][16] table
-            a[hh] = *reinterpret_cast<const v4f *>(b1t + u * 64 + (g & 1) * 16 + 8 * hh + 4 * (g >> 1));
-            gg[hh] = *reinterpret_cast<const v4f *>(b1t + u * 64 + 32 + (g & 1) * 16 + 8 * hh + 4 * (g >> 1));
-          }
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            a[hh] = mfma_bf(R[16 * r + 4 * k + 2 * hh + 0], xq[k], a[hh]);
-            gg[hh] = mfma_bf(R[16 * r + 4 * k + 2 * hh + 1], xq[k], gg[hh]);
-          }
-        }
-        if (r == 0) {   // round 0's registers are free: this wave's W2 fragments — accumulator tile `wave`, all sixteen chunks (W2 of chunk c sits in FF record c + FF_SKEW, tiles 8..11)
-          const char *w2 = pin_ptr(reinterpret_cast<const char *>(bp.chunks + (size_t)FF_SKEW * CHUNK_TILES * TSTRIDE) + (8 + (wave >> 1)) * TILE_B);
-          const unsigned ao = (wave & 1) ? goff1 : goff0;
-#pragma unroll
-          for (int c = 0; c < FF_CHUNKS; ++c) R[c] = gather(w2 + (size_t)c * CHUNK_TILES * TILE_B, ao);
-        }
-        // packed-fp16 GELU on the eight values of the two halves (gelu16_f16_math on four pairs): hid = a gelu(g) with the pack's scales
-        h2 ap[4], gp[4], y[4], z[4], rr[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) gp[i] = pk_f16(gg[i >> 1][2 * (i & 1)], gg[i >> 1][2 * (i & 1) + 1]), ap[i] = pk_f16(a[i >> 1][2 * (i & 1)], a[i >> 1][2 * (i & 1) + 1]);
-#define DFX_ST4(expr) _Pragma("unroll") for (int i = 0; i < 4; ++i) { expr; }
-        DFX_ST4(z[i] = __builtin_elementwise_fma(gp[i], gp[i], h2c(-1.62f)));
-        DFX_ST4(y[i] = ap[i] * gp[i]);
-        DFX_ST4(z[i] = __builtin_elementwise_min(z[i], h2c(1.62f)));
-        DFX_ST4(rr[i] = __builtin_elementwise_fma(z[i], h2c(-0.0011402554f), h2c(0.0057853916f)));
-        DFX_ST4(rr[i] = __builtin_elementwise_fma(rr[i], z[i], h2c(-0.0158536041f)));
-        DFX_ST4(rr[i] = __builtin_elementwise_fma(rr[i], z[i], h2c(0.0409006897f)));
-        DFX_ST4(rr[i] = __builtin_elementwise_fma(rr[i], z[i], h2c(-0.1098130657f)));
-        DFX_ST4(rr[i] = __builtin_elementwise_fma(rr[i], z[i], h2c(0.3885767652f)));
-        DFX_ST4(asm("v_pk_fma_f16 %0, %1, %2, 0.5 op_sel_hi:[1,1,0] clamp" : "=v"(z[i]) : "v"(gp[i]), "v"(rr[i])));
-        DFX_ST4(y[i] = y[i] * z[i]);
-#undef DFX_ST4
-        s_hid[u * 64 + lane] = make_uint4(__builtin_bit_cast(unsigned, y[0]), __builtin_bit_cast(unsigned, y[1]), __builtin_bit_cast(unsigned, y[2]),
-                                          __builtin_bit_cast(unsigned, y[3]));
-      }
-      tr.stamp(14);
-      __syncthreads();   // 2: hid of all chunks is in LDS
-      tr.stamp(15);
-      // ---- phase G: wave w accumulates tile w of h over the sixteen chunks, + b2
-      {
-        v4f ht = *hs_ptr(wave);
-#pragma unroll
-        for (int u = 0; u < FF_CHUNKS; ++u) frag_fix(R[u]);
-#pragma unroll
-        for (int u = 0; u < FF_CHUNKS; ++u) ht = mfma_h(R[u], s_hid[u * 64 + lane], ht);
-        const float *b2 = reinterpret_cast<const float *>(at + asms_bytes(PREC) + 1024);
-        const v4f bb = *reinterpret_cast<const v4f *>(b2 + cv(wave));
-        *hs_ptr(wave) = ht + bb;
-      }
-    }
-    tr.stamp(16);
-    __syncthreads();   // the last block's tiles are in h's home
-    tr.stamp(17);
-    if (w0) {
-      v4f h[8];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) h[c] = *hs_ptr(c);
-      float mean, rstd;
-      ln16(h, mean, rstd);
-      const float nmr = -mean * rstd;
-      float e0 = 0.f, e1 = 0.f, e2 = 0.f;
-#pragma unroll
-      for (int c = 0; c < 8; ++c)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float4 w = wout[cv(c) + r];
-          const float v = fmaf(h[c][r], rstd, nmr);
-          e0 = fmaf(w.x, v, e0), e1 = fmaf(w.y, v, e1), e2 = fmaf(w.z, v, e2);
-        }
-      const float eps[3] = {xg(e0) + p.d.bout[0], xg(e1) + p.d.bout[1], xg(e2) + p.d.bout[2]};
-      PointState ps;
-      ps.s = s, ps.n = n, ps.gid = 0, ps.live = g == 0;
-      pstate_load(ps_lds, j, C16_PTS, ps, true);
-      const float *s_z = reinterpret_cast<const float *>(pipe_smem + C16_Z);
-      const float zr[3] = {s_z[j], s_z[16 + j], s_z[32 + j]};
-      const bool zok = p.mode != MODE_EPS;
-      tr.stamp(18);
-      if (step_epilogue(p, ps, eps, step, t, zok ? zr : nullptr, zok ? s_z + 128 : nullptr)) break;
-      tr.stamp(19);
-      pstate_store(ps_lds, j, C16_PTS, ps, false);
-      if (step + 1 < p.nsteps) enter_step(ps);
+      if (step + 1 < p.nsteps) coop_enter_step(ps, home, cc, lane);
       tr.stamp(20);
     }
   }
@@ -2681,16 +1953,16 @@ constexpr int C2_HID = C2_XN + 2 * 8 * 1024;                       // 2 tiles x 
 constexpr int C2_BC = C2_HID + 2 * FF_CHUNKS * 2048;               // 2 x block constants, by block parity
 constexpr int C2_AT = C2_BC + 2 * BCONST_BYTES;                    // attention record + c_t row (one shape per workgroup)
 constexpr int C2_HS = C2_AT + asms_bytes(DFX_PREC_BF16) + 1024;    // 2 tiles x 16 KiB: h's home
-constexpr int C2_CONST = C2_HS + 2 * 16 * 1024;                    // chain-invariant operands (as k_denoise_coop)
-constexpr int C2_Z = C2_CONST + 7 * 1024;                          // 2 tiles x (noise z[3][32] | posterior table row at +512)
+constexpr int C2_CONST = C2_HS + 2 * 16 * 1024;                    // chain-invariant operands (CC_*)
+constexpr int C2_Z = C2_CONST + CC_BYTES;                          // 2 tiles x (noise z[3][32] | posterior table row at +512)
 constexpr int C2_PS = C2_Z + 2 * 1024;                             // 2 tiles x per-point chain state
 constexpr int C2_TOTAL = C2_PS + 2 * 2048;
 static_assert(C2_TOTAL <= 160 * 1024, "LDS budget of the two-tile co-operative kernel");
 
 __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop2(const KParams p) {
-  constexpr int PREC = DFX_PREC_BF16;
-  constexpr int TSTRIDE = tile_units(PREC) * 64, AREC = asms_bytes(PREC) / 16;
+  constexpr int AREC = COOP_AREC;
   uint4 *s_at = reinterpret_cast<uint4 *>(pipe_smem + C2_AT);
+  unsigned char *cc = pipe_smem + C2_CONST;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int hf = lane >> 5, pj = lane & 31;
@@ -2702,72 +1974,27 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop2(const KParams
   const int gt = wave >> 2, ct = wave & 3;     // phase G: output tile ct of tile gt
   auto xn_base = [&](int t) { return reinterpret_cast<uint4 (*)[64]>(pipe_smem + C2_XN + t * 8 * 1024); };
   auto hid_base = [&](int t) { return reinterpret_cast<uint4 (*)[2][64]>(pipe_smem + C2_HID + t * FF_CHUNKS * 2048); };
-  auto hs_ptr = [&](int t, int c, int q) -> v4f * { return reinterpret_cast<v4f *>(pipe_smem + C2_HS + t * 16 * 1024) + (c * 4 + q) * 64 + lane; };
+  auto home = [&](int t) { return reinterpret_cast<v4f *>(pipe_smem + C2_HS + t * 16 * 1024) + lane; };
+  auto z_base = [&](int t) { return reinterpret_cast<float *>(pipe_smem + C2_Z + t * 1024); };
   float *ps_lds = reinterpret_cast<float *>(pipe_smem + C2_PS + (wave & 1) * 2048);   // (waves 0, 1)
+  const int n_a = nbase + wave * 32 + pj;                                             // (waves 0, 1: this lane's point)
   unsigned vmask = 0;
-  if (arole) {
-    PointState ps0;
-    const int n = nbase + wave * 32 + pj;
-    point_init(p, ps0, s, n, ((unsigned long long)p.shape0 + (unsigned)s) * (unsigned)p.N + (unsigned)n, vmask);
-    pstate_store(ps_lds, pj, 32, ps0, true);
-  }
+  if (arole) coop_point_init(p, ps_lds, s, n_a, pj, vmask);
   const uint4 *asms_s = p.as_ms + (size_t)s * depth * AREC;
-  {   // chain-invariant small operands -> LDS
-    float4 *c_winx = reinterpret_cast<float4 *>(pipe_smem + C2_CONST);
-    float2 *c_pregb = reinterpret_cast<float2 *>(pipe_smem + C2_CONST + 2048);
-    float4 *c_wout = reinterpret_cast<float4 *>(pipe_smem + C2_CONST + 3072);
-    float *c_cp = reinterpret_cast<float *>(pipe_smem + C2_CONST + 5120);
-    const int tid = threadIdx.x;
-    if (tid < 128) c_winx[tid] = p.d.win_x[tid], c_pregb[tid] = p.d.pre_gb[tid], c_wout[tid] = p.d.wout[tid];
-    c_cp[tid] = p.cpart[(size_t)s * NCLS * INNER + tid];
-    __syncthreads();
-  }
-  const float4 *winx = reinterpret_cast<const float4 *>(pipe_smem + C2_CONST) + hf * 64;
-  const float2 *pregb = reinterpret_cast<const float2 *>(pipe_smem + C2_CONST + 2048) + hf * 64;
-  const float4 *wout = reinterpret_cast<const float4 *>(pipe_smem + C2_CONST + 3072) + hf * 64;
+  coop_stage_consts(cc, p, s);
+  __syncthreads();
   const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)pipe_smem);
   const unsigned voff = lane * 16;
 
   uint4 R[32];   // phase H: GEMM1 fragments of round 0 (R[0..15]) / round 1 (R[16..31]); phase G: W2 fragments of the own output tile, chunk u in R[2 u], R[2 u + 1]
-  auto load_w1 = [&](int base, const uint4 *chunks, int u) {
-    const uint4 *ck = reinterpret_cast<const uint4 *>(pin_ptr(reinterpret_cast<const char *>(chunks + (size_t)u * CHUNK_TILES * TSTRIDE))) + lane;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      R[base + 4 * c + 0] = ck[(0 + c) * TSTRIDE], R[base + 4 * c + 1] = ck[(0 + c) * TSTRIDE + 64];
-      R[base + 4 * c + 2] = ck[(4 + c) * TSTRIDE], R[base + 4 * c + 3] = ck[(4 + c) * TSTRIDE + 64];
-    }
-  };
-  auto load_w2 = [&](int first, const uint4 *chunks) {   // W2 of chunks first .. first + 7, output tile ct (W2 of chunk c sits in FF record c + FF_SKEW, tiles 8..11)
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const uint4 *ck = reinterpret_cast<const uint4 *>(pin_ptr(reinterpret_cast<const char *>(chunks + (size_t)(first + c + FF_SKEW) * CHUNK_TILES * TSTRIDE + (8 + ct) * TSTRIDE))) + lane;
-      R[2 * (first + c)] = ck[0], R[2 * (first + c) + 1] = ck[64];
-    }
-  };
   // attention record, c_t row and block constants of block b at time t -> LDS: 23 pieces over the 8 waves
   auto stage_block = [&](int b, int t, int parity) {
-    const BlockPack bq = block_pack(p, b);
-    constexpr int NA = asms_bytes(PREC) / 1024, NB = BCONST_BYTES / 1024;
-#pragma unroll
-    for (int i = 0; i < (NA + 1 + NB + COOP_NW - 1) / COOP_NW; ++i) {
-      const int k = i * COOP_NW + wave;
-      if (k < NA) dma1k_pinned(reinterpret_cast<const char *>(asms_s + (size_t)b * AREC) + k * 1024, voff, lds0 + C2_AT + k * 1024);
-      else if (k == NA) dma1k_pinned(reinterpret_cast<const char *>(bq.ct + (size_t)t * CT_ROW), voff, lds0 + C2_AT + NA * 1024);
-      else if (k < NA + 1 + NB) dma1k_pinned(reinterpret_cast<const char *>(bq.bconst) + (k - NA - 1) * 1024, voff, lds0 + C2_BC + parity * BCONST_BYTES + (k - NA - 1) * 1024);
-    }
-  };
-  auto enter_step = [&](const PointState &ps) {   // proj_in + pre_norm of the chain state -> h's home (waves 0, 1)
-    v16f h[4];
-    proj_in_prenorm_tiles(h, ps.x, reinterpret_cast<const float *>(pipe_smem + C2_CONST + 5120) + ps.sg * INNER + hf * 64, winx, pregb);
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) *hs_ptr(wave, c, q) = v4f{h[c][4 * q], h[c][4 * q + 1], h[c][4 * q + 2], h[c][4 * q + 3]};
+    coop_stage_block<COOP_NW>(block_pack(p, b), asms_s + (size_t)b * AREC, t, wave, voff, lds0 + C2_AT, lds0 + C2_BC + parity * BCONST_BYTES);
   };
   if (arole) {
     PointState ps;
     pstate_load(ps_lds, pj, 32, ps, false);
-    enter_step(ps);
+    coop_enter_step(ps, home(wave), cc, lane);
   }
   int seq = 0;
   if (p.nsteps > 0) stage_block(0, step_t(p, 0, s), 0);
@@ -2777,88 +2004,41 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop2(const KParams
       const BlockPack bp = block_pack(p, b);
       float *s_bc = reinterpret_cast<float *>(pipe_smem + C2_BC + (seq & 1) * BCONST_BYTES);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the block's operands (requested a phase G ago)
-      load_w1(0, bp.chunks, wave);   // round 0: in flight through phase A
+      coop_load_w1(R, 0, bp.chunks, wave, lane);   // round 0: in flight through phase A
       __syncthreads();   // 0: attention record, c_t, block constants of this block are in LDS; h's homes hold the previous block's result
       if (arole) {       // ---- phase A: wave w on tile w
-        v16f h[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const v4f x = *hs_ptr(wave, c, q);
-            h[c][4 * q] = x[0], h[c][4 * q + 1] = x[1], h[c][4 * q + 2] = x[2], h[c][4 * q + 3] = x[3];
-          }
-        const uint4 *rec = s_at + lane;
-        attention<PREC>(h, rec, reinterpret_cast<const float *>(s_at + 8 * TSTRIDE) + hf * 16, reinterpret_cast<const float *>(s_at + AREC) + hf * 64, vmask);
-        Act<PREC> xo[4];
-        ln_to_act<PREC>(h, xo);
-        bias_slot_one(xo, hf);
-        uint4 (*s_xn)[64] = xn_base(wave);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) s_xn[2 * c][lane] = __builtin_bit_cast(uint4, xo[c].f[0]), s_xn[2 * c + 1][lane] = __builtin_bit_cast(uint4, xo[c].f[1]);
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) *hs_ptr(wave, c, q) = v4f{h[c][4 * q], h[c][4 * q + 1], h[c][4 * q + 2], h[c][4 * q + 3]};
+        coop_phase_a(home(wave), s_at, xn_base(wave), lane, vmask);
       } else if (wave >= COOP_NW - 2 && b == depth - 1 && p.mode != MODE_EPS) {   // the step's noise and posterior coefficients: wave 6 for tile 0, wave 7 for tile 1
-        const int tz = wave - (COOP_NW - 2), n = nbase + tz * 32 + pj;
-        float z[3];
-        if (p.noise) {
-#pragma unroll
-          for (int i = 0; i < 3; ++i) z[i] = p.noise[(((size_t)step * p.B + s) * 3 + i) * p.N + n];
-        } else {
-          philox_normal3(p.seed, ((unsigned long long)p.shape0 + (unsigned)s) * (unsigned)p.N + (unsigned)n, (unsigned)t, 0u, z);
-        }
-        float *s_z = reinterpret_cast<float *>(pipe_smem + C2_Z + tz * 1024);
-        if (hf == 0) s_z[pj] = z[0], s_z[32 + pj] = z[1], s_z[64 + pj] = z[2];
-        if (lane < 8) s_z[128 + lane] = p.d.tab[(size_t)t * 8 + lane];
+        const int tz = wave - (COOP_NW - 2);
+        coop_draw_noise(p, z_base(tz), step, t, s, nbase + tz * 32 + pj, lane);
       }
       __syncthreads();   // 1: xn3 of both tiles and h are in LDS
       // ---- phase H: every wave, chunks `wave` and `wave + 8`, both tiles per fragment set
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
         const int u = r * COOP_NW + wave, cur = r * 16;
-        if (r == 0) load_w1(16, bp.chunks, u + COOP_NW);
-        else load_w2(0, bp.chunks);   // round 0's registers are free: W2 of chunks 0..7
+        if (r == 0) coop_load_w1(R, 16, bp.chunks, u + COOP_NW, lane);
+        else coop_load_w2(R, 0, bp.chunks, ct, lane);   // round 0's registers are free: W2 of chunks 0..7
 #pragma unroll
         for (int tl = 0; tl < 2; ++tl) {
-          uint4 (*s_xn)[64] = xn_base(tl);
-          v16f a = zero16(), g = zero16();   // b1' rides on the constant-one K slot (bias_slot_one)
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            const v8bf x0 = __builtin_bit_cast(v8bf, s_xn[2 * c][lane]), x1 = __builtin_bit_cast(v8bf, s_xn[2 * c + 1][lane]);
-            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(R[cur + 4 * c + 0]), x0, a, 0, 0, 0);
-            g = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(R[cur + 4 * c + 2]), x0, g, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(R[cur + 4 * c + 1]), x1, a, 0, 0, 0);
-            g = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(R[cur + 4 * c + 3]), x1, g, 0, 0, 0);
-          }
+          v16f a, g;
+          coop_gemm1(a, g, R, cur, xn_base(tl), lane);
           if (r == 1 && tl == 1) {   // round 1's fragments are done with: W2 of chunks 8..15 travels under the last GELU
             __builtin_amdgcn_sched_barrier(0);
-            load_w2(8, bp.chunks);
+            coop_load_w2(R, 8, bp.chunks, ct, lane);
             __builtin_amdgcn_sched_barrier(0);
           }
-          h2 aa[8], gg[8];
-          HidAct hid;
-          gelu16_f16_cvt(a, g, aa, gg);
-          gelu16_f16_math(aa, gg, hid);
-          uint4 (*s_hid)[2][64] = hid_base(tl);
-          s_hid[u][0][lane] = hid.f[0], s_hid[u][1][lane] = hid.f[1];
+          coop_gelu_store(a, g, hid_base(tl)[u], lane);
         }
       }
       __syncthreads();   // 2: hid of all chunks of both tiles is in LDS; nobody reads the attention record any more
-      {                  // the next block's operands (next step's c_t row behind the last block)
-        const int nb = b + 1 < depth ? b + 1 : 0;
-        if (b + 1 < depth) stage_block(nb, t, (seq + 1) & 1);
-        else if (step + 1 < p.nsteps) stage_block(0, step_t(p, step + 1, s), (seq + 1) & 1);
-      }
+      // the next block's operands (next step's c_t row behind the last block)
+      if (b + 1 < depth) stage_block(b + 1, t, (seq + 1) & 1);
+      else if (step + 1 < p.nsteps) stage_block(0, step_t(p, step + 1, s), (seq + 1) & 1);
       // ---- phase G: wave (gt, ct) accumulates output tile ct of tile gt, chunk after chunk (the accumulation order of the pipelined kernel), + b2
       {
         v16f ht;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const v4f x = *hs_ptr(gt, ct, q);
-          ht[4 * q] = x[0], ht[4 * q + 1] = x[1], ht[4 * q + 2] = x[2], ht[4 * q + 3] = x[3];
-        }
+        hs_load(ht, home(gt) + ct * 256);
         uint4 hq[4][2];   // hid fragments: a ring three chunks deep, fenced per chunk (see k_denoise_coop)
         unsigned hoff = C2_HID + gt * FF_CHUNKS * 2048 + lane * 16;
         asm volatile("" : "+v"(hoff));
@@ -2873,35 +2053,17 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop2(const KParams
           ht = mma_hid(R[2 * u + 1], hq[u & 3][1], ht);
           __builtin_amdgcn_sched_barrier(0);
         }
-        const float *b2 = s_bc + BCONST_B2_OFF + hf * 64 + ct * 16;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const v4f bb = *reinterpret_cast<const v4f *>(b2 + 4 * q);
-          *hs_ptr(gt, ct, q) = v4f{ht[4 * q] + bb[0], ht[4 * q + 1] + bb[1], ht[4 * q + 2] + bb[2], ht[4 * q + 3] + bb[3]};
-        }
+        hs_store_plus(home(gt) + ct * 256, ht, s_bc + BCONST_B2_OFF + hf * 64 + ct * 16);
       }
     }
     __syncthreads();   // the last block's tiles are in h's homes
     if (arole) {
-      v16f h[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const v4f x = *hs_ptr(wave, c, q);
-          h[c][4 * q] = x[0], h[c][4 * q + 1] = x[1], h[c][4 * q + 2] = x[2], h[c][4 * q + 3] = x[3];
-        }
       float eps[3];
-      post_eps_tiles(h, wout, p.d.bout, eps);
+      coop_eps(eps, home(wave), cc, p, lane);
       PointState ps;
-      ps.s = s, ps.n = nbase + wave * 32 + pj, ps.gid = 0;   // (gid: the noise was drawn by waves 6, 7)
-      pstate_load(ps_lds, pj, 32, ps, true);
-      const float *s_z = reinterpret_cast<const float *>(pipe_smem + C2_Z + wave * 1024);
-      const float zr[3] = {s_z[pj], s_z[32 + pj], s_z[64 + pj]};
-      const bool zok = p.mode != MODE_EPS;
-      if (step_epilogue(p, ps, eps, step, t, zok ? zr : nullptr, zok ? s_z + 128 : nullptr)) break;   // (the other waves leave through the loop bound: nsteps = 1 in these modes)
+      if (coop_posterior(p, ps, eps, ps_lds, z_base(wave), s, n_a, step, t, pj)) break;   // (the other waves leave through the loop bound: nsteps = 1 in these modes)
       pstate_store(ps_lds, pj, 32, ps, false);
-      if (step + 1 < p.nsteps) enter_step(ps);
+      if (step + 1 < p.nsteps) coop_enter_step(ps, home(wave), cc, lane);
     }
   }
 }
@@ -2959,12 +2121,11 @@ struct VariantKernel {
 };
 const VariantKernel KERNELS[NUM_VARIANTS] = {
     {k_denoise_pipe<8>, PipeCfg<8>::L_TOTAL},     {k_denoise_pipe<4>, PipeCfg<4>::L_TOTAL},     {k_denoise_pipe<2>, PipeCfg<2>::L_TOTAL},
-    {k_denoise_pipe2, P2_LDS},                    {k_denoise_coop, CL_TOTAL},                   {k_denoise_coop2, C2_TOTAL},
-    {k_denoise_coop16, C16_TOTAL},                {k_denoise_pipe_f32<8>, PipeCfg<8>::L_TOTAL}, {k_denoise_pipe_f32<4>, PipeCfg<4>::L_TOTAL},
-    {k_denoise_pipe_f32<2>, PipeCfg<2>::L_TOTAL}, {k_denoise<DFX_PREC_BF16, 4>, 0},             {k_denoise<DFX_PREC_F32, 4>, 0},
+    {k_denoise_coop, CL_TOTAL},                   {k_denoise_coop2, C2_TOTAL},                  {k_denoise_pipe_f32<8>, PipeCfg<8>::L_TOTAL},
+    {k_denoise_pipe_f32<4>, PipeCfg<4>::L_TOTAL}, {k_denoise_pipe_f32<2>, PipeCfg<2>::L_TOTAL}, {k_denoise<DFX_PREC_BF16, 4>, 0},
+    {k_denoise<DFX_PREC_F32, 4>, 0},
 };
-static_assert(info(Variant::Pipe2Tiles).threads == P2_NW * 64 && info(Variant::Coop).threads == COOP_NW * 64 && info(Variant::Coop2).threads == COOP_NW * 64 &&
-                  info(Variant::Coop16).threads == C16_NW * 64 && info(Variant::Coop16).points == C16_PTS && info(Variant::Pipe8).points == PipeCfg<8>::PTS,
+static_assert(info(Variant::Coop).threads == COOP_NW * 64 && info(Variant::Coop2).threads == COOP_NW * 64 && info(Variant::Pipe8).points == PipeCfg<8>::PTS,
               "denoiser_plan.h's table against the kernels' launch bounds");
 
 int launch(const dfx_denoiser *d, const void *shape_ctx, KParams &p, hipStream_t st) {

@@ -7,7 +7,7 @@
 
 namespace dfx {
 
-enum class Variant { Pipe8, Pipe4, Pipe2, Pipe2Tiles, Coop, Coop2, Coop16, PipeF32_8, PipeF32_4, PipeF32_2, DirectBf16, DirectF32, COUNT };
+enum class Variant { Pipe8, Pipe4, Pipe2, Coop, Coop2, PipeF32_8, PipeF32_4, PipeF32_2, DirectBf16, DirectF32, COUNT };
 constexpr int NUM_VARIANTS = (int)Variant::COUNT;
 
 struct VariantInfo {
@@ -17,33 +17,29 @@ struct VariantInfo {
 };
 constexpr VariantInfo VARIANTS[NUM_VARIANTS] = {
     {"k_denoise_pipe<8>", 512, 256},     {"k_denoise_pipe<4>", 256, 128},     {"k_denoise_pipe<2>", 128, 64},
-    {"k_denoise_pipe2", 256, 256},       {"k_denoise_coop", 512, 32},         {"k_denoise_coop2", 512, 64},
-    {"k_denoise_coop16", 512, 16},       {"k_denoise_pipe_f32<8>", 512, 256}, {"k_denoise_pipe_f32<4>", 256, 128},
-    {"k_denoise_pipe_f32<2>", 128, 64},  {"k_denoise<bf16>", 256, 128},       {"k_denoise<f32>", 256, 128},
+    {"k_denoise_coop", 512, 32},         {"k_denoise_coop2", 512, 64},        {"k_denoise_pipe_f32<8>", 512, 256},
+    {"k_denoise_pipe_f32<4>", 256, 128}, {"k_denoise_pipe_f32<2>", 128, 64},  {"k_denoise<bf16>", 256, 128},
+    {"k_denoise<f32>", 256, 128},
 };
 constexpr const VariantInfo &info(Variant v) { return VARIANTS[(int)v]; }
 
 // dfx_debug_pipe_waves: the integer codes are the external interface (bench.py --pipe-waves, tools, tests), this is what they mean
-enum class Force { Auto, AutoNoCoop16, Pipe8, Pipe4, Pipe2, CoopOrDirect, Coop2, Pipe2Tiles, Coop16 };
+enum class Force { Auto, Pipe8, Pipe4, Pipe2, CoopOrDirect, Coop2 };
 constexpr Force force_from_code(int code) {
   switch (code) {
-    case 161: return Force::AutoNoCoop16;   // automatic, with k_denoise_coop16 ruled out (A/B of the planner's choice)
     case 8: return Force::Pipe8;
     case 4: return Force::Pipe4;
     case 2: return Force::Pipe2;
     case 1: return Force::CoopOrDirect;     // bf16: k_denoise_coop; fp32: the direct kernel
     case 16: return Force::Coop2;           // N % 64 != 0: k_denoise_coop
-    case 64: return Force::Pipe2Tiles;      // 256-point tiles padding the shape by more than 3x: the automatic pipelined choice
-    case 160: return Force::Coop16;
-    default: return Force::Auto;
+    default: return Force::Auto;            // (every other code, the retired 64, 160 and 161 among them)
   }
 }
 
 // ms per round of num_cus workgroups at N = 2048, T = 1000 (only the ratios matter).  Pipelined kernels by wavefronts per workgroup and the
 // co-operative kernel: profiles/r02_small_batch_sweep.txt; k_denoise_coop2: between one and two rounds of k_denoise_coop (B = 5 .. 8 shapes of
-// 2048 points) the cheapest; k_denoise_coop16 (16-point tiles, round 5: 2 x the workgroups of k_denoise_coop): 1e9 = never chosen
-// automatically until measured (profiles/r05_small_batch_sweep.txt).
-constexpr double PIPE8_ROUND_MS = 93.5, PIPE4_ROUND_MS = 88.5, PIPE2_ROUND_MS = 86.5, COOP_ROUND_MS = 32.7, COOP2_ROUND_MS = 48.2, C16_ROUND_MS = 1e9;
+// 2048 points) the cheapest.
+constexpr double PIPE8_ROUND_MS = 93.5, PIPE4_ROUND_MS = 88.5, PIPE2_ROUND_MS = 86.5, COOP_ROUND_MS = 32.7, COOP2_ROUND_MS = 48.2;
 
 struct PlanInput {
   int prec;            // DFX_PREC_F32 / DFX_PREC_BF16
@@ -60,8 +56,8 @@ struct Plan {
 
 // One workgroup per CU, so a launch runs in rounds of num_cus workgroups and the cheapest estimate wins.  The pipelined kernels work on tiles
 // of nw x 32 points of one shape (a partial last tile idles whole wavefronts) with nw = 8, 4 or 2 wavefronts per workgroup — fewer wavefronts
-// spread a small batch over more CUs; the co-operative ones put eight wavefronts on one (k_denoise_coop), two (coop2) or half a (coop16)
-// 32-point tile.  Every variant of one precision produces the same bits.
+// spread a small batch over more CUs; the co-operative ones put eight wavefronts on one (k_denoise_coop) or two (coop2)
+// 32-point tiles.  Every variant of one precision produces the same bits.
 inline Plan plan_launch(const PlanInput &in) {
   const int N = in.N, num_cus = in.num_cus;
   const long long waves = ((long long)in.B * N) / 32;
@@ -77,11 +73,10 @@ inline Plan plan_launch(const PlanInput &in) {
   auto tiled = [&](Variant first, int nw) { return Plan{(Variant)((int)first + (nw == 8 ? 0 : nw == 4 ? 1 : 2)), tiles(nw) * in.B}; };
 
   // Eligibility.  A bf16 engine without the W1 bias fold (every hidden channel is an outlier of some block's W1', or dfx_debug_w1_fold(0)) has
-  // the plain pack, which only the direct kernel and k_denoise_coop16 read: the other chain kernels take b1' from slot 127.
-  const bool bf16_any_pack = in.prec == DFX_PREC_BF16 && !in.force_direct, bf16 = bf16_any_pack && in.w1_fold, f32 = in.prec == DFX_PREC_F32 && !in.force_direct;
+  // the plain pack, which only the direct kernel reads: the chain kernels take b1' from slot 127.
+  const bool bf16 = in.prec == DFX_PREC_BF16 && !in.force_direct && in.w1_fold, f32 = in.prec == DFX_PREC_F32 && !in.force_direct;
   const Force force = in.force;
-  const bool automatic = force == Force::Auto || force == Force::AutoNoCoop16;
-  if (bf16 && force == Force::Pipe2Tiles && fits(8)) return Plan{Variant::Pipe2Tiles, tiles(8) * in.B};
+  const bool automatic = force == Force::Auto;
 
   // Cost comparison: the pipelined kernel's cheapest nw (a forced one replaces it, its estimate `best` stays the automatic one) ...
   int nw = 8;
@@ -92,17 +87,13 @@ inline Plan plan_launch(const PlanInput &in) {
     if (cost < best) best = cost, nw = c;
   }
   if (const int forced_nw = force == Force::Pipe8 ? 8 : force == Force::Pipe4 ? 4 : force == Force::Pipe2 ? 2 : 0) nw = forced_nw;
-  const bool pipe = bf16 && fits(nw), pipe_f32 = f32 && force != Force::CoopOrDirect && fits(nw);   // (fp32 ignores Coop2 / Pipe2Tiles / Coop16)
+  const bool pipe = bf16 && fits(nw), pipe_f32 = f32 && force != Force::CoopOrDirect && fits(nw);   // (fp32 ignores Coop2)
   // ... against the co-operative kernels (coop2 needs N % 64 == 0; without a pipelined candidate k_denoise_coop takes up to one round)
   const double coop_cost = rounds_cost(waves, COOP_ROUND_MS, 0.0), coop2_cost = rounds_cost((waves + 1) / 2, COOP2_ROUND_MS, 0.0);
-  const double coop16_cost = rounds_cost(((long long)in.B * N) / 16, C16_ROUND_MS, 0.0);
   const bool coop = bf16 && (force == Force::CoopOrDirect || (force == Force::Coop2 && N % 64 != 0) || (automatic && (pipe ? coop_cost < best : waves <= num_cus)));
   const bool coop2 = bf16 && N % 64 == 0 && (force == Force::Coop2 || (automatic && coop2_cost < coop_cost && (!pipe || coop2_cost < best)));
-  // (an engine without the fold would otherwise take the direct kernel, ~3x the pipelined estimate)
-  const bool coop16 = bf16_any_pack && (force == Force::Coop16 || (force == Force::Auto && coop16_cost < (coop2 ? coop2_cost : coop ? coop_cost : bf16 ? best : 3.0 * best)));
 
   // The first that applies; the direct kernels are the fallback of everything above.
-  if (coop16) return flat(Variant::Coop16);
   if (coop2) return flat(Variant::Coop2);
   if (coop) return flat(Variant::Coop);
   if (pipe) return tiled(Variant::Pipe8, nw);

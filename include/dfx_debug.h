@@ -70,19 +70,15 @@ void dfx_debug_w1_fold(int mode);
 /* The hidden channel whose K slot of the packed W1 carries b1' (127 unless create relabelled the channels; -1 = engine without the fold). */
 int dfx_debug_w1_fold_channel(const dfx_denoiser *d);
 /* Debug: force one chain-kernel variant of the denoiser launches (csrc/denoiser_plan.h: force_from_code).  The codes:
- *     0 = automatic: chosen from the batch shape by the cost model (the default); any value not listed here is treated as 0;
- *   161 = automatic, with k_denoise_coop16 ruled out (the cost model never picks it today, so the same choice as 0);
+ *     0 = automatic: chosen from the batch shape by the cost model (the default); any value not listed here is treated as 0 - among them
+ *       64, 160 and 161, which selected two since-retired kernels (bench.py's --pipe-waves help still lists 64: it now means automatic);
  *     8, 4, 2 = wavefronts per workgroup of the pipelined chain kernel (k_denoise_pipe<NW>, for an fp32 denoiser k_denoise_pipe_f32<NW>);
  *       tiles of NW x 32 points that would pad a shape by more than 3x fall back to the direct kernel;
  *     1 = the co-operative latency kernel k_denoise_coop (one 32-point tile per workgroup, eight wavefronts on it); for an fp32 denoiser: the
  *       direct kernel;
- *    16 = k_denoise_coop2 (bf16 only: the co-operative kernel with two 32-point tiles per workgroup; N % 64 != 0 falls back to k_denoise_coop);
- *    64 = k_denoise_pipe2 (bf16 only: four wavefronts of two 32-point tiles each; when its 256-point workgroup tiles would pad a shape by more
- *       than 3x - ceil(N / 256) * 256 > 3 N - the request falls back SILENTLY to the automatic choice among k_denoise_pipe<4>, <2> and the
- *       direct kernel);
- *   160 = k_denoise_coop16 (bf16 only: the co-operative kernel on 16-point tiles; reads either W1 pack; NOT bit-identical to the others).
- * An fp32 denoiser ignores 16, 64 and 160; a bf16 engine without the W1 bias fold, or under dfx_debug_force_direct, takes the direct kernel
- * whatever the code, except that 160 still applies without the fold.  All other variants of one precision are bit-identical.
+ *    16 = k_denoise_coop2 (bf16 only: the co-operative kernel with two 32-point tiles per workgroup; N % 64 != 0 falls back to k_denoise_coop).
+ * An fp32 denoiser ignores 16; a bf16 engine without the W1 bias fold, or under dfx_debug_force_direct, takes the direct kernel
+ * whatever the code.  All variants of one precision are bit-identical.
  * dfx_last_kernel_variant() (dfx.h) names the kernel a launch actually took. */
 void dfx_debug_pipe_waves(int nw);
 /* Host-side run (no GPU) of the launcher's planner (csrc/denoiser_plan.h): the name dfx_last_kernel_variant() would report after a denoiser

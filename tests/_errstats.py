@@ -11,7 +11,7 @@ import numpy as np
 # point index n, shape b, output coordinate c -> group id
 GROUPINGS = {
     "lane": lambda b, c, n: n % 32,            # lane of the 32-point tile of one wavefront
-    "lane16": lambda b, c, n: n % 16,          # the 16-point co-operative kernel
+    "lane16": lambda b, c, n: n % 16,          # point within half a 32-point tile
     "wave": lambda b, c, n: (n // 32) % 8,     # wavefront slot in the 256-point workgroup
     "tile": lambda b, c, n: n // 256,          # workgroup tile
     "shape": lambda b, c, n: b,

@@ -67,7 +67,7 @@ EPS_CASES = {"B4_N2048": (4, 2048, 11, True, ALL_GROUPS),
              "B3_N100": (3, 100, 14, True, ()),                       # the padded path
              "B12_N2048": (12, 2048, 15, True, ALL_GROUPS)}           # XCD remap (8 shapes) + natural-order tail (4)
 #                  label               forced variant (tests/_variants.py; "direct": dfx_debug_force_direct)   lane grouping of the kernel
-BF16_VARIANTS = (("k_denoise_pipe<8>", 8), ("k_denoise<bf16>", "direct"), ("k_denoise_coop", 1), ("k_denoise_coop16", 160))
+BF16_VARIANTS = (("k_denoise_pipe<8>", 8), ("k_denoise<bf16>", "direct"), ("k_denoise_coop", 1))
 F32_VARIANTS = (("k_denoise_pipe_f32<8>", 8), ("k_denoise<f32>", 1))
 
 
@@ -212,11 +212,10 @@ def test_eps_every_variant_vs_float64(yardsticks, engines, name, prec):
         c = y["case"]
         cx = cx or _prep(eng, c)
         for label, how in _variants(prec):
-            g = tuple(k for k in groups if not (k == "lane" and how == 160))      # 16-point tiles: the lane grouping is n % 16
             with _Run(prec, label, how) as r:
                 eps = eng.eps(cx, _tt(c["x"]), _tt(c["seg"]), t).cpu().numpy()
                 r.ran()
-            _judge(fails, f"eps {name} t={t}", label, prec, eps, y["truth"], y[prec], g)
+            _judge(fails, f"eps {name} t={t}", label, prec, eps, y["truth"], y[prec], groups)
     assert not fails, "\n".join(fails)
 
 
@@ -247,9 +246,8 @@ def test_eps_bf16_plain_w1_pack_and_moved_fold_channel_vs_float64(W, yardsticks)
                 cx = cx or _prep(eng, c)
                 eps = eng.eps(cx, _tt(c["x"]), _tt(c["seg"]), t).cpu().numpy()
                 v = last_kernel_variant()
-                g = tuple(k for k in EPS_CASES[name][4] if not (k == "lane" and v == "k_denoise_coop16"))
                 _judge(fails, f"eps {name} t={t} weights={wkey} w1_fold={'plain' if ch is None else f'channel {ch}'}", v, "bf16", eps,
-                       y["truth"], y["bf16"], g)
+                       y["truth"], y["bf16"], EPS_CASES[name][4])
         eng.close()
     assert not fails, "\n".join(fails)
 

@@ -20,7 +20,6 @@ CASES = [("bf16",       0,    1,  2048, "k_denoise_coop"),
          ("bf16_nofold", 0,   3,  2048, "k_denoise<bf16>"),
          ("f32",        0,    3,  2048, None),
          ("f32",        0,    3,  96,   None),
-         ("bf16",       64,   3,  2048, "k_denoise_pipe2"),
          ("bf16",       16,   3,  2048, "k_denoise_coop2"),
          ("bf16",       16,   3,  96,   "k_denoise_coop")]
 

@@ -44,7 +44,7 @@ def main():
                 rows.append([[N], cells])
         for ns, cells in rows:
             print(f"| {label} | {', '.join(map(str, ns))} | {cells} |")
-    forced = {_ffi.lib().dfx_debug_plan_variant(prec, 1, 0, code, 3, 2048, None).decode() for prec in (0, 1) for code in (1, 2, 4, 8, 16, 64, 160)}
+    forced = {_ffi.lib().dfx_debug_plan_variant(prec, 1, 0, code, 3, 2048, None).decode() for prec in (0, 1) for code in (1, 2, 4, 8, 16)}
     print("\nOnly when forced (`dfx_debug_pipe_waves`, `dfx_debug_force_direct`):", ", ".join(f"`{n}`" for n in sorted(forced - auto)))
 
 

@@ -1,6 +1,6 @@
 """Soak test of the pipelined chain's LDS ring protocol (GPU box): the same launch repeated must be bit-identical.
 A protocol race (a ring slot overwritten before its last reader, a read ahead of its DMA) would show up as a mismatch.
-    python tools/soak_determinism.py [reps] [T] [bf16|f32] [pipe-waves]      (pipe-waves 64 = k_denoise_pipe2)"""
+    python tools/soak_determinism.py [reps] [T] [bf16|f32] [pipe-waves]      (include/dfx_debug.h: dfx_debug_pipe_waves)"""
 import os
 import sys
 

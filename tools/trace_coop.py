@@ -1,4 +1,4 @@
-"""Phase durations of the co-operative kernels (library built with -DDFX_TRACE): python tools/trace_coop16.py [160|1]   (160 = 16-point tiles, 1 = 32-point)"""
+"""Phase durations of the co-operative kernel k_denoise_coop (library built with -DDFX_TRACE): python tools/trace_coop.py"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, ctypes
@@ -6,13 +6,12 @@ from difffacto_amd import build
 build.build(force=True, verbose=False, extra_flags=["-DDFX_TRACE"])
 from difffacto_amd import synth, _ffi
 from difffacto_amd.engine import DenoiserEngine, last_kernel_variant
-code = int(sys.argv[1]) if len(sys.argv) > 1 else 160
 T, B, N, CAP = 6, 1, 2048, 4096
 eng = DenoiserEngine({k: torch.from_numpy(v) for k, v in synth.make_denoiser_weights(0).items()}, num_timesteps=T, precision="bf16")
 pc, m, lv, va = synth.make_latents(B, seed=1)
 ctx = eng.prepare_shapes(*map(torch.from_numpy, (pc, m, np.exp(lv).astype(np.float32), va)))
 seg = torch.from_numpy(synth.make_seg_mask(va, N))
-_ffi.lib().dfx_debug_pipe_waves(code)
+_ffi.lib().dfx_debug_pipe_waves(1)   # k_denoise_coop, the co-operative kernel that carries the stamps
 eng.sample_chain(ctx, seg, seed=1)
 buf = torch.zeros(2 * CAP, dtype=torch.int64, device="cuda")
 _ffi.lib().dfx_debug_trace(ctypes.c_void_p(buf.data_ptr()), CAP)

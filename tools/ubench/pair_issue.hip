@@ -1,4 +1,4 @@
-// Micro-benchmark for k_denoise_pipe2's MFMA stream: ONE wavefront per SIMD (256 threads, 512 registers) issuing pairs of
+// Micro-benchmark of an MFMA stream with two point tiles per wavefront (the schedule of a since-retired chain kernel): ONE wavefront per SIMD (256 threads, 512 registers) issuing pairs of
 // v_mfma_f32_32x32x16 that share their A fragment (two point tiles), the fragment refilled in place from LDS behind the pair.
 // Variants: C/D in the accumulator file or in VGPRs, B from the accumulator file or VGPRs, with / without the refill, NV packed
 // fp16 VALU fillers per MFMA.  Prints shader cycles per MFMA (floor: 32).
