@@ -182,6 +182,8 @@ SIGNATURES = {
     "dfx_debug_diverse_global_path": (None, [_I]),
     "dfx_debug_bn_fused_stats": (None, [_I]),
     "dfx_debug_stats_merge": (None, [_P, _I, _I, _P]),
+    "dfx_debug_pointnet_v2_branch": (_I, [ctypes.POINTER(PointNetV2Weights), _P, _SZ, _I, _I, ctypes.POINTER(c_fp), ctypes.POINTER(c_fp), _P, _P]),
+    "dfx_debug_prior_loss_branch": (_I, [_P, _SZ, _I, _I, _I, _P, _P, _P]),
     "dfx_debug_rowmap": (None, [_I, _P, _P]),
     "dfx_debug_emd_state_global": (None, [_I]),
     "dfx_debug_chamfer_queries": (None, [_I]),

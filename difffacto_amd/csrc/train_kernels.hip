@@ -1566,6 +1566,19 @@ __global__ void k_relu_mask(float *__restrict__ d, const float *__restrict__ h, 
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n && !(h[i] > 0.f)) d[i] = 0.f;
 }
+// Test-only branch export (dfx_debug_*_branch): one byte per unit, 1 where the backward passes the gradient on.  The BatchNorm sites state
+// the mask through bn_affine — the backward's own test —, the flows' through k_relu_mask's.
+__global__ void k_dbg_bn_mask(const float *__restrict__ z, const float *__restrict__ mean, const float *__restrict__ rstd,
+                              const float *__restrict__ g, const float *__restrict__ be, uint8_t *__restrict__ out, long long total, int Cc) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int c = (int)(i % Cc);
+  out[i] = bn_affine(z[i], mean[c], rstd[c], g[c], be[c]) > 0.f ? 1 : 0;
+}
+__global__ void k_dbg_pos_mask(const float *__restrict__ h, uint8_t *__restrict__ out, long long n) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = h[i] > 0.f ? 1 : 0;
+}
 // per (part, shape): log p(w) + log det (0 for absent parts), posterior entropy, and the loss coefficient a = kl valid / (B n_valid)
 __global__ __launch_bounds__(256) void k_prior_terms(const float *__restrict__ w, const float *__restrict__ logdet, const float *__restrict__ logvar,
                                                       const float *__restrict__ valid, float prior_var, float kl, int B, float *__restrict__ logp,
@@ -2937,6 +2950,53 @@ int dfx_shared_mlp_train_backward(const dfx_shared_mlp_train *t, void *workspace
 void dfx_debug_train_fused(int on) { g_ff_fused = on != 0, g_attn_in_ff = on != 2; }
 const char *dfx_debug_last_train_path(void) { return t_last_path; }
 void dfx_debug_bn_fused_stats(int on) { g_bn_fused_stats = on != 0; }
+// The branch dfx_pointnet_v2_train_backward will take on this workspace (call between the forward and the backward; reads only): the ReLU masks
+// of the three trunk layers (B N, 128 / 128 / 256) and of the heads' two BatchNorm sites (B, 4 x 256), (B, 4 x 128) in the order mlp_m.1, mlp_m.4,
+// mlp_v.1, mlp_v.4, one byte per unit, and the pool's arg-max (B, 4, 512).
+int dfx_debug_pointnet_v2_branch(const dfx_pointnet_v2_weights *wt, const void *workspace, size_t workspace_bytes, int B, int N,
+                                 uint8_t *const *trunk_masks, uint8_t *const *head_masks, int32_t *arg, dfx_stream_t stream) {
+  int rc = check_pn(wt, workspace, workspace_bytes, B, N, "debug_pointnet_v2_branch");
+  if (rc) return rc;
+  DFX_REQUIRE(trunk_masks && head_masks && arg, "debug_pointnet_v2_branch: null output");
+  hipStream_t st = dfx::as_stream(stream);
+  const int A = wt->num_anchors;
+  PnWs w;
+  carve_pn(w, const_cast<void *>(workspace), B, N, A, wt->zdim);
+  const long long R = (long long)B * N;
+  for (int l = 0; l < 3; ++l) {
+    DFX_REQUIRE(trunk_masks[l], "debug_pointnet_v2_branch: null trunk mask %d", l);
+    const long long total = R * PN_C[l + 1];
+    k_dbg_bn_mask<<<(int)((total + 255) / 256), 256, 0, st>>>(w.z[l], w.mean[l], w.rstd[l], wt->bn_w[l], wt->bn_b[l], trunk_masks[l], total, PN_C[l + 1]);
+  }
+  const int hc[2] = {256, 128};
+  for (int k = 0; k < 2; ++k)
+    for (int l = 0; l < 2; ++l) {
+      DFX_REQUIRE(head_masks[2 * k + l], "debug_pointnet_v2_branch: null head mask %d", 2 * k + l);
+      const long long total = (long long)B * A * hc[l];
+      k_dbg_bn_mask<<<(int)((total + 255) / 256), 256, 0, st>>>(w.hz[k][l], w.hmean[k][l], w.hrstd[k][l], wt->head_bn_w[k][l], wt->head_bn_b[k][l],
+                                                                head_masks[2 * k + l], total, A * hc[l]);
+    }
+  DFX_HIP_TRY(hipMemcpyAsync(arg, w.arg, sizeof(int32_t) * (size_t)B * A * 512, hipMemcpyDeviceToDevice, st));
+  return dfx::check_launch("debug_pointnet_v2_branch");
+}
+// The same for dfx_prior_loss_backward: the masks h1[l] > 0 and h2[l] > 0 of every coupling layer, (depth, 4 B, H) bytes each, rows part-major.
+int dfx_debug_prior_loss_branch(const void *workspace, size_t workspace_bytes, int flow_depth, int flow_hidden, int B, uint8_t *h1_masks,
+                                uint8_t *h2_masks, dfx_stream_t stream) {
+  DFX_REQUIRE(workspace && h1_masks && h2_masks, "debug_prior_loss_branch: null argument");
+  DFX_REQUIRE(flow_depth >= 1 && flow_depth <= DFX_MAX_FLOW_DEPTH && flow_hidden >= 8 && flow_hidden % 8 == 0 && B >= 1,
+              "debug_prior_loss_branch: depth %d hidden %d B %d", flow_depth, flow_hidden, B);
+  FlowWs w;
+  DFX_REQUIRE(workspace_bytes >= carve_flow(w, nullptr, B, flow_depth, flow_hidden), "debug_prior_loss_branch: workspace too small");
+  DFX_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "debug_prior_loss_branch: workspace must be 256-byte aligned");
+  hipStream_t st = dfx::as_stream(stream);
+  carve_flow(w, const_cast<void *>(workspace), B, flow_depth, flow_hidden);
+  const long long n = (long long)NPART * B * flow_hidden;
+  for (int l = 0; l < flow_depth; ++l) {
+    k_dbg_pos_mask<<<(int)((n + 255) / 256), 256, 0, st>>>(w.h1[l], h1_masks + (size_t)l * n, n);
+    k_dbg_pos_mask<<<(int)((n + 255) / 256), 256, 0, st>>>(w.h2[l], h2_masks + (size_t)l * n, n);
+  }
+  return dfx::check_launch("debug_prior_loss_branch");
+}
 // Host-side run of the statistics arithmetic of k_lin_wide_lds<.., LM_STATS> / k_bn_merge (the same stats_merge, compiled for the host): `n` values cut
 // into pieces of `chunk` (a lane's 16 rows of a tile), each piece as (count, mean, sum of squared deviations from its own mean), merged left to right.
 void dfx_debug_stats_merge(const float *values, int n, int chunk, float *out3) {

@@ -284,6 +284,41 @@ def pointnet_v2_train_forward(params, buffers, x, attn, num_anchors=4, zdim=256,
                                    [buffers[n] for n in PNV2_BUFFERS], *[params[n] for n in PNV2_PARAMS])
 
 
+def pointnet_v2_branch(m):
+    """Test hook (dfx_debug_pointnet_v2_branch): the branch the backward of `m` = pointnet_v2_train_forward(...)[0] will take, read from its
+    workspace before backward() runs: {"bn1" / "bn2" / "bn3": (B N, C) uint8, "mlp_m.1" / "mlp_m.4" / "mlp_v.1" / "mlp_v.4": (B, 4 C) uint8,
+    "arg": (B, 4, 512) int32} as cuda tensors.  Changes nothing the forward or the backward execute."""
+    fn = m.grad_fn
+    if not type(fn).__name__.startswith("PointNetV2TrainFn") or fn.ws_ptr is None:
+        raise ValueError("pointnet_v2_branch: an output of pointnet_v2_train_forward whose backward has not run yet is expected")
+    num_anchors, zdim, reweight, eps = fn.cfg[:4]
+    B, N = fn.shape
+    dev = fn.attn.device
+    out = {f"bn{l + 1}": torch.empty(B * N, c, dtype=torch.uint8, device=dev) for l, c in enumerate((128, 128, 256))}
+    out.update({f"{h}.{i}": torch.empty(B, num_anchors * c, dtype=torch.uint8, device=dev) for h in ("mlp_m", "mlp_v") for i, c in ((1, 256), (4, 128))})
+    out["arg"] = torch.empty(B, num_anchors, 512, dtype=torch.int32, device=dev)
+    w = _pnv2_struct(fn.t, num_anchors, zdim, reweight, eps)
+    with torch.cuda.device(dev):
+        _ffi.check(_ffi.lib().dfx_debug_pointnet_v2_branch(ctypes.byref(w), fn.ws_ptr, fn.nbytes, B, N, _ptr_array([out[f"bn{l}"] for l in (1, 2, 3)]),
+                                                           _ptr_array([out[k] for k in ("mlp_m.1", "mlp_m.4", "mlp_v.1", "mlp_v.4")]),
+                                                           out["arg"].data_ptr(), _ffi.current_stream()), "dfx_debug_pointnet_v2_branch")
+    return out
+
+
+def prior_loss_branch(loss):
+    """Test hook (dfx_debug_prior_loss_branch): the ReLU masks the backward of `loss` = prior_loss(...)[0] will apply, read from its workspace
+    before backward() runs: {"h1", "h2": (depth, 4 B, hidden) uint8 cuda tensors, rows part * B + shape}."""
+    fn = loss.grad_fn
+    if not type(fn).__name__.startswith("PriorLossFn") or fn.ws_ptr is None:
+        raise ValueError("prior_loss_branch: the loss of prior_loss whose backward has not run yet is expected")
+    depth, hidden = fn.cfg[:2]
+    out = {k: torch.empty(depth, 4 * fn.B, hidden, dtype=torch.uint8, device=fn.vd.device) for k in ("h1", "h2")}
+    with torch.cuda.device(fn.vd.device):
+        _ffi.check(_ffi.lib().dfx_debug_prior_loss_branch(fn.ws_ptr, fn.nbytes, depth, hidden, fn.B, out["h1"].data_ptr(), out["h2"].data_ptr(),
+                                                          _ffi.current_stream()), "dfx_debug_prior_loss_branch")
+    return out
+
+
 def flow_param_names(depth, n_class=4):
     """state_dict names (relative to the encoder) of the coupling flows, in libdfx's [part][layer][w0,b0,w1,b1,w2,b2] order."""
     return [f"flow.{i}.chain.{l}.net_s_t.{k}.{wb}" for i in range(n_class) for l in range(depth) for k in (0, 2, 4) for wb in ("weight", "bias")]

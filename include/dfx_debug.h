@@ -32,6 +32,16 @@ void dfx_debug_train_streams(int on);
  * (>= 8192 rows), equal up to fp32 rounding of the statistics; and BatchNorm over at most 512 rows (the per-part heads: over the B shapes) as one
  * launch per direction instead of seven / four, bit-identical to the multi-launch passes. */
 void dfx_debug_bn_fused_stats(int on);
+/* Test hook: the branch dfx_pointnet_v2_train_backward will derive from this workspace, copied out between the forward and the backward (the
+ * workspace is only read).  trunk_masks[3]: one byte per unit of the three ReLU trunk layers, (B N, 128 / 128 / 256); head_masks[4]: the heads'
+ * ReLU sites mlp_m.1, mlp_m.4, mlp_v.1, mlp_v.4, (B, 4 x 256) and (B, 4 x 128) per head; 1 = the gradient passes, from the backward's own test
+ * (the BatchNorm affine of z > 0).  arg: the max-pool's selected point per (shape, part, channel), (B, 4, 512) int32.  Device pointers. */
+int dfx_debug_pointnet_v2_branch(const dfx_pointnet_v2_weights *wt, const void *workspace, size_t workspace_bytes, int B, int N,
+                                 uint8_t *const *trunk_masks, uint8_t *const *head_masks, int32_t *arg, dfx_stream_t stream);
+/* Test hook: the same for dfx_prior_loss_backward: the ReLU masks h1 > 0 and h2 > 0 of every coupling layer, (flow_depth, 4 B, flow_hidden)
+ * bytes each, rows part-major (part * B + shape). */
+int dfx_debug_prior_loss_branch(const void *workspace, size_t workspace_bytes, int flow_depth, int flow_hidden, int B, uint8_t *h1_masks,
+                                uint8_t *h2_masks, dfx_stream_t stream);
 /* Host-side run (no GPU) of that statistics arithmetic: n values in pieces of `chunk`, each piece as (count, mean, M2), merged left to right with
  * the kernels' own merge function; out3 = (count, mean, sum of squared deviations). */
 void dfx_debug_stats_merge(const float *values, int n, int chunk, float *out3);

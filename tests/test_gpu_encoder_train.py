@@ -4,6 +4,7 @@ running-statistics update, and the backward, against the reference class's own a
 Tolerances (fp32; the batch statistics and the column reductions sum in a different order than torch): outputs 2e-5 max-abs,
 running statistics 1e-5, gradients 1e-3 of each tensor's max-abs (BatchNorm over B = 5 samples in the heads amplifies
 rounding: 1 / sqrt(var + eps) of five numbers).
+The same kernels against float64 on the branch they took, with the fp32 oracle's own error as yardstick: tests/test_gpu_encoder_train_highprec.py.
 """
 import os
 import sys
