@@ -177,6 +177,7 @@ SIGNATURES = {
     "dfx_debug_dropout_factors": (_I, [_U64, _I, _F, _P, ctypes.c_longlong, _P]),
     "dfx_debug_train_fused": (None, [_I]),
     "dfx_debug_last_train_path": (ctypes.c_char_p, []),
+    "dfx_debug_plan_train": (ctypes.c_char_p, [_I, _F, _I, _I, _I, _I, ctypes.POINTER(_I)]),
     "dfx_debug_train_streams": (None, [_I]),
     "dfx_debug_lin_split_k": (None, [_I]),
     "dfx_debug_diverse_global_path": (None, [_I]),

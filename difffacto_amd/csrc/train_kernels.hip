@@ -14,7 +14,6 @@
 //   dW = dY^T X, db    -> k_wgrad: one wavefront owns a 64 x 64 tile of dW and a slab of rows, two rows per
 //                         v_mfma_f32_32x32x2_f32 (lane (j, hf) feeds dY[r + hf][o0 + j] and X[r + hf][i0 + j]: 128-byte
 //                         coalesced row segments), partial tiles per slab, deterministic second pass (no atomics)
-#include <functional>
 #include <mutex>
 #include <unordered_map>
 
@@ -23,6 +22,7 @@
 #include "gemm_bf16.h"
 #include "train_attn_fused.h"
 #include "mfma_linear.h"
+#include "train_plan.h"
 
 namespace {
 
@@ -1762,30 +1762,22 @@ bool g_attn_in_ff = true;   // (debug: 2 in dfx_debug_train_fused keeps the atte
 // Fused path: the context branch of the forward (time-embedding MLP, keys / values, attention folds) and the parameter-gradient
 // reductions of the backward run on the device's side stream (dfx::SideStream) beside the kernels over the points: they are chains of
 // small-grid launches that leave most of the chip idle.  Same kernels, same operands, same results; dfx_debug_train_streams(0) = one stream.
-int g_train_streams = 1;   // 0 = off, 1 = the default set, other values = explicit set of SS_* bits (A/B)
-enum { SS_FWD_CTX = 2, SS_HEAD_EARLY = 4, SS_STEM_EARLY = 8, SS_LEAVES = 16, SS_STEM_END = 32, SS_DEFAULT = SS_HEAD_EARLY | SS_STEM_EARLY | SS_LEAVES };
-inline int ss_mask() { return g_train_streams == 1 ? SS_DEFAULT : g_train_streams; }
-// The switches are sampled ONCE per step, by the forward, and recorded per workspace on the host: the backward follows the record,
-// not the switches, so toggling dfx_debug_train_fused between a forward and its backward (the A/B tests do) cannot pair a fused
-// backward with the activations of a layer-by-layer forward.
-struct PathRecord { bool fused, attn_in_ff; int prec; float dropout_p; int B, N; unsigned long long seq; };
+int g_train_streams = 1;   // 0 = off, 1 = the default set, other values = explicit set of SS_* bits (train_plan.h; A/B)
+// These three are the debug switches' storage, read only where a plan is made (train_plan.h: plan_train, plan_train_streams).  The PATH is
+// planned ONCE per step, by the forward, and recorded per workspace on the host: the backward follows the record, not the switches, so
+// toggling dfx_debug_train_fused between a forward and its backward (the A/B tests do) cannot pair a fused backward with the activations
+// of a layer-by-layer forward.  The side-stream decisions are planned from the live switch by each call.
+struct PathRecord { dfx::TrainPath path; int prec; float dropout_p; int B, N; unsigned long long seq; };
 unsigned long long g_path_seq = 0;   // forward counter: the record with the smallest seq is the one evicted when the table is full
 std::mutex g_path_mu;
 std::unordered_map<const void *, PathRecord> g_path;   // keyed by workspace pointer (a handful per process)
-thread_local bool t_ff_fused = true, t_attn_in_ff = true;   // what the call in progress on this thread uses
 thread_local const char *t_last_path = "none";                // dfx_debug_last_train_path(): the kernel family the last forward on this thread took
-// (dropout > 0 takes the fused kernels when the attention sub-block sits inside them — the default — : k_ff<*, true> / k_ff_wgrad<true>)
-inline bool ff_fused(bool bf, float dropout_p, long long R, int N) { return t_ff_fused && bf && (dropout_p == 0.f || t_attn_in_ff) && R % 32 == 0 && N % 32 == 0; }
 
-// bf16 operands (fp32 accumulate, fp32 results) for the large products when the caller asked for DFX_PREC_BF16
-thread_local int g_prec = DFX_PREC_F32;
-// product-only tensors are stored as bf16 when every product over the points takes the bf16 kernel (see store4 above)
-inline bool bf_store(long long R) { return g_prec == DFX_PREC_BF16 && R >= 256; }
-
-// x_bf: X is one of the bf16-stored tensors (only when bf_store(R): the bf16 product kernel is then guaranteed to apply)
-int lin(hipStream_t st, const float *X, int ldx, const float *W, const float *b, float *Y, int ldy, long long M, int N_,
+// prec: DFX_PREC_BF16 = bf16 operands (fp32 accumulate, fp32 results) for the large products, where the bf16 kernel's shape rules allow
+// x_bf: X is one of the bf16-stored tensors (only when TrainPlan::bf_store: the bf16 product kernel is then guaranteed to apply)
+int lin(hipStream_t st, int prec, const float *X, int ldx, const float *W, const float *b, float *Y, int ldy, long long M, int N_,
         int K, const float *resid = nullptr, int ldr = 0, bool x_bf = false, bool y_bf = false) {
-  if (g_prec == DFX_PREC_BF16) {
+  if (prec == DFX_PREC_BF16) {
     dfx::gemm::GemmArgs g{};
     g.A = X, g.lda = ldx, g.B = W, g.ldb = K, g.bias = b, g.R = resid, g.ldr = ldr, g.C = Y, g.ldc = ldy, g.M = (int)M, g.N = N_, g.K = K;
     g.a_bf16 = x_bf, g.c_bf16 = y_bf;
@@ -1834,12 +1826,12 @@ struct PartBufs {   // scratch of the two-pass reductions
   float *bpart;
   size_t bpart_floats;
 };
-int wgrad(hipStream_t st, const PartBufs &w, const float *dY, int ldy, const float *X, int ldx, float *dW, float *db, int O, int I,
+int wgrad(hipStream_t st, int prec, const PartBufs &w, const float *dY, int ldy, const float *X, int ldx, float *dW, float *db, int O, int I,
           int I_valid, long long R, bool dy_bf = false, bool x_bf = false) {
   bool done = false;
   int ns = 1;
   const size_t bcap = w.bpart_floats / (size_t)O;   // slabs the bias partials have room for
-  if (g_prec == DFX_PREC_BF16) {
+  if (prec == DFX_PREC_BF16) {
     dfx::gemm::GemmArgs g{};
     g.A = dY, g.lda = ldy, g.B = X, g.ldb = ldx, g.C = w.part, g.ldc = I, g.bpart = db ? w.bpart : nullptr, g.M = O, g.N = I, g.K = (int)R;
     g.rows_per_slab = pick_slab(R, (long long)(O / 128) * (I / 128), 512, w.part_floats, (size_t)O * I);
@@ -1878,9 +1870,9 @@ int wgrad(hipStream_t st, const PartBufs &w, const float *dY, int ldy, const flo
   return dfx::check_launch("train: wgrad");
 }
 
-inline int wgrad(hipStream_t st, TrainWs &w, const float *dY, int ldy, const float *X, int ldx, float *dW, float *db, int O, int I,
+inline int wgrad(hipStream_t st, int prec, TrainWs &w, const float *dY, int ldy, const float *X, int ldx, float *dW, float *db, int O, int I,
                  int I_valid, long long R, bool dy_bf = false, bool x_bf = false) {
-  return wgrad(st, PartBufs{w.part, w.part_floats, w.bpart, w.bpart_floats}, dY, ldy, X, ldx, dW, db, O, I, I_valid, R, dy_bf, x_bf);
+  return wgrad(st, prec, PartBufs{w.part, w.part_floats, w.bpart, w.bpart_floats}, dY, ldy, X, ldx, dW, db, O, I, I_valid, R, dy_bf, x_bf);
 }
 
 int ln_bwd(hipStream_t st, TrainWs &w, const float *dy, const float *x, const float *stats, const float *g, const float *resid,
@@ -2218,6 +2210,384 @@ int check_smt(const dfx_shared_mlp_train *t, const void *ws, size_t ws_bytes, in
   DFX_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: workspace must be 256-byte aligned", what);
   return DFX_OK;
 }
+
+// ---- the denoiser training step: one forward and one backward function per family of paths (train_plan.h) ----
+struct TrainFwdIo {
+  const float *x;
+  const int32_t *t;
+  const float *ctx_code, *ctx_mv, *anchors, *variances, *valid;
+  const int32_t *assignment;
+  float *eps;
+};
+struct TrainBwdIo {
+  const float *d_eps;
+  const dfx_denoiser_weights *grads;
+  float *d_ctx_code, *d_ctx_mv, *d_x, *d_variances;
+};
+struct TrainStep {   // one call: weights, carved workspace, shape, plan, the caller's stream
+  const dfx_denoiser_weights *wt;
+  TrainWs w;
+  int B, N, BJ;
+  long long R;
+  dfx::TrainPlan plan;
+  dfx::TrainStreams side;
+  float dropout_p;
+  uint64_t dropout_seed;
+  hipStream_t st;
+
+  TrainStep(const dfx_denoiser_weights *wt_, void *workspace, int B_, int N_, const dfx::TrainPlan &plan_, float p, uint64_t seed, dfx_stream_t stream)
+      : wt(wt_), B(B_), N(N_), BJ(B_ * J), R((long long)B_ * N_), plan(plan_), side(dfx::plan_train_streams(plan_.path, g_train_streams)),   // (the side-stream decisions: from the live switch, by each call)
+        dropout_p(p), dropout_seed(seed), st(dfx::as_stream(stream)) {
+    carve(w, workspace, B, N, wt->depth);
+  }
+
+  // ---- forward ----
+  // time embedding -> context rows, on sc
+  int context_rows(const TrainFwdIo &io, hipStream_t sc) {
+    int rc;
+    k_timestep_embedding<<<(B * TE + 255) / 256, 256, 0, sc>>>(io.t, w.te_in, B);
+    if ((rc = lin(sc, plan.prec, w.te_in, TE, wt->te0_w, wt->te0_b, w.te_ag, 2 * TEH, B, 2 * TEH, TE))) return rc;
+    k_geglu_fwd<false><<<(int)(((long long)B * TEH / 4 + 255) / 256), 256, 0, sc>>>(w.te_ag, w.te_hid, TEH, (long long)B * TEH, Drop{dropout_p, dropout_seed, SITE_TE});
+    if ((rc = lin(sc, plan.prec, w.te_hid, TEH, wt->te2_w, wt->te2_b, w.te_out, TE, B, TE, TEH))) return rc;
+    k_build_ctx<<<(BJ * CTXP + 255) / 256, 256, 0, sc>>>(io.ctx_code, io.ctx_mv, w.te_out, w.ctx, B);
+    return DFX_OK;
+  }
+  int keep_flags(const float *valid) {
+    if (valid) DFX_HIP_TRY(hipMemcpyAsync(w.valid, valid, sizeof(float) * BJ, hipMemcpyDeviceToDevice, st));
+    else DFX_HIP_TRY(hipMemsetAsync(w.valid, 0x3f, sizeof(float) * BJ, st));   // any non-zero value = keep
+    return DFX_OK;
+  }
+
+  int forward_layered(const TrainFwdIo &io) {   // LayerF32, LayerBf16
+    int rc;
+    const int prec = plan.prec;
+    const bool bf = plan.bf_store;
+    if ((rc = context_rows(io, st)) || (rc = keep_flags(io.valid))) return rc;
+    // proj_in + pre_norm
+    k_build_xin<<<(int)((R + 255) / 256), 256, 0, st>>>(io.x, io.anchors, io.variances, io.assignment, w.xin, N, R);
+    k_pad_cols<<<(C * XIN + 255) / 256, 256, 0, st>>>(wt->proj_in_w, w.wpad, C, 13, XIN);
+    if ((rc = lin(st, prec, w.xin, XIN, w.wpad, wt->proj_in_b, w.h0, C, R, C, XIN))) return rc;
+    k_ln_fwd<false><<<(int)((R + 7) / 8), 256, 0, st>>>(w.h0, wt->pre_norm_w, wt->pre_norm_b, w.blk[0].hin, w.st_pre, R);
+    for (int i = 0; i < wt->depth; ++i) {
+      const dfx_block_weights &bw = wt->blk[i];
+      BlockAct &a = w.blk[i];
+      float *hout = i + 1 < wt->depth ? w.blk[i + 1].hin : w.hfin;
+      if (bf) k_ln_fwd<true><<<(int)((R + 7) / 8), 256, 0, st>>>(a.hin, bw.norm2_w, bw.norm2_b, a.xn2, a.st2, R);
+      else k_ln_fwd<false><<<(int)((R + 7) / 8), 256, 0, st>>>(a.hin, bw.norm2_w, bw.norm2_b, a.xn2, a.st2, R);
+      if ((rc = lin(st, prec, a.xn2, C, bw.to_q, nullptr, a.q, C, R, C, C, nullptr, 0, bf))) return rc;
+      k_pad_cols<<<(C * CTXP + 255) / 256, 256, 0, st>>>(bw.to_k, w.wpad, C, CTX, CTXP);
+      if ((rc = lin(st, prec, w.ctx, CTXP, w.wpad, nullptr, a.k, C, BJ, C, CTXP))) return rc;
+      k_pad_cols<<<(C * CTXP + 255) / 256, 256, 0, st>>>(bw.to_v, w.wpad, C, CTX, CTXP);
+      if ((rc = lin(st, prec, w.ctx, CTXP, w.wpad, nullptr, a.v, C, BJ, C, CTXP))) return rc;
+      if (bf) k_attn_fwd<true><<<dim3(N / 32, B), 256, 0, st>>>(a.q, a.k, a.v, w.valid, a.p, a.att, N);
+      else k_attn_fwd<false><<<dim3(N / 32, B), 256, 0, st>>>(a.q, a.k, a.v, w.valid, a.p, a.att, N);
+      if (dropout_p > 0.f) {   // h1 = dropout(att Wo^T + bo) + hin   (attention.py:177: to_out = Sequential(Linear, Dropout))
+        if ((rc = lin(st, prec, a.att, C, bw.to_out_w, bw.to_out_b, a.h1, C, R, C, C, nullptr, 0, bf))) return rc;
+        k_dropout<<<(int)((R * C / 4 + 255) / 256), 256, 0, st>>>(a.h1, a.hin, a.h1, R * C, Drop{dropout_p, dropout_seed, (unsigned)(2 * i)});
+      } else if ((rc = lin(st, prec, a.att, C, bw.to_out_w, bw.to_out_b, a.h1, C, R, C, C, a.hin, C, bf))) return rc;
+      if (bf) k_ln_fwd<true><<<(int)((R + 7) / 8), 256, 0, st>>>(a.h1, bw.norm3_w, bw.norm3_b, a.xn3, a.st3, R);
+      else k_ln_fwd<false><<<(int)((R + 7) / 8), 256, 0, st>>>(a.h1, bw.norm3_w, bw.norm3_b, a.xn3, a.st3, R);
+      if ((rc = lin(st, prec, a.xn3, C, bw.ff0_w, bw.ff0_b, a.ag, 2 * FH, R, 2 * FH, C, nullptr, 0, bf, bf && AG_BF16))) return rc;
+      const Drop dff{dropout_p, dropout_seed, (unsigned)(2 * i + 1)};
+      if (bf) k_geglu_fwd<true><<<(int)((R * FH / 4 + 255) / 256), 256, 0, st>>>(a.ag, a.hid, FH, R * FH, dff);
+      else k_geglu_fwd<false><<<(int)((R * FH / 4 + 255) / 256), 256, 0, st>>>(a.ag, a.hid, FH, R * FH, dff);
+      if ((rc = lin(st, prec, a.hid, FH, bw.ff2_w, bw.ff2_b, hout, C, R, C, FH, a.h1, C, bf))) return rc;
+    }
+    k_ln_fwd<false><<<(int)((R + 7) / 8), 256, 0, st>>>(w.hfin, wt->post_norm_w, wt->post_norm_b, w.hn, w.st_post, R);
+    k_eps_fwd<<<(int)((R + 7) / 8), 256, 0, st>>>(w.hn, wt->proj_out_w, wt->proj_out_b, io.eps, N, R);
+    return dfx::check_launch("denoiser_train_forward");
+  }
+
+  int forward_fused(const TrainFwdIo &io) {   // Fused, FusedSplitAttn
+    int rc;
+    const bool split = plan.path == dfx::TrainPath::FusedSplitAttn;   // the attention forward as a kernel of its own, single-block launches, k_head_fwd
+    // Two branches meet in front of the first block: the points (input rows, proj_in + pre_norm, the blocks' weight fragments) on the caller's
+    // stream, the context (time embedding -> context rows -> keys / values of every block -> folded attention operands) on the side stream
+    dfx::SideStream ss;
+    if ((rc = ss.open(st, side.fwd_ctx))) return rc;
+    hipStream_t sc = ss.side;
+    if ((rc = ss.fork())) return rc;
+    if ((rc = context_rows(io, sc))) return rc;
+    const int LDKV = 2 * wt->depth * C;
+    {   // packed key / value weights of every block (the side stream's product below reads them: second fork)
+      KvPtrs kp{};
+      for (int i = 0; i < wt->depth; ++i) kp.p[2 * i] = wt->blk[i].to_k, kp.p[2 * i + 1] = wt->blk[i].to_v;
+      k_pack_kv<<<(2 * wt->depth * C * CTXP + 255) / 256, 256, 0, st>>>(kp, w.wkv, 2 * wt->depth);
+    }
+    if ((rc = keep_flags(io.valid))) return rc;
+    if ((rc = ss.fork())) return rc;
+    // proj_in + pre_norm
+    k_build_xin<<<(int)((R + 255) / 256), 256, 0, st>>>(io.x, io.anchors, io.variances, io.assignment, w.xin, N, R);
+    k_stem_fwd<<<2048, 256, 0, st>>>(w.xin, wt->proj_in_w, wt->proj_in_b, wt->pre_norm_w, wt->pre_norm_b, w.blk[0].hin, R);
+    // W1 / W2 of every block as bf16 MFMA fragments (train_ff_fused.h), one launch
+    dfx::ffused::PackBatch pb{};
+    for (int i = 0; i < wt->depth; ++i)
+      pb.blk[i] = dfx::ffused::PackArgs{wt->blk[i].ff0_w, wt->blk[i].ff0_b, wt->blk[i].ff2_w, wt->blk[i].ff2_b, w.ff_frags[i], w.ff_b1p[i], w.ff_b2p[i],
+                                        dropout_p > 0.f ? 1.0f / (1.0f - dropout_p) : 1.0f, wt->blk[i].norm3_w, wt->blk[i].norm3_b,
+                                        w.ff_b1p[i] + dfx::ffused::B1P_FLOATS, w.ff_b1p[i] + 2 * dfx::ffused::B1P_FLOATS};
+    if (!split)   // + the head's table: the last block's forward kernel computes eps itself
+      pb.head_w = wt->proj_out_w, pb.head_b = wt->proj_out_b, pb.head_g = wt->post_norm_w, pb.head_be = wt->post_norm_b, pb.head_tab = w.head_tab;
+    dfx::ffused::launch_pack(st, pb, wt->depth);
+    // keys and values of every block: one product over the B x 4 context tokens
+    if ((rc = lin(sc, plan.prec, w.ctx, CTXP, w.wkv, nullptr, w.kv, LDKV, BJ, LDKV, CTXP))) return rc;
+    dfx::afused::FoldArgs fo{};
+    fo.kv = w.kv, fo.ldkv = LDKV;
+    for (int i = 0; i < wt->depth; ++i) fo.wq[i] = wt->blk[i].to_q, fo.wo[i] = wt->blk[i].to_out_w, fo.frags[i] = w.at_frags[i];
+    dfx::afused::k_attn_fold<<<dim3(B, wt->depth), 256, 0, sc>>>(fo);
+    if ((rc = ss.join())) return rc;
+    dfx::ffused::FfChain chain{};
+    for (int i = 0; i < wt->depth; ++i) {
+      const dfx_block_weights &bw = wt->blk[i];
+      BlockAct &a = w.blk[i];
+      float *hout = i + 1 < wt->depth ? w.blk[i + 1].hin : w.hfin;
+      // the whole block in two launches (train_attn_fused.h, train_ff_fused.h): h1 = hin + attention(LN2(hin)), hout = h1 + FF(LN3(h1));
+      // q, P, att, xn2, xn3, [a | g], hid never exist in memory
+      dfx::ffused::FfArgs fa{};
+      fa.frags = w.ff_frags[i], fa.b2p = w.ff_b2p[i], fa.g3 = bw.norm3_w, fa.b3 = bw.norm3_b;
+      fa.b1p = w.ff_b1p[i] + (split ? 0 : 2 * dfx::ffused::B1P_FLOATS);   // ff_fwd's table: scaled like its W1 tiles (PackArgs::b1ps)
+      fa.h1 = a.h1, fa.h2 = hout, fa.R = R, fa.B = B, fa.N = N;
+      if (split) {
+        dfx::afused::AttnArgs aa{};
+        aa.frags = w.at_frags[i], aa.valid = w.valid, aa.g2 = bw.norm2_w, aa.b2 = bw.norm2_b, aa.bo = bw.to_out_b;
+        aa.h = a.hin, aa.h1 = a.h1, aa.N = N, aa.R = R;
+        dfx::afused::k_attn_fwd_fused<<<(int)((R / 32 + dfx::afused::NW - 1) / dfx::afused::NW), dfx::afused::NW * 64, 0, st>>>(aa);
+      } else {   // attention sub-block inside the feed-forward kernel's prologue: h1 computed from hin, written once
+        // tile-major rows between the fused kernels (train_ff_fused.h): everything but the stem's output and the head's input
+        // (+ h1 itself only as what the backward kernels want of it: the xhat3 fragments and 1 / std, TL_H1_FRAG)
+        fa.tiled = dfx::ffused::TL_H1 | (i > 0 ? dfx::ffused::TL_HIN : 0) | (i + 1 < wt->depth ? dfx::ffused::TL_H2 : 0) | dfx::ffused::TL_H1_FRAG;
+        fa.at_frags = w.at_frags[i], fa.valid = w.valid, fa.g2 = bw.norm2_w, fa.b2n = bw.norm2_b, fa.bo = bw.to_out_b;
+        fa.hin = a.hin, fa.h1_out = a.h1;
+        if (i + 1 == wt->depth) fa.tiled |= dfx::ffused::TL_HEAD, fa.head_tab = w.head_tab, fa.eps = io.eps;   // post_norm + proj_out in this kernel's epilogue
+        if (dropout_p > 0.f) {   // the two sites of block i (the layer-by-layer path's numbering); bits -> a.p (R x 32 floats, unused by the fused path; 80 B per point needed)
+          fa.dk = dfx::drop_key(dropout_seed, dropout_p), fa.site_att = (unsigned)(2 * i), fa.site_ff = (unsigned)(2 * i + 1);
+          fa.dmask = reinterpret_cast<unsigned *>(a.p);
+        }
+#if !defined(DFX_TRACE_FF) || defined(DFX_TRACE_FF_CHAIN)   // (the phase-trace build stamps single-block launches unless asked for the chain)
+        chain.blk[i] = fa;   // all blocks in ONE launch (k_ff_fwd_chain): collected here, launched behind the last one
+        if (i + 1 == wt->depth) {
+          chain.n = wt->depth;
+          if (dfx::ffused::launch_ff_chain(st, chain)) return dfx::set_error(DFX_ERR_HIP, "train: fused forward chain launch");
+        }
+        continue;
+#endif
+      }
+      if (dfx::ffused::launch_ff<false>(st, fa)) return dfx::set_error(DFX_ERR_HIP, "train: fused feed-forward launch");
+    }
+    if (split) k_head_fwd<<<2048, 256, 0, st>>>(w.hfin, wt->post_norm_w, wt->post_norm_b, wt->proj_out_w, wt->proj_out_b, io.eps, N, R);
+    return dfx::check_launch("denoiser_train_forward");
+  }
+
+  // ---- backward ----
+  int backward_layered(const TrainBwdIo &io) {   // LayerF32, LayerBf16
+    int rc;
+    const int prec = plan.prec;
+    const bool bf = plan.bf_store;
+    const dfx_denoiser_weights *grads = io.grads;
+    // proj_out, post_norm
+    const int nb = (int)((R + EPSB_ROWS - 1) / EPSB_ROWS);
+    k_eps_bwd<<<nb, 128, 0, st>>>(io.d_eps, w.hn, wt->proj_out_w, w.dh2, w.part, N, R);
+    k_sum_parts<<<3 * C / 32, 1024, 0, st>>>(w.part, mut(grads->proj_out_w), nb, 3 * C, 4 * C);
+    k_sum_parts<<<1, 1024, 0, st>>>(w.part + 3 * C, mut(grads->proj_out_b), nb, 3, 4 * C);
+    if ((rc = ln_bwd(st, w, w.dh2, w.hfin, w.st_post, wt->post_norm_w, nullptr, w.dh, mut(grads->post_norm_w), mut(grads->post_norm_b), R))) return rc;
+    DFX_HIP_TRY(hipMemsetAsync(w.dctx, 0, sizeof(float) * (size_t)BJ * CTXP, st));
+    for (int i = wt->depth - 1; i >= 0; --i) {
+      const dfx_block_weights &bw = wt->blk[i], &gw = grads->blk[i];
+      BlockAct &a = w.blk[i];
+      // feed-forward: h2 = h1 + W2 hid + b2, hid = a gelu(g), [a | g] = W1 xn3 + b1
+      if ((rc = wgrad(st, prec, w, w.dh, C, a.hid, FH, mut(gw.ff2_w), mut(gw.ff2_b), C, FH, FH, R, false, bf))) return rc;
+      transpose(st, bw.ff2_w, w.wT, C, FH);                                    // (512, 128)
+      if ((rc = lin(st, prec, w.dh, C, w.wT, nullptr, w.dhid, FH, R, FH, C))) return rc;
+      const Drop dff{dropout_p, dropout_seed, (unsigned)(2 * i + 1)};
+      if (bf) k_geglu_bwd<true><<<(int)((R * FH / 4 + 255) / 256), 256, 0, st>>>(a.ag, w.dhid, w.dwide, FH, R * FH, dff);
+      else k_geglu_bwd<false><<<(int)((R * FH / 4 + 255) / 256), 256, 0, st>>>(a.ag, w.dhid, w.dwide, FH, R * FH, dff);
+      if ((rc = wgrad(st, prec, w, w.dwide, 2 * FH, a.xn3, C, mut(gw.ff0_w), mut(gw.ff0_b), 2 * FH, C, C, R, bf, bf))) return rc;
+      transpose(st, bw.ff0_w, w.wT, 2 * FH, C);                                // (128, 1024)
+      if ((rc = lin(st, prec, w.dwide, 2 * FH, w.wT, nullptr, w.dh2, C, R, C, 2 * FH, nullptr, 0, bf))) return rc;
+      if ((rc = ln_bwd(st, w, w.dh2, a.h1, a.st3, bw.norm3_w, w.dh, w.dh, mut(gw.norm3_w), mut(gw.norm3_b), R))) return rc;
+      // attention: h1 = hin + Wo att + bo
+      const float *dho = w.dh;   // gradient at the output of to_out: dh behind the dropout
+      if (dropout_p > 0.f) {
+        k_dropout<<<(int)((R * C / 4 + 255) / 256), 256, 0, st>>>(w.dh, nullptr, w.dh2, R * C, Drop{dropout_p, dropout_seed, (unsigned)(2 * i)});
+        dho = w.dh2;
+      }
+      if ((rc = wgrad(st, prec, w, dho, C, a.att, C, mut(gw.to_out_w), mut(gw.to_out_b), C, C, C, R, false, bf))) return rc;
+      transpose(st, bw.to_out_w, w.wT, C, C);
+      if ((rc = lin(st, prec, dho, C, w.wT, nullptr, w.datt, C, R, C, C))) return rc;
+      const int nab = (N + ATT_BP - 1) / ATT_BP;
+      if (bf) k_attn_bwd<true><<<dim3(nab, B), 256, 0, st>>>(w.datt, a.q, a.k, a.v, a.p, w.dq, w.apart, N);
+      else k_attn_bwd<false><<<dim3(nab, B), 256, 0, st>>>(w.datt, a.q, a.k, a.v, a.p, w.dq, w.apart, N);
+      k_attn_bwd_finish<<<B, J * C, 0, st>>>(w.apart, w.dk, w.dv, nab);
+      if ((rc = wgrad(st, prec, w, w.dq, C, a.xn2, C, mut(gw.to_q), nullptr, C, C, C, R, bf, bf))) return rc;
+      transpose(st, bw.to_q, w.wT, C, C);
+      if ((rc = lin(st, prec, w.dq, C, w.wT, nullptr, w.dh2, C, R, C, C, nullptr, 0, bf))) return rc;
+      if ((rc = ln_bwd(st, w, w.dh2, a.hin, a.st2, bw.norm2_w, w.dh, w.dh, mut(gw.norm2_w), mut(gw.norm2_b), R))) return rc;
+      // keys / values of the 4 context tokens
+      if ((rc = wgrad(st, prec, w, w.dk, C, w.ctx, CTXP, mut(gw.to_k), nullptr, C, CTXP, CTX, BJ))) return rc;
+      if ((rc = wgrad(st, prec, w, w.dv, C, w.ctx, CTXP, mut(gw.to_v), nullptr, C, CTXP, CTX, BJ))) return rc;
+      DFX_HIP_TRY(hipMemsetAsync(w.wT, 0, sizeof(float) * (size_t)CTXP * C, st));
+      transpose(st, bw.to_k, w.wT, C, CTX);                                    // (522 -> 528 rows of 128)
+      if ((rc = lin(st, prec, w.dk, C, w.wT, nullptr, w.dctx, CTXP, BJ, CTXP, C, w.dctx, CTXP))) return rc;
+      transpose(st, bw.to_v, w.wT, C, CTX);
+      if ((rc = lin(st, prec, w.dv, C, w.wT, nullptr, w.dctx, CTXP, BJ, CTXP, C, w.dctx, CTXP))) return rc;
+    }
+    // pre_norm, proj_in
+    if ((rc = ln_bwd(st, w, w.dh, w.h0, w.st_pre, wt->pre_norm_w, nullptr, w.dh2, mut(grads->pre_norm_w), mut(grads->pre_norm_b), R))) return rc;
+    if ((rc = wgrad(st, prec, w, w.dh2, C, w.xin, XIN, mut(grads->proj_in_w), mut(grads->proj_in_b), C, XIN, 13, R))) return rc;
+    if ((rc = backward_tail(io, w.dh))) return rc;
+    return dfx::check_launch("denoiser_train_backward");
+  }
+
+  int backward_fused(const TrainBwdIo &io) {   // Fused, FusedSplitAttn
+    int rc;
+    const int prec = plan.prec;
+    const bool split = plan.path == dfx::TrainPath::FusedSplitAttn;   // the attention's input gradient as a kernel of its own, fp32 rows between the blocks
+    const dfx_denoiser_weights *grads = io.grads;
+    // Parameter-gradient reductions that nothing on the way back to the input waits for run on the side stream (joined before the return):
+    // the head's and the stem's partial sums — in buffers of their own (w.hn, w.datt: free on the fused path), because the products behind
+    // the block loop use w.part on the caller's stream meanwhile — and the leaves of the finishing kernels behind the block loop.
+    dfx::SideStream ss;
+    if ((rc = ss.open(st, side.bwd_open))) return rc;
+    const dfx::TrainStreams so = ss.on ? side : dfx::TrainStreams{};   // (a caller beyond the side streams' cap gets none: everything on its own stream)
+    hipStream_t sp = ss.side;
+    // proj_out, post_norm
+    const int nbh = (int)((R + HEAD_ROWS - 1) / HEAD_ROWS);
+    float *hp = w.hn;
+    k_head_bwd<<<nbh, 256, 0, st>>>(io.d_eps, w.hfin, wt->post_norm_w, wt->post_norm_b, wt->proj_out_w, w.dh, hp, N, R, !split);
+    auto head_sums = [&](hipStream_t s) {
+      k_sum_parts<<<3 * C / 32, 1024, 0, s>>>(hp, mut(grads->proj_out_w), nbh, 3 * C, HEAD_PART);
+      k_sum_parts_multi<<<2 * C / 32, 1024, 0, s>>>(hp + 3 * C, SumOuts{{mut(grads->post_norm_w), mut(grads->post_norm_b), nullptr, nullptr}}, nbh, C, HEAD_PART);
+      k_sum_parts<<<1, 1024, 0, s>>>(hp + 5 * C, mut(grads->proj_out_b), nbh, 3, HEAD_PART);
+    };
+    const bool head_late = ss.on && !so.head_early;   // with the leaves behind the block loop; else here (on the caller's stream without a side stream)
+    if (!head_late) {
+      if ((rc = ss.fork())) return rc;
+      head_sums(sp);
+    }
+    DFX_HIP_TRY(hipMemsetAsync(w.dctx, 0, sizeof(float) * (size_t)BJ * CTXP, st));
+    float *dh_cur = w.dh;   // the gradient of the residual stream: where the next kernel on the way back finds it
+    auto stem_backward = [&](hipStream_t s, float *part) {   // pre_norm, proj_in: reads dh_cur, the input rows and the weights
+      const int nb = (int)((R + STEM_ROWS - 1) / STEM_ROWS);
+      k_stem_bwd<<<nb, 256, 0, s>>>(dh_cur, w.xin, wt->proj_in_w, wt->proj_in_b, wt->pre_norm_w, part, R);
+      k_sum_parts<<<C * 13 / 32, 1024, 0, s>>>(part, mut(grads->proj_in_w), nb, C * 13, 2048);
+      k_sum_parts_multi<<<3 * C / 32, 1024, 0, s>>>(part + C * 13, SumOuts{{mut(grads->proj_in_b), mut(grads->pre_norm_w), mut(grads->pre_norm_b), nullptr}}, nb, C, 2048);
+    };
+    for (int i = wt->depth - 1; i >= 0; --i) {
+      const dfx_block_weights &bw = wt->blk[i], &gw = grads->blk[i];
+      BlockAct &a = w.blk[i];
+      // feed-forward: h2 = h1 + W2 hid + b2, hid = a gelu(g), [a | g] = W1 xn3 + b1
+      // one pass over the points: xn3 = LN3(h1) and [a | g] recomputed, d hid = W2^T dh, GEGLU backward, dxn3 = W1^T d[a | g], LayerNorm3
+      // backward -> dh1; hid, d[a | g] and xn3 leave the kernel once, as bf16, for the two weight-gradient products
+      dfx::ffused::FfArgs fa{};
+      fa.frags = w.ff_frags[i], fa.b1p = w.ff_b1p[i], fa.b2p = w.ff_b2p[i], fa.g3 = bw.norm3_w, fa.b3 = bw.norm3_b;
+      fa.h1 = a.h1, fa.dh = dh_cur, fa.pk = reinterpret_cast<uint4 *>(w.dwide), fa.dh1 = w.dh2, fa.cpart = w.cpart[i], fa.R = R, fa.B = B, fa.N = N;
+      const float *dh_in_blk = dh_cur;
+      if (!split) {   // the attention's input gradient in the same kernel (dh1 leaves as fragments for the parameter kernel)
+        // The gradient travels from the head through the blocks as bf16-pair tiles (train_ff_fused.h, TL_DH_HL; k_head_bwd writes the pair format
+        // too), alternating between w.dh and w.dh2 (k_ff_wgrad reads block i's INCOMING gradient after k_ff<true> has written the outgoing one);
+        // block 0 writes the fp32 rows the stem reads (dh_cur behind the loop).  + the layouts the forward left behind
+        fa.tiled = dfx::ffused::TL_H1 | (i > 0 ? dfx::ffused::TL_HIN | dfx::ffused::TL_DHIN | dfx::ffused::TL_DHIN_HL : 0) |
+                   (i + 1 < wt->depth ? dfx::ffused::TL_DH : 0) | dfx::ffused::TL_DH_HL | dfx::ffused::TL_H1_FRAG;
+        fa.at_frags = w.at_frags[i], fa.valid = w.valid, fa.g2 = bw.norm2_w, fa.b2n = bw.norm2_b, fa.bo = bw.to_out_b;
+        fa.hin = a.hin, fa.dh_in = dh_cur = (dh_cur == w.dh ? w.dh2 : w.dh);
+        fa.pk2 = reinterpret_cast<uint4 *>(w.dq);   // xn2 / dh1 as fragments for the parameter kernel (w.dq: free in this path)
+      }
+      if (dropout_p > 0.f) {   // the bits the forward left in a.p (the plan admits dropout only with the attention inside these kernels)
+        fa.dk = dfx::drop_key(dropout_seed, dropout_p), fa.site_att = (unsigned)(2 * i), fa.site_ff = (unsigned)(2 * i + 1);
+        fa.dmask = reinterpret_cast<unsigned *>(a.p);
+      }
+      if (dfx::ffused::launch_ff<true>(st, fa)) return dfx::set_error(DFX_ERR_HIP, "train: fused feed-forward backward launch");
+      if (i == 0 && so.stem_early) {   // w.dh is final: pre_norm / proj_in backward beside the rest of the block's parameter kernels
+        if ((rc = ss.fork())) return rc;
+        stem_backward(sp, w.datt);
+      }
+      // (with the attention's input gradient in the same kernel, the six column sums of every block are one launch behind the loop)
+      if (split)
+        k_sum_parts_multi<<<3 * C / 32, 1024, 0, st>>>(w.cpart[i], SumOuts{{nullptr, nullptr, mut(gw.ff2_b), nullptr}}, (int)dfx::ffused::ff_groups(B, N), C, 3 * C);
+      // dW1, db1, dW2: weight-stationary, hid and d[a | g] recomputed from the tiles k_ff<true> left in w.dwide; the slab partials of every
+      // block are summed in one launch behind the loop
+      {
+        // (without the attention inside — dfx_debug_train_fused(2) — k_ff<true> reads fp32 rows and leaves both fragment sets in w.dwide)
+        dfx::ffused::FwArgs wa{w.ff_frags[i], w.ff_b1p[i] + dfx::ffused::B1P_FLOATS,
+                               split ? reinterpret_cast<const uint4 *>(w.dwide) : reinterpret_cast<const uint4 *>(a.h1), w.ffw_part[i], w.ffw_bpart[i],
+                               R / 32, w.ffw_slabs, dropout_p > 0.f ? reinterpret_cast<const unsigned *>(a.p) : nullptr,
+                               split ? reinterpret_cast<const uint4 *>(w.dwide) + dfx::ffused::PK_TILE_U4 / 2 : reinterpret_cast<const uint4 *>(dh_in_blk)};
+        if (dfx::ffused::launch_ff_wgrad(st, wa)) return dfx::set_error(DFX_ERR_HIP, "train: feed-forward weight-gradient launch");
+      }
+      // attention + LayerNorm2 (train_attn_fused.h): parameter side first (reads dh1 = w.dh2), then dh -> w.dh
+      dfx::afused::AttnArgs aa{};
+      aa.frags = w.at_frags[i], aa.valid = w.valid, aa.g2 = bw.norm2_w, aa.b2 = bw.norm2_b, aa.bo = bw.to_out_b;
+      aa.h = a.hin, aa.dh1 = w.dh2, aa.dh = w.dh, aa.part = w.at_part[i], aa.cpart = w.cpart[i], aa.N = N, aa.split = w.at_split, aa.R = R;
+      aa.pk2 = split ? nullptr : reinterpret_cast<const uint4 *>(w.dq);
+      if (split) {
+        dfx::afused::k_attn_bwd_param<false><<<B * w.at_split, dfx::afused::NW * 64, 0, st>>>(aa);
+        const int np = dfx::afused::dx_groups(R);
+        dfx::afused::k_attn_bwd_dx<<<np, dfx::afused::NW * 64, 0, st>>>(aa);
+        k_sum_parts_multi<<<3 * C / 32, 1024, 0, st>>>(w.cpart[i], SumOuts{{mut(gw.norm2_w), mut(gw.norm2_b), mut(gw.to_out_b), nullptr}}, np, C, 3 * C);
+      } else {
+        dfx::afused::k_attn_bwd_param<true><<<B * w.at_split, dfx::afused::NW * 64, 0, st>>>(aa);
+      }
+    }
+    {
+      // parameter gradients of ALL blocks from the partials the block loop left behind: one launch per kind (keys / values of all blocks: one pair
+      // of products)
+      const int LDKV0 = 2 * wt->depth * C;
+      dfx::ffused::FwFinishBatch fb{};
+      dfx::afused::UnfoldBatch ub{};
+      SumJobs sj{};
+      for (int i = 0; i < wt->depth; ++i) {
+        const dfx_block_weights &bw = wt->blk[i], &gw = grads->blk[i];
+        fb.blk[i] = dfx::ffused::FwFinishArgs{w.ffw_part[i], w.ffw_bpart[i], mut(gw.ff0_w), mut(gw.ff0_b), mut(gw.ff2_w), w.ffw_slabs,
+                                              dropout_p > 0.f ? 1.0f / (1.0f - dropout_p) : 1.0f, bw.norm3_w, bw.norm3_b, bw.ff0_w,
+                                              w.ffw_lnpart[i], mut(gw.norm3_w), mut(gw.norm3_b)};   // (d gamma3 / d beta3: k_ln3_param behind the slab sums)
+        ub.blk[i] = dfx::afused::UnfoldArgs{w.at_part[i], w.kv + 2 * i * C, w.kv + (2 * i + 1) * C, bw.to_q, bw.to_out_w, w.dkv + 2 * i * C, w.dkv + (2 * i + 1) * C,
+                                            mut(gw.to_q), mut(gw.to_out_w), w.at_sum[i], B, w.at_split, LDKV0};
+        sj.part[i] = w.cpart[i];
+        float *o6[6] = {nullptr, nullptr, mut(gw.ff2_b), mut(gw.norm2_w), mut(gw.norm2_b), mut(gw.to_out_b)};   // (rows 0, 1 of the partials are unused)
+        for (int q = 0; q < 6; ++q) sj.o[i][q] = o6[q];
+      }
+      // the chain towards the context gradient (unfold_kv -> d Wk / d Wv / d ctx -> time-embedding MLP) stays on the caller's stream; the
+      // leaves (slab sums of dW1 / dW2, dWq / dWo, the six column sums per block) go beside it
+      if ((rc = ss.fork())) return rc;
+      hipStream_t sl = so.leaves ? sp : st;
+      dfx::afused::k_attn_unfold_kv<<<dim3(dfx::afused::J, B, wt->depth), 256, 0, st>>>(ub);
+      if (so.stem_end) stem_backward(sp, w.datt);
+      dfx::ffused::launch_ff_wgrad_finish(sl, fb, wt->depth);
+      if (!split) k_sum_parts_jobs<<<wt->depth * 6 * (C / 32), 1024, 0, sl>>>(sj, (int)dfx::ffused::ff_groups(B, N), C, 6 * C);
+      if (head_late) head_sums(sp);
+      if ((rc = ss.fork())) return rc;   // (k_attn_unfold_w reads the per-shape sums k_attn_unfold_kv leaves in at_sum)
+      dfx::afused::k_attn_unfold_w<<<dim3(C / dfx::afused::UW_D, 1, wt->depth), 1024, 0, sl>>>(ub);
+      // d Wk, d Wv of every block and d ctx from the side-by-side key / value gradients
+      const int n2 = 2 * wt->depth, LDKV = n2 * C;
+      if ((rc = wgrad(st, prec, w, w.dkv, LDKV, w.ctx, CTXP, w.dwkv, nullptr, LDKV, CTXP, CTXP, BJ))) return rc;
+      KvMutPtrs gp{};
+      for (int i = 0; i < wt->depth; ++i) gp.p[2 * i] = mut(grads->blk[i].to_k), gp.p[2 * i + 1] = mut(grads->blk[i].to_v);
+      k_unpack_kv<<<(n2 * C * CTX + 255) / 256, 256, 0, st>>>(w.dwkv, gp, n2);
+      transpose(st, w.wkv, w.wkvT, LDKV, CTXP);                                  // (528 rows of 2 depth x 128)
+      if ((rc = lin(st, prec, w.dkv, LDKV, w.wkvT, nullptr, w.dctx, CTXP, BJ, CTXP, LDKV))) return rc;
+    }
+    // pre_norm, proj_in
+    if (!so.stem_early && !so.stem_end) stem_backward(st, w.part);
+    if ((rc = backward_tail(io, dh_cur))) return rc;
+    if ((rc = ss.join())) return rc;
+    return dfx::check_launch("denoiser_train_backward");
+  }
+
+  // dh: the gradient behind pre_norm, final and row-major on either path
+  int backward_tail(const TrainBwdIo &io, const float *dh) {
+    int rc;
+    const int prec = plan.prec;
+    const dfx_denoiser_weights *grads = io.grads;
+    // gradient at the input rows (optional)
+    if (io.d_x || io.d_variances) k_stem_dx<<<2048, 256, 0, st>>>(dh, w.xin, wt->proj_in_w, wt->proj_in_b, wt->pre_norm_w, io.d_x, io.d_variances, N, R);
+    // context -> part codes, (mean, var), time embedding MLP
+    k_ctx_bwd<<<(B * CTX + 255) / 256, 256, 0, st>>>(w.dctx, io.d_ctx_code, io.d_ctx_mv, w.dte_out, B);
+    if ((rc = wgrad(st, prec, w, w.dte_out, TE, w.te_hid, TEH, mut(grads->te2_w), mut(grads->te2_b), TE, TEH, TEH, B))) return rc;
+    transpose(st, wt->te2_w, w.wT, TE, TEH);                                   // (1024, 256)
+    if ((rc = lin(st, prec, w.dte_out, TE, w.wT, nullptr, w.dte_hid, TEH, B, TEH, TE))) return rc;
+    k_geglu_bwd<false><<<(int)(((long long)B * TEH / 4 + 255) / 256), 256, 0, st>>>(w.te_ag, w.dte_hid, w.dte_ag, TEH, (long long)B * TEH, Drop{dropout_p, dropout_seed, SITE_TE});
+    return wgrad(st, prec, w, w.dte_ag, 2 * TEH, w.te_in, TE, mut(grads->te0_w), mut(grads->te0_b), 2 * TEH, TE, TE, B);
+  }
+};
 }  // namespace
 
 extern "C" {
@@ -2236,8 +2606,7 @@ int dfx_denoiser_train_forward(const dfx_denoiser_weights *wt, void *workspace, 
   if (rc) return rc;
   DFX_REQUIRE(precision == DFX_PREC_F32 || precision == DFX_PREC_BF16, "denoiser_train_forward: precision %d", precision);
   DFX_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "denoiser_train_forward: dropout_p %g", (double)dropout_p);
-  g_prec = precision;
-  t_ff_fused = g_ff_fused, t_attn_in_ff = g_attn_in_ff;
+  const dfx::TrainPlan plan = dfx::plan_train(precision, dropout_p, B, N, dfx::TrainSwitches{g_ff_fused, g_attn_in_ff, g_train_streams});
   {
     std::lock_guard<std::mutex> lk(g_path_mu);
     // bounded table: a record is overwritten by the next forward into the same workspace (stale addresses cost nothing); when 4096
@@ -2249,138 +2618,13 @@ int dfx_denoiser_train_forward(const dfx_denoiser_weights *wt, void *workspace, 
         if (it->second.seq < oldest->second.seq) oldest = it;
       g_path.erase(oldest);
     }
-    g_path[workspace] = PathRecord{t_ff_fused, t_attn_in_ff, precision, dropout_p, B, N, ++g_path_seq};
+    g_path[workspace] = PathRecord{plan.path, precision, dropout_p, B, N, ++g_path_seq};
   }
-  const bool bf = bf_store((long long)B * N);
   DFX_REQUIRE(x && t && ctx_code && ctx_mv && anchors && variances && assignment && eps, "denoiser_train_forward: null tensor");
-  hipStream_t st = dfx::as_stream(stream);
-  TrainWs w;
-  carve(w, workspace, B, N, wt->depth);
-  const long long R = (long long)B * N;
-  const int BJ = B * J;
-  const bool fused_ends = ff_fused(bf, dropout_p, R, N);
-  t_last_path = fused_ends ? (dropout_p > 0.f ? "fused_bf16_dropout" : "fused_bf16")
-                           : bf ? (dropout_p > 0.f ? "layer_bf16_dropout" : "layer_bf16") : (dropout_p > 0.f ? "layer_f32_dropout" : "layer_f32");
-  // Two branches meet in front of the first block: the points (input rows, proj_in + pre_norm, the blocks' weight fragments) on the caller's
-  // stream, the context (time embedding -> context rows -> keys / values of every block -> folded attention operands) on the side stream
-  dfx::SideStream ss;
-  if ((rc = ss.open(st, (ss_mask() & SS_FWD_CTX) && fused_ends))) return rc;
-  hipStream_t sc = ss.side;
-  if ((rc = ss.fork())) return rc;
-  // time embedding -> context rows
-  k_timestep_embedding<<<(B * TE + 255) / 256, 256, 0, sc>>>(t, w.te_in, B);
-  if ((rc = lin(sc, w.te_in, TE, wt->te0_w, wt->te0_b, w.te_ag, 2 * TEH, B, 2 * TEH, TE))) return rc;
-  k_geglu_fwd<false><<<(int)(((long long)B * TEH / 4 + 255) / 256), 256, 0, sc>>>(w.te_ag, w.te_hid, TEH, (long long)B * TEH, Drop{dropout_p, dropout_seed, SITE_TE});
-  if ((rc = lin(sc, w.te_hid, TEH, wt->te2_w, wt->te2_b, w.te_out, TE, B, TE, TEH))) return rc;
-  k_build_ctx<<<(BJ * CTXP + 255) / 256, 256, 0, sc>>>(ctx_code, ctx_mv, w.te_out, w.ctx, B);
-  const int LDKV = 2 * wt->depth * C;
-  if (fused_ends) {   // packed key / value weights of every block (the side stream's product below reads them: second fork)
-    KvPtrs kp{};
-    for (int i = 0; i < wt->depth; ++i) kp.p[2 * i] = wt->blk[i].to_k, kp.p[2 * i + 1] = wt->blk[i].to_v;
-    k_pack_kv<<<(2 * wt->depth * C * CTXP + 255) / 256, 256, 0, st>>>(kp, w.wkv, 2 * wt->depth);
-  }
-  if (valid) DFX_HIP_TRY(hipMemcpyAsync(w.valid, valid, sizeof(float) * BJ, hipMemcpyDeviceToDevice, st));
-  else DFX_HIP_TRY(hipMemsetAsync(w.valid, 0x3f, sizeof(float) * BJ, st));   // any non-zero value = keep
-  if ((rc = ss.fork())) return rc;
-  // proj_in + pre_norm
-  k_build_xin<<<(int)((R + 255) / 256), 256, 0, st>>>(x, anchors, variances, assignment, w.xin, N, R);
-  if (fused_ends) {
-    k_stem_fwd<<<2048, 256, 0, st>>>(w.xin, wt->proj_in_w, wt->proj_in_b, wt->pre_norm_w, wt->pre_norm_b, w.blk[0].hin, R);
-    // W1 / W2 of every block as bf16 MFMA fragments (train_ff_fused.h), one launch
-    dfx::ffused::PackBatch pb{};
-    for (int i = 0; i < wt->depth; ++i)
-      pb.blk[i] = dfx::ffused::PackArgs{wt->blk[i].ff0_w, wt->blk[i].ff0_b, wt->blk[i].ff2_w, wt->blk[i].ff2_b, w.ff_frags[i], w.ff_b1p[i], w.ff_b2p[i],
-                                        dropout_p > 0.f ? 1.0f / (1.0f - dropout_p) : 1.0f, wt->blk[i].norm3_w, wt->blk[i].norm3_b,
-                                        w.ff_b1p[i] + dfx::ffused::B1P_FLOATS, w.ff_b1p[i] + 2 * dfx::ffused::B1P_FLOATS};
-    if (t_attn_in_ff)   // + the head's table: the last block's forward kernel computes eps itself
-      pb.head_w = wt->proj_out_w, pb.head_b = wt->proj_out_b, pb.head_g = wt->post_norm_w, pb.head_be = wt->post_norm_b, pb.head_tab = w.head_tab;
-    dfx::ffused::launch_pack(st, pb, wt->depth);
-  } else {
-    k_pad_cols<<<(C * XIN + 255) / 256, 256, 0, st>>>(wt->proj_in_w, w.wpad, C, 13, XIN);
-    if ((rc = lin(st, w.xin, XIN, w.wpad, wt->proj_in_b, w.h0, C, R, C, XIN))) return rc;
-    k_ln_fwd<false><<<(int)((R + 7) / 8), 256, 0, st>>>(w.h0, wt->pre_norm_w, wt->pre_norm_b, w.blk[0].hin, w.st_pre, R);
-  }
-  if (fused_ends) {   // keys and values of every block: one product over the B x 4 context tokens
-    if ((rc = lin(sc, w.ctx, CTXP, w.wkv, nullptr, w.kv, LDKV, BJ, LDKV, CTXP))) return rc;
-    dfx::afused::FoldArgs fo{};
-    fo.kv = w.kv, fo.ldkv = LDKV;
-    for (int i = 0; i < wt->depth; ++i) fo.wq[i] = wt->blk[i].to_q, fo.wo[i] = wt->blk[i].to_out_w, fo.frags[i] = w.at_frags[i];
-    dfx::afused::k_attn_fold<<<dim3(B, wt->depth), 256, 0, sc>>>(fo);
-  }
-  if ((rc = ss.join())) return rc;
-  dfx::ffused::FfChain chain{};
-  for (int i = 0; i < wt->depth; ++i) {
-    const dfx_block_weights &bw = wt->blk[i];
-    BlockAct &a = w.blk[i];
-    float *hout = i + 1 < wt->depth ? w.blk[i + 1].hin : w.hfin;
-    const bool fused = ff_fused(bf, dropout_p, R, N);
-    if (fused) {
-      // the whole block in two launches (train_attn_fused.h, train_ff_fused.h): h1 = hin + attention(LN2(hin)), hout = h1 + FF(LN3(h1));
-      // q, P, att, xn2, xn3, [a | g], hid never exist in memory
-      dfx::ffused::FfArgs fa{};
-      fa.frags = w.ff_frags[i], fa.b2p = w.ff_b2p[i], fa.g3 = bw.norm3_w, fa.b3 = bw.norm3_b;
-      fa.b1p = w.ff_b1p[i] + (t_attn_in_ff ? 2 * dfx::ffused::B1P_FLOATS : 0);   // ff_fwd's table: scaled like its W1 tiles (PackArgs::b1ps)
-      fa.h1 = a.h1, fa.h2 = hout, fa.R = R, fa.B = B, fa.N = N;
-      // tile-major rows between the fused kernels (train_ff_fused.h): everything but the stem's output and the head's input
-      // (+ h1 itself only as what the backward kernels want of it: the xhat3 fragments and 1 / std, TL_H1_FRAG)
-      if (t_attn_in_ff) fa.tiled = dfx::ffused::TL_H1 | (i > 0 ? dfx::ffused::TL_HIN : 0) | (i + 1 < wt->depth ? dfx::ffused::TL_H2 : 0) | dfx::ffused::TL_H1_FRAG;
-      if (t_attn_in_ff) {   // attention sub-block inside the feed-forward kernel's prologue: h1 computed from hin, written once
-        fa.at_frags = w.at_frags[i], fa.valid = w.valid, fa.g2 = bw.norm2_w, fa.b2n = bw.norm2_b, fa.bo = bw.to_out_b;
-        fa.hin = a.hin, fa.h1_out = a.h1;
-        if (i + 1 == wt->depth) fa.tiled |= dfx::ffused::TL_HEAD, fa.head_tab = w.head_tab, fa.eps = eps;   // post_norm + proj_out in this kernel's epilogue
-        if (dropout_p > 0.f) {   // the two sites of block i (the layer-by-layer path's numbering); bits -> a.p (R x 32 floats, unused by the fused path; 80 B per point needed)
-          fa.dk = dfx::drop_key(dropout_seed, dropout_p), fa.site_att = (unsigned)(2 * i), fa.site_ff = (unsigned)(2 * i + 1);
-          fa.dmask = reinterpret_cast<unsigned *>(a.p);
-        }
-      } else {
-        dfx::afused::AttnArgs aa{};
-        aa.frags = w.at_frags[i], aa.valid = w.valid, aa.g2 = bw.norm2_w, aa.b2 = bw.norm2_b, aa.bo = bw.to_out_b;
-        aa.h = a.hin, aa.h1 = a.h1, aa.N = N, aa.R = R;
-        dfx::afused::k_attn_fwd_fused<<<(int)((R / 32 + dfx::afused::NW - 1) / dfx::afused::NW), dfx::afused::NW * 64, 0, st>>>(aa);
-      }
-#if !defined(DFX_TRACE_FF) || defined(DFX_TRACE_FF_CHAIN)   // (the phase-trace build stamps single-block launches unless asked for the chain)
-      if (t_attn_in_ff) {   // all blocks in ONE launch (k_ff_fwd_chain): collected here, launched behind the last one
-        chain.blk[i] = fa;
-        if (i + 1 == wt->depth) {
-          chain.n = wt->depth;
-          if (dfx::ffused::launch_ff_chain(st, chain)) return dfx::set_error(DFX_ERR_HIP, "train: fused forward chain launch");
-        }
-        continue;
-      }
-#endif
-      if (dfx::ffused::launch_ff<false>(st, fa)) return dfx::set_error(DFX_ERR_HIP, "train: fused feed-forward launch");
-      continue;
-    }
-    if (!fused) {
-      if (bf) k_ln_fwd<true><<<(int)((R + 7) / 8), 256, 0, st>>>(a.hin, bw.norm2_w, bw.norm2_b, a.xn2, a.st2, R);
-      else k_ln_fwd<false><<<(int)((R + 7) / 8), 256, 0, st>>>(a.hin, bw.norm2_w, bw.norm2_b, a.xn2, a.st2, R);
-      if ((rc = lin(st, a.xn2, C, bw.to_q, nullptr, a.q, C, R, C, C, nullptr, 0, bf))) return rc;
-    }
-    k_pad_cols<<<(C * CTXP + 255) / 256, 256, 0, st>>>(bw.to_k, w.wpad, C, CTX, CTXP);
-    if ((rc = lin(st, w.ctx, CTXP, w.wpad, nullptr, a.k, C, BJ, C, CTXP))) return rc;
-    k_pad_cols<<<(C * CTXP + 255) / 256, 256, 0, st>>>(bw.to_v, w.wpad, C, CTX, CTXP);
-    if ((rc = lin(st, w.ctx, CTXP, w.wpad, nullptr, a.v, C, BJ, C, CTXP))) return rc;
-    if (bf) k_attn_fwd<true><<<dim3(N / 32, B), 256, 0, st>>>(a.q, a.k, a.v, w.valid, a.p, a.att, N);
-    else k_attn_fwd<false><<<dim3(N / 32, B), 256, 0, st>>>(a.q, a.k, a.v, w.valid, a.p, a.att, N);
-    if (dropout_p > 0.f) {   // h1 = dropout(att Wo^T + bo) + hin   (attention.py:177: to_out = Sequential(Linear, Dropout))
-      if ((rc = lin(st, a.att, C, bw.to_out_w, bw.to_out_b, a.h1, C, R, C, C, nullptr, 0, bf))) return rc;
-      k_dropout<<<(int)((R * C / 4 + 255) / 256), 256, 0, st>>>(a.h1, a.hin, a.h1, R * C, Drop{dropout_p, dropout_seed, (unsigned)(2 * i)});
-    } else if ((rc = lin(st, a.att, C, bw.to_out_w, bw.to_out_b, a.h1, C, R, C, C, a.hin, C, bf))) return rc;
-    if (bf) k_ln_fwd<true><<<(int)((R + 7) / 8), 256, 0, st>>>(a.h1, bw.norm3_w, bw.norm3_b, a.xn3, a.st3, R);
-    else k_ln_fwd<false><<<(int)((R + 7) / 8), 256, 0, st>>>(a.h1, bw.norm3_w, bw.norm3_b, a.xn3, a.st3, R);
-    if ((rc = lin(st, a.xn3, C, bw.ff0_w, bw.ff0_b, a.ag, 2 * FH, R, 2 * FH, C, nullptr, 0, bf, bf && AG_BF16))) return rc;
-    const Drop dff{dropout_p, dropout_seed, (unsigned)(2 * i + 1)};
-    if (bf) k_geglu_fwd<true><<<(int)((R * FH / 4 + 255) / 256), 256, 0, st>>>(a.ag, a.hid, FH, R * FH, dff);
-    else k_geglu_fwd<false><<<(int)((R * FH / 4 + 255) / 256), 256, 0, st>>>(a.ag, a.hid, FH, R * FH, dff);
-    if ((rc = lin(st, a.hid, FH, bw.ff2_w, bw.ff2_b, hout, C, R, C, FH, a.h1, C, bf))) return rc;
-  }
-  if (fused_ends) {
-    if (!t_attn_in_ff) k_head_fwd<<<2048, 256, 0, st>>>(w.hfin, wt->post_norm_w, wt->post_norm_b, wt->proj_out_w, wt->proj_out_b, eps, N, R);
-  } else {
-    k_ln_fwd<false><<<(int)((R + 7) / 8), 256, 0, st>>>(w.hfin, wt->post_norm_w, wt->post_norm_b, w.hn, w.st_post, R);
-    k_eps_fwd<<<(int)((R + 7) / 8), 256, 0, st>>>(w.hn, wt->proj_out_w, wt->proj_out_b, eps, N, R);
-  }
-  return dfx::check_launch("denoiser_train_forward");
+  t_last_path = plan.record;
+  TrainStep s(wt, workspace, B, N, plan, dropout_p, dropout_seed, stream);
+  const TrainFwdIo io{x, t, ctx_code, ctx_mv, anchors, variances, valid, assignment, eps};
+  return plan.fused() ? s.forward_fused(io) : s.forward_layered(io);
 }
 
 int dfx_denoiser_train_backward(const dfx_denoiser_weights *wt, void *workspace, size_t workspace_bytes,
@@ -2391,7 +2635,7 @@ int dfx_denoiser_train_backward(const dfx_denoiser_weights *wt, void *workspace,
   if (rc) return rc;
   DFX_REQUIRE(precision == DFX_PREC_F32 || precision == DFX_PREC_BF16, "denoiser_train_backward: precision %d", precision);
   DFX_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "denoiser_train_backward: dropout_p %g", (double)dropout_p);
-  g_prec = precision;
+  dfx::TrainPath path;
   {
     std::lock_guard<std::mutex> lk(g_path_mu);
     const auto it = g_path.find(workspace);
@@ -2400,212 +2644,13 @@ int dfx_denoiser_train_backward(const dfx_denoiser_weights *wt, void *workspace,
     DFX_REQUIRE(r.prec == precision && r.dropout_p == dropout_p && r.B == B && r.N == N,
                 "denoiser_train_backward: the forward of this workspace ran with precision %d, dropout %g, B %d, N %d", r.prec,
                 (double)r.dropout_p, r.B, r.N);
-    t_ff_fused = r.fused, t_attn_in_ff = r.attn_in_ff;
+    path = r.path;
   }
-  const bool bf = bf_store((long long)B * N);
   DFX_REQUIRE(d_eps && grads, "denoiser_train_backward: null tensor");
-  hipStream_t st = dfx::as_stream(stream);
-  TrainWs w;
-  carve(w, workspace, B, N, wt->depth);
-  const long long R = (long long)B * N;
-  const int BJ = B * J;
-  // proj_out, post_norm
-  const bool fused_ends = ff_fused(bf, dropout_p, R, N);
-  // Parameter-gradient reductions that nothing on the way back to the input waits for run on the side stream (joined before the return):
-  // the head's and the stem's partial sums — in buffers of their own (w.hn, w.datt: free on the fused path), because the products behind
-  // the block loop use w.part on the caller's stream meanwhile — and the leaves of the finishing kernels behind the block loop.
-  dfx::SideStream ss;
-  const int ssm = ss_mask();
-  if ((rc = ss.open(st, (ssm & ~SS_FWD_CTX) && ssm != 0 && fused_ends))) return rc;
-  hipStream_t sp = ss.side;
-  std::function<void(hipStream_t)> head_sums;
-  bool head_done = false;
-  if (fused_ends) {
-    const int nb = (int)((R + HEAD_ROWS - 1) / HEAD_ROWS);
-    float *hp = w.hn;
-    k_head_bwd<<<nb, 256, 0, st>>>(d_eps, w.hfin, wt->post_norm_w, wt->post_norm_b, wt->proj_out_w, w.dh, hp, N, R, t_attn_in_ff);
-    head_sums = [&, nb, hp](hipStream_t s) {
-      k_sum_parts<<<3 * C / 32, 1024, 0, s>>>(hp, mut(grads->proj_out_w), nb, 3 * C, HEAD_PART);
-      k_sum_parts_multi<<<2 * C / 32, 1024, 0, s>>>(hp + 3 * C, SumOuts{{mut(grads->post_norm_w), mut(grads->post_norm_b), nullptr, nullptr}}, nb, C, HEAD_PART);
-      k_sum_parts<<<1, 1024, 0, s>>>(hp + 5 * C, mut(grads->proj_out_b), nb, 3, HEAD_PART);
-    };
-    if (!ss.on) head_sums(st), head_done = true;
-    else if (ssm & SS_HEAD_EARLY) {
-      if ((rc = ss.fork())) return rc;
-      head_sums(sp), head_done = true;
-    }
-  } else {
-    const int nb = (int)((R + EPSB_ROWS - 1) / EPSB_ROWS);
-    k_eps_bwd<<<nb, 128, 0, st>>>(d_eps, w.hn, wt->proj_out_w, w.dh2, w.part, N, R);
-    k_sum_parts<<<3 * C / 32, 1024, 0, st>>>(w.part, mut(grads->proj_out_w), nb, 3 * C, 4 * C);
-    k_sum_parts<<<1, 1024, 0, st>>>(w.part + 3 * C, mut(grads->proj_out_b), nb, 3, 4 * C);
-  }
-  if (!fused_ends && (rc = ln_bwd(st, w, w.dh2, w.hfin, w.st_post, wt->post_norm_w, nullptr, w.dh, mut(grads->post_norm_w), mut(grads->post_norm_b), R))) return rc;
-  DFX_HIP_TRY(hipMemsetAsync(w.dctx, 0, sizeof(float) * (size_t)BJ * CTXP, st));
-  bool stem_done = false;
-  const bool dx_in_ff_all = t_attn_in_ff;
-  float *dh_cur = w.dh;   // the gradient of the residual stream: where the next kernel on the way back finds it
-  auto stem_backward = [&](hipStream_t s, float *part) {   // pre_norm, proj_in (fused ends): reads w.dh, the input rows and the weights
-    const int nb = (int)((R + STEM_ROWS - 1) / STEM_ROWS);
-    k_stem_bwd<<<nb, 256, 0, s>>>(dh_cur, w.xin, wt->proj_in_w, wt->proj_in_b, wt->pre_norm_w, part, R);
-    k_sum_parts<<<C * 13 / 32, 1024, 0, s>>>(part, mut(grads->proj_in_w), nb, C * 13, 2048);
-    k_sum_parts_multi<<<3 * C / 32, 1024, 0, s>>>(part + C * 13, SumOuts{{mut(grads->proj_in_b), mut(grads->pre_norm_w), mut(grads->pre_norm_b), nullptr}}, nb, C, 2048);
-  };
-  for (int i = wt->depth - 1; i >= 0; --i) {
-    const dfx_block_weights &bw = wt->blk[i], &gw = grads->blk[i];
-    BlockAct &a = w.blk[i];
-    // feed-forward: h2 = h1 + W2 hid + b2, hid = a gelu(g), [a | g] = W1 xn3 + b1
-    const bool fused = ff_fused(bf, dropout_p, R, N);
-    if (fused) {
-      // one pass over the points: xn3 = LN3(h1) and [a | g] recomputed, d hid = W2^T dh, GEGLU backward, dxn3 = W1^T d[a | g], LayerNorm3
-      // backward -> dh1; hid, d[a | g] and xn3 leave the kernel once, as bf16, for the two weight-gradient products
-      dfx::ffused::FfArgs fa{};
-      fa.frags = w.ff_frags[i], fa.b1p = w.ff_b1p[i], fa.b2p = w.ff_b2p[i], fa.g3 = bw.norm3_w, fa.b3 = bw.norm3_b;
-      fa.h1 = a.h1, fa.dh = dh_cur, fa.pk = reinterpret_cast<uint4 *>(w.dwide), fa.dh1 = w.dh2, fa.cpart = w.cpart[i], fa.R = R, fa.B = B, fa.N = N;
-      const bool dx_in_ff = t_attn_in_ff;   // the attention's input gradient in the same kernel (dh1 leaves as fragments for the parameter kernel)
-      // With the attention inside, the gradient travels from the head through the blocks as bf16-pair tiles (train_ff_fused.h, TL_DH_HL), alternating
-      // between w.dh and w.dh2 (k_ff_wgrad reads block i's INCOMING gradient after k_ff<true> has written the outgoing one); block 0 writes the fp32
-      // rows the stem reads (dh_cur behind the loop)
-      const bool hl_in = dx_in_ff, hl_out = dx_in_ff && i > 0;   // (k_head_bwd writes the pair format too; block 0 hands fp32 rows to the stem)
-      const float *dh_in_blk = dh_cur;
-      if (t_attn_in_ff)   // + the layouts the forward left behind
-        fa.tiled = dfx::ffused::TL_H1 | (i > 0 ? dfx::ffused::TL_HIN | dfx::ffused::TL_DHIN : 0) | (i + 1 < wt->depth ? dfx::ffused::TL_DH : 0) |
-                   (hl_in ? dfx::ffused::TL_DH_HL : 0) | (hl_out ? dfx::ffused::TL_DHIN_HL : 0) | dfx::ffused::TL_H1_FRAG;
-      if (dx_in_ff) {
-        fa.at_frags = w.at_frags[i], fa.valid = w.valid, fa.g2 = bw.norm2_w, fa.b2n = bw.norm2_b, fa.bo = bw.to_out_b;
-        fa.hin = a.hin, fa.dh_in = dh_cur = (dh_cur == w.dh ? w.dh2 : w.dh);
-        fa.pk2 = reinterpret_cast<uint4 *>(w.dq);   // xn2 / dh1 as fragments for the parameter kernel (w.dq: free in this path)
-      }
-      if (dropout_p > 0.f) {   // the bits the forward left in a.p (ff_fused() admits dropout only with the attention inside these kernels)
-        fa.dk = dfx::drop_key(dropout_seed, dropout_p), fa.site_att = (unsigned)(2 * i), fa.site_ff = (unsigned)(2 * i + 1);
-        fa.dmask = reinterpret_cast<unsigned *>(a.p);
-      }
-      if (dfx::ffused::launch_ff<true>(st, fa)) return dfx::set_error(DFX_ERR_HIP, "train: fused feed-forward backward launch");
-      if (i == 0 && dx_in_ff && ss.on && (ssm & SS_STEM_EARLY)) {   // w.dh is final: pre_norm / proj_in backward beside the rest of the block's parameter kernels
-        if ((rc = ss.fork())) return rc;
-        stem_backward(sp, w.datt);
-        stem_done = true;
-      }
-      const int groups = (int)dfx::ffused::ff_groups(B, N);
-      // (with the attention's input gradient in the same kernel, the six column sums of every block are one launch behind the loop)
-      if (!dx_in_ff)
-        k_sum_parts_multi<<<3 * C / 32, 1024, 0, st>>>(w.cpart[i], SumOuts{{nullptr, nullptr, mut(gw.ff2_b), nullptr}}, groups, C, 3 * C);
-      // dW1, db1, dW2: weight-stationary, hid and d[a | g] recomputed from the tiles k_ff<true> left in w.dwide; the slab partials of every
-      // block are summed in one launch behind the loop
-      {
-        dfx::ffused::FwArgs wa{w.ff_frags[i], w.ff_b1p[i] + dfx::ffused::B1P_FLOATS,
-                               dx_in_ff ? reinterpret_cast<const uint4 *>(a.h1) : reinterpret_cast<const uint4 *>(w.dwide), w.ffw_part[i], w.ffw_bpart[i],
-                               R / 32, w.ffw_slabs, dropout_p > 0.f ? reinterpret_cast<const unsigned *>(a.p) : nullptr,
-                               hl_in ? reinterpret_cast<const uint4 *>(dh_in_blk) : reinterpret_cast<const uint4 *>(w.dwide) + dfx::ffused::PK_TILE_U4 / 2};
-        // (without the attention inside — dfx_debug_train_fused(2) — k_ff<true> reads fp32 rows and leaves both fragment sets in w.dwide)
-        if (dfx::ffused::launch_ff_wgrad(st, wa)) return dfx::set_error(DFX_ERR_HIP, "train: feed-forward weight-gradient launch");
-      }
-      // attention + LayerNorm2 (train_attn_fused.h): parameter side first (reads dh1 = w.dh2), then dh -> w.dh
-      dfx::afused::AttnArgs aa{};
-      aa.frags = w.at_frags[i], aa.valid = w.valid, aa.g2 = bw.norm2_w, aa.b2 = bw.norm2_b, aa.bo = bw.to_out_b;
-      aa.h = a.hin, aa.dh1 = w.dh2, aa.dh = w.dh, aa.part = w.at_part[i], aa.cpart = w.cpart[i], aa.N = N, aa.split = w.at_split, aa.R = R;
-      aa.pk2 = dx_in_ff ? reinterpret_cast<const uint4 *>(w.dq) : nullptr;
-      if (dx_in_ff) dfx::afused::k_attn_bwd_param<true><<<B * w.at_split, dfx::afused::NW * 64, 0, st>>>(aa);
-      else dfx::afused::k_attn_bwd_param<false><<<B * w.at_split, dfx::afused::NW * 64, 0, st>>>(aa);
-      const int np = dfx::afused::dx_groups(R);
-      if (!dx_in_ff) {
-        dfx::afused::k_attn_bwd_dx<<<np, dfx::afused::NW * 64, 0, st>>>(aa);
-        k_sum_parts_multi<<<3 * C / 32, 1024, 0, st>>>(w.cpart[i], SumOuts{{mut(gw.norm2_w), mut(gw.norm2_b), mut(gw.to_out_b), nullptr}}, np, C, 3 * C);
-      }
-    } else {
-    if ((rc = wgrad(st, w, w.dh, C, a.hid, FH, mut(gw.ff2_w), mut(gw.ff2_b), C, FH, FH, R, false, bf))) return rc;
-    transpose(st, bw.ff2_w, w.wT, C, FH);                                    // (512, 128)
-    if ((rc = lin(st, w.dh, C, w.wT, nullptr, w.dhid, FH, R, FH, C))) return rc;
-    const Drop dff{dropout_p, dropout_seed, (unsigned)(2 * i + 1)};
-    if (bf) k_geglu_bwd<true><<<(int)((R * FH / 4 + 255) / 256), 256, 0, st>>>(a.ag, w.dhid, w.dwide, FH, R * FH, dff);
-    else k_geglu_bwd<false><<<(int)((R * FH / 4 + 255) / 256), 256, 0, st>>>(a.ag, w.dhid, w.dwide, FH, R * FH, dff);
-    if ((rc = wgrad(st, w, w.dwide, 2 * FH, a.xn3, C, mut(gw.ff0_w), mut(gw.ff0_b), 2 * FH, C, C, R, bf, bf))) return rc;
-    transpose(st, bw.ff0_w, w.wT, 2 * FH, C);                                // (128, 1024)
-    if ((rc = lin(st, w.dwide, 2 * FH, w.wT, nullptr, w.dh2, C, R, C, 2 * FH, nullptr, 0, bf))) return rc;
-    if ((rc = ln_bwd(st, w, w.dh2, a.h1, a.st3, bw.norm3_w, w.dh, w.dh, mut(gw.norm3_w), mut(gw.norm3_b), R))) return rc;
-    // attention: h1 = hin + Wo att + bo
-    const float *dho = w.dh;   // gradient at the output of to_out: dh behind the dropout
-    if (dropout_p > 0.f) {
-      k_dropout<<<(int)((R * C / 4 + 255) / 256), 256, 0, st>>>(w.dh, nullptr, w.dh2, R * C, Drop{dropout_p, dropout_seed, (unsigned)(2 * i)});
-      dho = w.dh2;
-    }
-    if ((rc = wgrad(st, w, dho, C, a.att, C, mut(gw.to_out_w), mut(gw.to_out_b), C, C, C, R, false, bf))) return rc;
-    transpose(st, bw.to_out_w, w.wT, C, C);
-    if ((rc = lin(st, dho, C, w.wT, nullptr, w.datt, C, R, C, C))) return rc;
-    const int nab = (N + ATT_BP - 1) / ATT_BP;
-    if (bf) k_attn_bwd<true><<<dim3(nab, B), 256, 0, st>>>(w.datt, a.q, a.k, a.v, a.p, w.dq, w.apart, N);
-    else k_attn_bwd<false><<<dim3(nab, B), 256, 0, st>>>(w.datt, a.q, a.k, a.v, a.p, w.dq, w.apart, N);
-    k_attn_bwd_finish<<<B, J * C, 0, st>>>(w.apart, w.dk, w.dv, nab);
-    if ((rc = wgrad(st, w, w.dq, C, a.xn2, C, mut(gw.to_q), nullptr, C, C, C, R, bf, bf))) return rc;
-    transpose(st, bw.to_q, w.wT, C, C);
-    if ((rc = lin(st, w.dq, C, w.wT, nullptr, w.dh2, C, R, C, C, nullptr, 0, bf))) return rc;
-    if ((rc = ln_bwd(st, w, w.dh2, a.hin, a.st2, bw.norm2_w, w.dh, w.dh, mut(gw.norm2_w), mut(gw.norm2_b), R))) return rc;
-    }
-    if (fused) continue;   // (keys / values of all blocks: one pair of products behind the loop)
-    // keys / values of the 4 context tokens
-    if ((rc = wgrad(st, w, w.dk, C, w.ctx, CTXP, mut(gw.to_k), nullptr, C, CTXP, CTX, BJ))) return rc;
-    if ((rc = wgrad(st, w, w.dv, C, w.ctx, CTXP, mut(gw.to_v), nullptr, C, CTXP, CTX, BJ))) return rc;
-    DFX_HIP_TRY(hipMemsetAsync(w.wT, 0, sizeof(float) * (size_t)CTXP * C, st));
-    transpose(st, bw.to_k, w.wT, C, CTX);                                    // (522 -> 528 rows of 128)
-    if ((rc = lin(st, w.dk, C, w.wT, nullptr, w.dctx, CTXP, BJ, CTXP, C, w.dctx, CTXP))) return rc;
-    transpose(st, bw.to_v, w.wT, C, CTX);
-    if ((rc = lin(st, w.dv, C, w.wT, nullptr, w.dctx, CTXP, BJ, CTXP, C, w.dctx, CTXP))) return rc;
-  }
-  if (ff_fused(bf, dropout_p, R, N)) {
-    // parameter gradients of ALL blocks from the partials the block loop left behind: one launch per kind
-    const int LDKV0 = 2 * wt->depth * C;
-    dfx::ffused::FwFinishBatch fb{};
-    dfx::afused::UnfoldBatch ub{};
-    SumJobs sj{};
-    for (int i = 0; i < wt->depth; ++i) {
-      const dfx_block_weights &bw = wt->blk[i], &gw = grads->blk[i];
-      fb.blk[i] = dfx::ffused::FwFinishArgs{w.ffw_part[i], w.ffw_bpart[i], mut(gw.ff0_w), mut(gw.ff0_b), mut(gw.ff2_w), w.ffw_slabs,
-                                            dropout_p > 0.f ? 1.0f / (1.0f - dropout_p) : 1.0f, bw.norm3_w, bw.norm3_b, bw.ff0_w,
-                                            w.ffw_lnpart[i], mut(gw.norm3_w), mut(gw.norm3_b)};   // (d gamma3 / d beta3: k_ln3_param behind the slab sums)
-      ub.blk[i] = dfx::afused::UnfoldArgs{w.at_part[i], w.kv + 2 * i * C, w.kv + (2 * i + 1) * C, bw.to_q, bw.to_out_w, w.dkv + 2 * i * C, w.dkv + (2 * i + 1) * C,
-                                          mut(gw.to_q), mut(gw.to_out_w), w.at_sum[i], B, w.at_split, LDKV0};
-      sj.part[i] = w.cpart[i];
-      float *o6[6] = {nullptr, nullptr, mut(gw.ff2_b), mut(gw.norm2_w), mut(gw.norm2_b), mut(gw.to_out_b)};   // (rows 0, 1 of the partials are unused)
-      for (int q = 0; q < 6; ++q) sj.o[i][q] = o6[q];
-    }
-    // the chain towards the context gradient (unfold_kv -> d Wk / d Wv / d ctx -> time-embedding MLP) stays on the caller's stream; the
-    // leaves (slab sums of dW1 / dW2, dWq / dWo, the six column sums per block) go beside it
-    if ((rc = ss.fork())) return rc;
-    hipStream_t sl = (ssm & SS_LEAVES) ? sp : st;
-    dfx::afused::k_attn_unfold_kv<<<dim3(dfx::afused::J, B, wt->depth), 256, 0, st>>>(ub);
-    if (ss.on && !stem_done && dx_in_ff_all && (ssm & SS_STEM_END)) stem_backward(sp, w.datt), stem_done = true;
-    dfx::ffused::launch_ff_wgrad_finish(sl, fb, wt->depth);
-    if (t_attn_in_ff) k_sum_parts_jobs<<<wt->depth * 6 * (C / 32), 1024, 0, sl>>>(sj, (int)dfx::ffused::ff_groups(B, N), C, 6 * C);
-    if (!head_done && head_sums) head_sums(sp), head_done = true;
-    if ((rc = ss.fork())) return rc;   // (k_attn_unfold_w reads the per-shape sums k_attn_unfold_kv leaves in at_sum)
-    dfx::afused::k_attn_unfold_w<<<dim3(C / dfx::afused::UW_D, 1, wt->depth), 1024, 0, sl>>>(ub);
-    // d Wk, d Wv of every block and d ctx from the side-by-side key / value gradients
-    const int n2 = 2 * wt->depth, LDKV = n2 * C;
-    if ((rc = wgrad(st, w, w.dkv, LDKV, w.ctx, CTXP, w.dwkv, nullptr, LDKV, CTXP, CTXP, BJ))) return rc;
-    KvMutPtrs gp{};
-    for (int i = 0; i < wt->depth; ++i) gp.p[2 * i] = mut(grads->blk[i].to_k), gp.p[2 * i + 1] = mut(grads->blk[i].to_v);
-    k_unpack_kv<<<(n2 * C * CTX + 255) / 256, 256, 0, st>>>(w.dwkv, gp, n2);
-    transpose(st, w.wkv, w.wkvT, LDKV, CTXP);                                  // (528 rows of 2 depth x 128)
-    if ((rc = lin(st, w.dkv, LDKV, w.wkvT, nullptr, w.dctx, CTXP, BJ, CTXP, LDKV))) return rc;
-  }
-  // pre_norm, proj_in
-  if (fused_ends) {
-    if (!stem_done) stem_backward(st, w.part);
-  } else {
-    if ((rc = ln_bwd(st, w, w.dh, w.h0, w.st_pre, wt->pre_norm_w, nullptr, w.dh2, mut(grads->pre_norm_w), mut(grads->pre_norm_b), R))) return rc;
-    if ((rc = wgrad(st, w, w.dh2, C, w.xin, XIN, mut(grads->proj_in_w), mut(grads->proj_in_b), C, XIN, 13, R))) return rc;
-  }
-  // gradient at the input rows (optional; w.dh = the gradient behind pre_norm is final and row-major on either path)
-  if (d_x || d_variances) k_stem_dx<<<2048, 256, 0, st>>>(dh_cur, w.xin, wt->proj_in_w, wt->proj_in_b, wt->pre_norm_w, d_x, d_variances, N, R);
-  // context -> part codes, (mean, var), time embedding MLP
-  k_ctx_bwd<<<(B * CTX + 255) / 256, 256, 0, st>>>(w.dctx, d_ctx_code, d_ctx_mv, w.dte_out, B);
-  if ((rc = wgrad(st, w, w.dte_out, TE, w.te_hid, TEH, mut(grads->te2_w), mut(grads->te2_b), TE, TEH, TEH, B))) return rc;
-  transpose(st, wt->te2_w, w.wT, TE, TEH);                                   // (1024, 256)
-  if ((rc = lin(st, w.dte_out, TE, w.wT, nullptr, w.dte_hid, TEH, B, TEH, TE))) return rc;
-  k_geglu_bwd<false><<<(int)(((long long)B * TEH / 4 + 255) / 256), 256, 0, st>>>(w.te_ag, w.dte_hid, w.dte_ag, TEH, (long long)B * TEH, Drop{dropout_p, dropout_seed, SITE_TE});
-  if ((rc = wgrad(st, w, w.dte_ag, 2 * TEH, w.te_in, TE, mut(grads->te0_w), mut(grads->te0_b), 2 * TEH, TE, TE, B))) return rc;
-  if ((rc = ss.join())) return rc;
-  return dfx::check_launch("denoiser_train_backward");
+  const dfx::TrainPlan plan = dfx::train_plan_of(path, precision, dropout_p);
+  TrainStep s(wt, workspace, B, N, plan, dropout_p, dropout_seed, stream);
+  const TrainBwdIo io{d_eps, grads, d_ctx_code, d_ctx_mv, d_x, d_variances};
+  return plan.fused() ? s.backward_fused(io) : s.backward_layered(io);
 }
 
 int dfx_masked_mse_backward_f32(const float *target, const float *pred, const float *flags, const double *workspace2,
@@ -2631,7 +2676,6 @@ int dfx_pointnet_v2_train_forward(const dfx_pointnet_v2_weights *wt, void *works
   if (rc) return rc;
   DFX_REQUIRE(x && attn && m && v, "pointnet_v2_train_forward: null tensor");
   DFX_REQUIRE(precision == DFX_PREC_F32 || precision == DFX_PREC_BF16, "pointnet_v2_train_forward: precision %d", precision);
-  g_prec = precision;
   hipStream_t st = dfx::as_stream(stream);
   const int A = wt->num_anchors, zd = wt->zdim;
   PnWs w;
@@ -2645,13 +2689,13 @@ int dfx_pointnet_v2_train_forward(const dfx_pointnet_v2_weights *wt, void *works
     // fp32 trunk: the product's epilogue leaves the BatchNorm batch statistics of its output (per-workgroup (count, mean, M2) partials): the two
     // statistics passes over z (0.64 ms of the 2.1 ms forward at 128 x 2048 points) are gone
     int parts = 0;
-    if (g_prec == DFX_PREC_F32 && g_bn_fused_stats) {
+    if (precision == DFX_PREC_F32 && g_bn_fused_stats) {
       LinArgs la{};
       la.X = in, la.ldx = K, la.W = l == 0 ? w.wpad : wt->conv_w[l], la.b = wt->conv_b[l], la.Y = w.z[l], la.ldy = Co, la.M = (int)R, la.N = Co, la.K = K;
       la.stats = w.pb.part;
       if ((size_t)std::min<long long>((R + 255) / 256, 512) * Co * 3 <= w.pb.part_floats) parts = dfx::lin::launch_wide_lds_stats(st, la);
     }
-    if (!parts && (rc = lin(st, in, K, l == 0 ? w.wpad : wt->conv_w[l], wt->conv_b[l], w.z[l], Co, R, Co, K))) return rc;
+    if (!parts && (rc = lin(st, precision, in, K, l == 0 ? w.wpad : wt->conv_w[l], wt->conv_b[l], w.z[l], Co, R, Co, K))) return rc;
     if ((rc = bn_fwd(st, w, w.z[l], R, Co, wt->bn_w[l], wt->bn_b[l], mut(wt->bn_mean[l]), mut(wt->bn_var[l]), momentum, wt->bn_eps,
                      w.mean[l], w.rstd[l], w.y[l], l < 3, l < 3, parts))) return rc;
   }
@@ -2678,7 +2722,6 @@ int dfx_pointnet_v2_train_backward(const dfx_pointnet_v2_weights *wt, void *work
   if (rc) return rc;
   DFX_REQUIRE(attn && dm && dv && grads, "pointnet_v2_train_backward: null tensor");
   DFX_REQUIRE(precision == DFX_PREC_F32 || precision == DFX_PREC_BF16, "pointnet_v2_train_backward: precision %d", precision);
-  g_prec = precision;
   hipStream_t st = dfx::as_stream(stream);
   const int A = wt->num_anchors, zd = wt->zdim;
   PnWs w;
@@ -2711,12 +2754,12 @@ int dfx_pointnet_v2_train_backward(const dfx_pointnet_v2_weights *wt, void *work
         } else if ((rc = lin_g4<dfx::lin::EPI_NONE>(st, dz, A * cout, cout, nullptr, nullptr, w.wT, wt_gs, w.dh[0], A * cin, cin, B, cin, cout))) return rc;
       } else
       for (int a = 0; a < A; ++a) {   // per-part weights: group a of the grouped 1x1 convolution
-        if ((rc = wgrad(st, w.pb, dz + a * cout, A * cout, in + a * cin, A * cin, mut(grads->head_w[k][l]) + (size_t)a * cout * cin,
+        if ((rc = wgrad(st, precision, w.pb, dz + a * cout, A * cout, in + a * cin, A * cin, mut(grads->head_w[k][l]) + (size_t)a * cout * cin,
                         mut(grads->head_b[k][l]) + a * cout, cout, cin, cin, B))) return rc;
         transpose(st, wt->head_w[k][l] + (size_t)a * cout * cin, w.wT, cout, cin);   // (cin, cout)
         if (l == 0) {   // d pooled accumulates over the two heads
-          if ((rc = lin(st, dz + a * cout, A * cout, w.wT, nullptr, w.dpooled + a * cin, A * cin, B, cin, cout, w.dpooled + a * cin, A * cin))) return rc;
-        } else if ((rc = lin(st, dz + a * cout, A * cout, w.wT, nullptr, w.dh[0] + a * cin, A * cin, B, cin, cout))) return rc;
+          if ((rc = lin(st, precision, dz + a * cout, A * cout, w.wT, nullptr, w.dpooled + a * cin, A * cin, B, cin, cout, w.dpooled + a * cin, A * cin))) return rc;
+        } else if ((rc = lin(st, precision, dz + a * cout, A * cout, w.wT, nullptr, w.dh[0] + a * cin, A * cin, B, cin, cout))) return rc;
       }
       dcur = w.dh[0];
     }
@@ -2736,10 +2779,10 @@ int dfx_pointnet_v2_train_backward(const dfx_pointnet_v2_weights *wt, void *work
   for (int l = 3; l >= 0; --l) {
     const int K = PN_C[l], Co = PN_C[l + 1];
     if (l < 3 && (rc = bn_bwd(st, w, dy, wt->bn_b[l], w.z[l], R, Co, wt->bn_w[l], w.mean[l], w.rstd[l], dz, mut(grads->bn_w[l]), mut(grads->bn_b[l]), true))) return rc;
-    if ((rc = wgrad(st, w.pb, dz, Co, l == 0 ? w.X8 : w.y[l - 1], K, mut(grads->conv_w[l]), mut(grads->conv_b[l]), Co, K, l == 0 ? 3 : K, R))) return rc;
+    if ((rc = wgrad(st, precision, w.pb, dz, Co, l == 0 ? w.X8 : w.y[l - 1], K, mut(grads->conv_w[l]), mut(grads->conv_b[l]), Co, K, l == 0 ? 3 : K, R))) return rc;
     if (l > 0) {
       transpose(st, wt->conv_w[l], w.wT, Co, K);   // (K, Co)
-      if ((rc = lin(st, dz, Co, w.wT, nullptr, dy, K, R, K, Co))) return rc;
+      if ((rc = lin(st, precision, dz, Co, w.wT, nullptr, dy, K, R, K, Co))) return rc;
     }
   }
   return dfx::check_launch("pointnet_v2_train_backward");
@@ -2760,8 +2803,6 @@ int dfx_prior_loss_forward(const float *const *flow, int flow_depth, int flow_hi
   DFX_REQUIRE(part_code && logvar && valid && loss && prior_var > 0.f, "prior_loss_forward: bad argument");
   hipStream_t st = dfx::as_stream(stream);
   const int H = flow_hidden, Rf = NPART * B;
-  const int prec_saved = g_prec;
-  g_prec = DFX_PREC_F32;   // few-row products: exact fp32
   FlowWs w;
   carve_flow(w, workspace, B, flow_depth, H);
   k_flow_gather<<<(Rf * ZD + 255) / 256, 256, 0, st>>>(part_code, w.xs[0], B);
@@ -2785,7 +2826,6 @@ int dfx_prior_loss_forward(const float *const *flow, int flow_depth, int flow_hi
       if (entropy) DFX_HIP_TRY(hipMemcpy2DAsync(entropy + i, NPART * sizeof(float), w.ent + (size_t)i * B, sizeof(float), sizeof(float), B, hipMemcpyDeviceToDevice, st));
     }
   }
-  g_prec = prec_saved;
   return dfx::check_launch("prior_loss_forward");
 }
 
@@ -2798,8 +2838,6 @@ int dfx_prior_loss_backward(const float *const *flow, int flow_depth, int flow_h
   for (int k = 0; k < NPART * flow_depth * 6; ++k) DFX_REQUIRE(flow_grads[k], "prior_loss_backward: null gradient buffer %d", k);
   hipStream_t st = dfx::as_stream(stream);
   const int H = flow_hidden, Rf = NPART * B;
-  const int prec_saved = g_prec;
-  g_prec = DFX_PREC_F32;
   FlowWs w;
   carve_flow(w, workspace, B, flow_depth, H);
   k_prior_bwd_init<<<(Rf * ZD + 255) / 256, 256, 0, st>>>(w.xs[flow_depth], w.acoef, valid, grad_scale, prior_var, B, w.dy, w.dlogdet, d_logvar);
@@ -2836,7 +2874,6 @@ int dfx_prior_loss_backward(const float *const *flow, int flow_depth, int flow_h
     dy = dx, dx = t;
   }
   if (d_part_code) k_flow_scatter<<<(Rf * ZD + 255) / 256, 256, 0, st>>>(dy, d_part_code, B);
-  g_prec = prec_saved;
   return dfx::check_launch("prior_loss_backward");
 }
 
@@ -2852,8 +2889,6 @@ int dfx_shared_mlp_train_forward(const dfx_shared_mlp_train *t, void *workspace,
   int rc = check_smt(t, workspace, workspace_bytes, B, M, ns, "shared_mlp_train_forward");
   if (rc) return rc;
   DFX_REQUIRE(x && out, "shared_mlp_train_forward: null tensor");
-  const int prec_saved = g_prec;
-  g_prec = DFX_PREC_F32;
   hipStream_t st = dfx::as_stream(stream);
   const long long G = (long long)B * M, R = G * ns, L = (long long)M * ns;
   SmtWs w;
@@ -2868,13 +2903,13 @@ int dfx_shared_mlp_train_forward(const dfx_shared_mlp_train *t, void *workspace,
       k_pad_cols<<<(co * w.cp0 + 255) / 256, 256, 0, st>>>(t->conv_w[0], w.wpad, co, t->ch[0], w.cp0);
       W = w.wpad;
     }
-    if ((rc = lin(st, in, K, W, t->conv_b[l], w.z[l], co, R, co, K))) break;
+    if ((rc = lin(st, DFX_PREC_F32, in, K, W, t->conv_b[l], w.z[l], co, R, co, K))) return rc;
     const bool relu = (t->relu_mask >> l) & 1u;
     const float *act = w.y[l];
     if (t->bn_w[l] && batch_stats) {
-      if ((rc = bn_fwd(st, w.pn, w.z[l], R, co, t->bn_w[l], t->bn_b[l], t->bn_mean[l], t->bn_var[l], momentum, t->bn_eps, w.mean[l], w.rstd[l], w.y[l], relu))) break;
+      if ((rc = bn_fwd(st, w.pn, w.z[l], R, co, t->bn_w[l], t->bn_b[l], t->bn_mean[l], t->bn_var[l], momentum, t->bn_eps, w.mean[l], w.rstd[l], w.y[l], relu))) return rc;
     } else if (t->bn_w[l]) {   // eval(): running statistics, nothing updated
-      if (!t->bn_mean[l] || !t->bn_var[l]) { rc = dfx::set_error(DFX_ERR_INVALID_ARG, "shared_mlp_train_forward: layer %d: running statistics required", l); break; }
+      if (!t->bn_mean[l] || !t->bn_var[l]) return dfx::set_error(DFX_ERR_INVALID_ARG, "shared_mlp_train_forward: layer %d: running statistics required", l);
       k_smt_running_stats<<<(co + 255) / 256, 256, 0, st>>>(t->bn_mean[l], t->bn_var[l], w.mean[l], w.rstd[l], t->bn_eps, co);
       if (relu) k_bn_apply<true><<<(int)((R * co / 4 + 255) / 256), 256, 0, st>>>(w.z[l], w.mean[l], w.rstd[l], t->bn_w[l], t->bn_b[l], w.y[l], R * co, co);
       else k_bn_apply<false><<<(int)((R * co / 4 + 255) / 256), 256, 0, st>>>(w.z[l], w.mean[l], w.rstd[l], t->bn_w[l], t->bn_b[l], w.y[l], R * co, co);
@@ -2885,8 +2920,6 @@ int dfx_shared_mlp_train_forward(const dfx_shared_mlp_train *t, void *workspace,
     }
     in = act, K = co;
   }
-  g_prec = prec_saved;
-  if (rc) return rc;
   const int cl = t->ch[t->layers];
   if (pool) k_smt_pool_fwd<<<dim3((cl + 63) / 64, (unsigned)G), 64, 0, st>>>(in, out, w.arg, M, ns, cl);
   else k_smt_from_rows<<<dim3((unsigned)((L + 31) / 32), (cl + 31) / 32, B), 256, 0, st>>>(in, out, cl, L, cl);
@@ -2901,8 +2934,6 @@ int dfx_shared_mlp_train_backward(const dfx_shared_mlp_train *t, void *workspace
   for (int l = 0; l < t->layers; ++l)
     DFX_REQUIRE(grads->conv_w[l] && (t->conv_b[l] ? grads->conv_b[l] != nullptr : true) && (t->bn_w[l] ? grads->bn_w[l] && grads->bn_b[l] : true),
                 "shared_mlp_train_backward: null gradient buffer in layer %d", l);
-  const int prec_saved = g_prec;
-  g_prec = DFX_PREC_F32;
   hipStream_t st = dfx::as_stream(stream);
   const long long G = (long long)B * M, R = G * ns, L = (long long)M * ns;
   SmtWs w;
@@ -2911,21 +2942,20 @@ int dfx_shared_mlp_train_backward(const dfx_shared_mlp_train *t, void *workspace
   float *dy = w.dA, *other = w.dB;
   if (pool) k_smt_pool_bwd<<<dim3((cl + 63) / 64, (unsigned)G), 64, 0, st>>>(d_out, w.arg, dy, M, ns, cl);
   else k_smt_to_rows<<<dim3((unsigned)((L + 31) / 32), (cl + 31) / 32, B), 256, 0, st>>>(d_out, dy, cl, L, cl);
-  for (int l = t->layers - 1; l >= 0 && !rc; --l) {
+  for (int l = t->layers - 1; l >= 0; --l) {
     const int co = t->ch[l + 1], ci = l == 0 ? w.cp0 : t->ch[l], ci_valid = t->ch[l];
     const bool relu = (t->relu_mask >> l) & 1u;
     const bool plain_below = l > 0 && !t->bn_w[l - 1] && !((t->relu_mask >> (l - 1)) & 1u);   // (the layer below handed its z on: see the forward)
     const float *xin = l == 0 ? w.rows0 : plain_below ? w.z[l - 1] : w.y[l - 1];
     float *dz = other;
     if (t->bn_w[l]) {
-      rc = bn_bwd(st, w.pn, dy, t->bn_b[l], w.z[l], R, co, t->bn_w[l], w.mean[l], w.rstd[l], dz, mut(grads->bn_w[l]), mut(grads->bn_b[l]), relu, batch_stats != 0);
+      if ((rc = bn_bwd(st, w.pn, dy, t->bn_b[l], w.z[l], R, co, t->bn_w[l], w.mean[l], w.rstd[l], dz, mut(grads->bn_w[l]), mut(grads->bn_b[l]), relu, batch_stats != 0))) return rc;
     } else if (relu) {
       k_smt_relu_bwd<<<(int)((R * co + 255) / 256), 256, 0, st>>>(dy, w.z[l], dz, R * co);
     } else {
       dz = dy;   // plain linear layer
     }
-    if (rc) break;
-    if ((rc = wgrad(st, w.pn.pb, dz, co, xin, ci, mut(grads->conv_w[l]), t->conv_b[l] ? mut(grads->conv_b[l]) : nullptr, co, ci, ci_valid, R))) break;
+    if ((rc = wgrad(st, DFX_PREC_F32, w.pn.pb, dz, co, xin, ci, mut(grads->conv_w[l]), t->conv_b[l] ? mut(grads->conv_b[l]) : nullptr, co, ci, ci_valid, R))) return rc;
     if (l > 0 || d_x) {   // d (input rows) = dz W
       const float *W = t->conv_w[l];
       if (ci != ci_valid) {
@@ -2934,13 +2964,11 @@ int dfx_shared_mlp_train_backward(const dfx_shared_mlp_train *t, void *workspace
       }
       transpose(st, W, w.wT, co, ci);   // (ci, co)
       float *dprev = dz == dy ? other : dy;   // (dy's buffer is free once dz has been formed; a plain layer's dz IS dy: the other buffer then)
-      if ((rc = lin(st, dz, co, w.wT, nullptr, dprev, ci, R, ci, co))) break;
+      if ((rc = lin(st, DFX_PREC_F32, dz, co, w.wT, nullptr, dprev, ci, R, ci, co))) return rc;
       if (dprev != dy) std::swap(dy, other);
     }
     // next layer down: its dy is what was just written into `dy`; dz's buffer becomes the scratch
   }
-  g_prec = prec_saved;
-  if (rc) return rc;
   if (d_x) k_smt_from_rows<<<dim3((unsigned)((L + 31) / 32), (t->ch[0] + 31) / 32, B), 256, 0, st>>>(dy, d_x, t->ch[0], L, w.cp0);
   return dfx::check_launch("shared_mlp_train_backward");
 }
@@ -2949,6 +2977,15 @@ int dfx_shared_mlp_train_backward(const dfx_shared_mlp_train *t, void *workspace
 // (site 2 i: behind to_out of block i, over (B N, 128); 2 i + 1: behind the GEGLU of block i, over (B N, 512); 1000: time_embed)
 void dfx_debug_train_fused(int on) { g_ff_fused = on != 0, g_attn_in_ff = on != 2; }
 const char *dfx_debug_last_train_path(void) { return t_last_path; }
+const char *dfx_debug_plan_train(int prec, float dropout_p, int fused_switch, int streams_switch, int B, int N, int *bits_out) {
+  if ((prec != DFX_PREC_F32 && prec != DFX_PREC_BF16) || !(dropout_p >= 0.f && dropout_p < 1.f) || B < 1 || N < 32 || N % 32 != 0) return nullptr;
+  const dfx::TrainSwitches sw = dfx::train_switches_from_codes(fused_switch, streams_switch);
+  const dfx::TrainPlan p = dfx::plan_train(prec, dropout_p, B, N, sw);
+  const dfx::TrainStreams s = dfx::plan_train_streams(p.path, sw.streams);
+  if (bits_out)
+    *bits_out = (int)p.path | p.bf_store << 2 | p.dropout << 3 | s.fwd_ctx << 4 | s.bwd_open << 5 | s.head_early << 6 | s.stem_early << 7 | s.leaves << 8 | s.stem_end << 9;
+  return p.record;
+}
 void dfx_debug_bn_fused_stats(int on) { g_bn_fused_stats = on != 0; }
 // The branch dfx_pointnet_v2_train_backward will take on this workspace (call between the forward and the backward; reads only): the ReLU masks
 // of the three trunk layers (B N, 128 / 128 / 256) and of the heads' two BatchNorm sites (B, 4 x 256), (B, 4 x 128) in the order mlp_m.1, mlp_m.4,

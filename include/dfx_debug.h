@@ -23,6 +23,14 @@ void dfx_debug_train_fused(int on);
  * "fused_bf16", "fused_bf16_dropout" (k_ff_fwd_chain / k_ff<true> / k_ff_wgrad), "layer_bf16(_dropout)" (layer-by-layer kernels, bf16
  * products), "layer_f32(_dropout)" (exact fp32; also what DFX_PREC_BF16 takes below 256 rows), "none" before the first call. */
 const char *dfx_debug_last_train_path(void);
+/* Host-side run (no GPU) of the training step's planner (csrc/train_plan.h): the name dfx_debug_last_train_path() would report after a
+ * dfx_denoiser_train_forward of B shapes of N points with `prec` (DFX_PREC_*) and dropout_p under dfx_debug_train_fused(fused_switch) and
+ * dfx_debug_train_streams(streams_switch); NULL for arguments the entry points reject.  *bits_out (may be NULL): bits 0-1 the path (0 layer
+ * by layer with fp32-stored activations, 1 layer by layer with bf16-stored product operands, 2 fused with the attention as kernels of its own,
+ * 3 fused), 4 = bf16-stored product operands, 8 = dropout on; what goes to the side stream: 16 the forward's context branch, 32 the backward
+ * uses the side stream at all, 64 the head's sums right behind k_head_bwd, 128 the stem's backward behind block 0, 256 the finishing kernels'
+ * leaves, 512 the stem's backward beside the finishing kernels.  A pure function of its arguments: the process-global switches are not read. */
+const char *dfx_debug_plan_train(int prec, float dropout_p, int fused_switch, int streams_switch, int B, int N, int *bits_out);
 /* Debug / A-B switch: 0 keeps every launch of the fused training path on the caller's stream (default 1: the context branch of the forward
  * and the parameter-gradient reductions of the backward run on a per-device side stream, forked from and joined into the caller's stream
  * inside the call).  Same kernels and operands either way: bit-identical results. */

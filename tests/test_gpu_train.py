@@ -18,7 +18,7 @@ from difffacto_amd import synth  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 
-def _run(case, with_flags=True, precision="f32", dropout=None):
+def _run(case, with_flags=True, precision="f32", dropout=None, before_backward=None):
     from difffacto_amd import training
     dev = "cuda"
     P = {k: torch.from_numpy(v).to(dev).requires_grad_(True) for k, v in case["W"].items()}
@@ -30,6 +30,8 @@ def _run(case, with_flags=True, precision="f32", dropout=None):
                                           torch.from_numpy(case["assignment"]).to(dev), precision=precision, dropout=dropout)
     flags = torch.from_numpy(case["flags"]).to(dev) if with_flags and case["flags"] is not None else None
     loss = training.masked_mse(torch.from_numpy(case["noise"]).to(dev), eps, flags)
+    if before_backward is not None:
+        before_backward(eps)
     loss.backward()
     torch.cuda.synchronize()
     return dict(loss=float(loss.detach()), eps=eps.detach().cpu().numpy(), grads={k: v.grad.cpu().numpy() for k, v in P.items()},
@@ -352,6 +354,45 @@ def test_fused_training_step_is_bit_reproducible():
     assert np.array_equal(a["eps"], b["eps"])
     for k in a["grads"]:
         assert np.array_equal(a["grads"][k], b["grads"][k]), k
+
+
+def test_backward_follows_the_forwards_record_not_the_live_switch():
+    """The path is planned once, by the forward, and kept per workspace (csrc/train_plan.h, PathRecord): flipping dfx_debug_train_fused(0)
+    between a default forward and its backward changes nothing — every gradient is the same bits as an untoggled step's — and a backward
+    called with the other precision is refused with the record's values.  B = 2, N = 128: 256 rows, the smallest shape on the fused path."""
+    from difffacto_amd import _ffi, synth
+    B, N = 2, 128
+    rng = np.random.Generator(np.random.PCG64(256))
+    W = synth.make_denoiser_weights(4)
+    pc, mean, logvar, valid = synth.make_latents(B, seed=27, all_valid=False)
+    seg = synth.make_seg_mask(valid, N)
+    var = np.exp(logvar).astype(np.float32)
+    idx = np.broadcast_to(seg.astype(np.int64)[:, None, :], (B, 3, N))
+    anc, vr = np.take_along_axis(mean, idx, axis=2), np.take_along_axis(var, idx, axis=2)
+    c = dict(W=W, x_t=(anc + np.sqrt(vr) * rng.standard_normal((B, 3, N))).astype(np.float32), t=rng.integers(0, 1000, size=(B,)).astype(np.int64),
+             ctx_code=pc, ctx_mv=np.concatenate([mean, var], axis=1).astype(np.float32),
+             anchors_pt=np.ascontiguousarray(anc.transpose(0, 2, 1)), variances_pt=np.ascontiguousarray(vr.transpose(0, 2, 1)),
+             valid=valid, assignment=seg.astype(np.int32), noise=rng.standard_normal((B, 3, N)).astype(np.float32),
+             flags=(rng.uniform(size=(B, 1, N)) > 0.3).astype(np.float32))
+    L = _ffi.lib()
+    plain = _run(c, True, precision="bf16")
+    assert L.dfx_debug_last_train_path() == b"fused_bf16"
+    try:
+        flipped = _run(c, True, precision="bf16", before_backward=lambda eps: L.dfx_debug_train_fused(0))
+    finally:
+        L.dfx_debug_train_fused(1)
+    assert L.dfx_debug_last_train_path() == b"fused_bf16"
+    assert flipped["loss"] == plain["loss"] and np.array_equal(flipped["eps"], plain["eps"])
+    assert set(flipped["grads"]) == set(plain["grads"]) and len(plain["grads"]) == 77
+    for k in plain["grads"]:
+        assert np.array_equal(flipped["grads"][k], plain["grads"][k]), k
+    assert np.array_equal(flipped["d_ctx_code"], plain["d_ctx_code"]) and np.array_equal(flipped["d_ctx_mv"], plain["d_ctx_mv"])
+
+    def other_precision(eps):
+        assert eps.grad_fn.prec == _ffi.DFX_PREC_BF16
+        eps.grad_fn.prec = _ffi.DFX_PREC_F32
+    with pytest.raises(RuntimeError, match=r"the forward of this workspace ran with precision 1, dropout 0, B 2, N 128"):
+        _run(c, True, precision="bf16", before_backward=other_precision)
 
 
 @pytest.mark.parametrize("B,N", [(4, 1024), (3, 160), (16, 2048)])

@@ -2,9 +2,11 @@
 """The decision table of DESIGN.md 5.1b, read off the launcher's planner (csrc/denoiser_plan.h) through its host-only hook
 dfx_debug_plan_variant — no GPU needed:
 
-    python tools/launch_plan_table.py        # markdown: the automatic choice by batch size B, one row per N and engine
+    python tools/launch_plan_table.py          # markdown: the automatic choice by batch size B, one row per N and engine
+    python tools/launch_plan_table.py --train  # markdown: the training step's path table of DESIGN.md 5.6 (csrc/train_plan.h, dfx_debug_plan_train)
 
 Paste the output over the table in DESIGN.md after re-measuring a cost constant or adding a variant."""
+import ctypes
 import os
 import sys
 
@@ -28,8 +30,31 @@ def bands(prec, fold, N, code=0):
     return out
 
 
+def train_table():
+    """path, record and side-stream use of a denoiser training step by precision, row count, dropout and dfx_debug_train_fused."""
+    paths = ("layer by layer, fp32-stored", "layer by layer, bf16-stored operands", "fused, attention as kernels of its own", "fused")
+    side = ((16, "forward: context branch"), (64, "head sums early"), (128, "stem early"), (256, "leaves"), (512, "stem at the end"))
+
+    def cells(prec, p, sw, B, N):
+        bits = ctypes.c_int(0)
+        rec = _ffi.lib().dfx_debug_plan_train(prec, p, sw, 1, B, N, ctypes.byref(bits)).decode()
+        return paths[bits.value & 3], f"`{rec}`", ", ".join(n for m, n in side if bits.value & m) or "-"
+
+    print("| precision | rows B N | dropout p | `dfx_debug_train_fused` | path | `dfx_debug_last_train_path` | beside the caller's stream (default `dfx_debug_train_streams`) |")
+    print("|---|---|---|---|---|---|---|")
+    for prec, B, N, label in ((0, 2, 128, "fp32 | any"), (1, 7, 32, "bf16 | < 256"), (1, 2, 128, "bf16 | >= 256")):
+        for p in (0.0, 0.2):
+            by_cells = {}   # switches that give the same plan share a row
+            for sw in (1, 2, 0):
+                by_cells.setdefault(cells(prec, p, sw, B, N), []).append(sw)
+            for c, sws in by_cells.items():
+                print(f"| {label} | {'0' if p == 0 else '> 0'} | {'any' if len(sws) == 3 else ', '.join(map(str, sws))} | {' | '.join(c)} |")
+
+
 def main():
     build.build(verbose=False)
+    if "--train" in sys.argv:
+        return train_table()
     print(f"| engine | N | automatic choice for B = 1 .. {BMAX} |\n|---|---|---|")
     auto = set()
     for label, prec, fold in ENGINES:
