@@ -201,6 +201,9 @@ SIGNATURES = {
     "dfx_adam_step_f32": (_I, [_P, _P, _P, _P, ctypes.c_longlong, _P, _F, _F, _F, _F, _F, _F, _I, _P]),
     "dfx_p_sample_ddim": (_I, [_P, _P, _P, _P, _I, _F, _P, _U64, _U64, _P, _P, _I, _I, _P]),
     "dfx_sample_chain_ddim": (_I, [_P, _P, _P, ctypes.POINTER(ctypes.c_int32), _I, _F, _P, _P, _U64, _U64, _I, _P, _P, _I, _I, _P]),
+    "dfx_sample_chain_from": (_I, [_P, _P, _P, _P, _I, _P, _U64, _U64, _P, _I, _P, _P, _I, _I, _P]),
+    "dfx_refine_chain": (_I, [_P, _P, _P, _P, _I, _P, _P, _U64, _U64, _P, _I, _P, _P, _I, _I, _P]),
+    "dfx_sample_chain_ddim_from": (_I, [_P, _P, _P, ctypes.POINTER(ctypes.c_int32), _I, _F, _P, _P, _U64, _U64, _P, _I, _P, _P, _I, _I, _P]),
     "dfx_debug_force_direct": (None, [_I]),
     "dfx_debug_bare_mfma": (_I, [_I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double), _P]),
     "dfx_debug_pipe_waves": (None, [_I]),

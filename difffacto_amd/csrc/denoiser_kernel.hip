@@ -32,6 +32,9 @@ typedef _Float16 v8h __attribute__((ext_vector_type(8)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 
 enum { MODE_EPS = 0, MODE_PSAMPLE = 1, MODE_CHAIN = 2 };
+// where a MODE_CHAIN launch takes its first state from: x_T = a + L z (generation), the caller's x_in (a snapshot, a noisy cloud),
+// or q_sample of the caller's clean x_in at the first executed timestep, computed in the prologue
+enum { START_NOISE = 0, START_GIVEN = 1, START_QSAMPLE = 2 };   // (START_NOISE: the generation kernels; the others: their FROM instantiations)
 constexpr int DDIM_MAX_STEPS = 128;
 
 struct KParams {
@@ -39,10 +42,10 @@ struct KParams {
   const float *part;     // shape ctx regions
   const float *cpart;
   const uint4 *as_ms;
-  const float *x_in;     // (B,3,N)        eps / p_sample
+  const float *x_in;     // (B,3,N)        eps / p_sample | chain, START_GIVEN: first state, START_QSAMPLE: clean cloud
   const int32_t *seg;    // (B,N)
   const float *noise;    // p_sample: (B,3,N) | chain: (nsteps,B,3,N) | null -> Philox
-  const float *xT_noise; // chain: (B,3,N) | null -> Philox
+  const float *xT_noise; // chain: (B,3,N) | null -> Philox (START_NOISE: the x_T draw; START_QSAMPLE: the forward-noising draw)
   float *out;            // eps: (B,3,N) | p_sample: (B,3,N) | chain: pred (B,N,3)
   float *traj;           // chain snapshots (n_keep,B,N,3) or null
   float *xstart;         // p_sample: optional pred_xstart (B,3,N)
@@ -58,6 +61,8 @@ struct KParams {
   float ddim_xdc[DDIM_MAX_STEPS];
   unsigned long long *trace;  // debug: s_memtime stamps of waves 0 and 4 of workgroup 0 at every slot boundary
   int trace_cap;
+  int start;              // chain: START_*
+  const int32_t *hold;    // chain, START_GIVEN / START_QSAMPLE: (B,) bit j = the points of part j keep their x_in coordinates | null
 };
 
 // ----------------------------------------------------------------------------------------------
@@ -679,6 +684,47 @@ struct PointState {
   bool live = true;   // false: a wavefront past the end of its shape's last (partial) 256-point tile recomputes that shape's last 32 points and stores nothing
 };
 
+// Partial chains (the FROM instantiations of the kernels; MODE_CHAIN only).  ps.x holds the caller's x_in.  START_GIVEN: that is the state entering
+// the first executed timestep (a DDPM launch over the whole chain, nsteps == T, also records it as the t = T snapshot).  START_QSAMPLE: x_in is a
+// clean cloud, forward-noised here to the first executed timestep t = nsteps-1 in k_q_sample's expression order, no contraction — bit-identical to
+// dfx_q_sample_f32 followed by START_GIVEN.  Its noise is the caller's xT_noise or the Philox stream of the x_T draw (stream 1) keyed by nsteps:
+// the step noise (stream 0) never meets it.
+__device__ __forceinline__ void chain_start_from(const KParams &p, PointState &ps, int hf) {
+  if (p.start == START_QSAMPLE) {
+#pragma clang fp contract(off)
+    float z[3];
+    if (p.xT_noise) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) z[i] = p.xT_noise[((size_t)ps.s * 3 + i) * p.N + ps.n];
+    } else {
+      philox_normal3(p.seed, ps.gid, (unsigned)p.nsteps, 1u, z);
+    }
+    const float qa = p.d.qtab[(p.nsteps - 1) * 2], qb = p.d.qtab[(p.nsteps - 1) * 2 + 1];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ps.x[i] = qa * (ps.x[i] - ps.anc[i]) + ps.anc[i] + qb * ps.L[i] * z[i];
+  } else if (p.traj && p.ddim_n == 0 && p.nsteps == p.d.T && p.d.T % p.ret_interval == 0 && hf == 0 && ps.live) {
+    float *o = p.traj + ((size_t)ps.s * p.N + ps.n) * 3;  // snapshot 0 <-> t = T
+    o[0] = ps.x[0]; o[1] = ps.x[1]; o[2] = ps.x[2];
+  }
+}
+
+// One point of `pred` or of a snapshot.  In a partial chain a point of a held part (hold bit of its part id) is written as the caller's x_in:
+// decided here, from the part id and the shape's mask, and re-read from global memory — nothing of it travels through the step loop.
+template <bool FROM>
+__device__ __forceinline__ void chain_store(const KParams &p, const PointState &ps, float *o) {
+  if constexpr (FROM) {
+    if (p.hold && ((p.hold[ps.s] >> ps.sg) & 1)) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) o[i] = p.x_in[((size_t)ps.s * 3 + i) * p.N + ps.n];
+      return;
+    }
+  }
+  o[0] = ps.x[0]; o[1] = ps.x[1]; o[2] = ps.x[2];
+}
+
+// FROM: the instantiation for partial chains (dfx_sample_chain_from / dfx_refine_chain / dfx_sample_chain_ddim_from).  Every kernel exists twice,
+// and the generation kernels (FROM = false) compile to what they were before partial chains existed.
+template <bool FROM = false>
 __device__ __forceinline__ void point_init(const KParams &p, PointState &ps, int s, int n, unsigned long long gid,
                                            unsigned &vmask) {
   ps.s = s; ps.n = n; ps.gid = gid;
@@ -695,7 +741,11 @@ __device__ __forceinline__ void point_init(const KParams &p, PointState &ps, int
   for (int j = 0; j < 4; ++j) vmask |= (part[24 + j] != 0.f ? 1u : 0u) << j;  // mask.to(bool), attention.py:196
   vmask = __builtin_amdgcn_readfirstlane(vmask);
   const int hf = (threadIdx.x >> 5) & 1;
-  if (p.mode == MODE_CHAIN) {
+  if constexpr (FROM) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ps.x[i] = p.x_in[((size_t)s * 3 + i) * p.N + n];
+    chain_start_from(p, ps, hf);
+  } else if (p.mode == MODE_CHAIN) {
     float z[3];
     if (p.xT_noise) {
 #pragma unroll
@@ -718,6 +768,7 @@ __device__ __forceinline__ void point_init(const KParams &p, PointState &ps, int
 // What happens to eps after the network: store it (MODE_EPS), or the anchored posterior update
 // (anchored_diffusion.py:306-319,365-367,378-380,401-409,175-213,476-483; reference op order, no contraction)
 // plus the bookkeeping of AnchorDiffAE.decode (anchor_gen.py:160-167).  Returns true when the kernel is done.
+template <bool FROM = false>
 __device__ __forceinline__ bool step_epilogue(const KParams &p, PointState &ps, const float (&eps)[3], int step, int t,
                                               const float *z_ready = nullptr, const float *tab_row = nullptr) {
   const int hf = ps.live ? (threadIdx.x >> 5) & 1 : 1;   // stores are done by half-wave 0 of live wavefronts
@@ -770,12 +821,10 @@ __device__ __forceinline__ bool step_epilogue(const KParams &p, PointState &ps, 
   }
   if (hf == 0) {
     if (t == 0) {
-      float *o = p.out + ((size_t)s * p.N + n) * 3;
-      o[0] = ps.x[0]; o[1] = ps.x[1]; o[2] = ps.x[2];
+      chain_store<FROM>(p, ps, p.out + ((size_t)s * p.N + n) * 3);
     } else if (p.traj && t % p.ret_interval == 0) {
       const int k = p.d.T / p.ret_interval - t / p.ret_interval;
-      float *o = p.traj + (((size_t)k * p.B + s) * p.N + n) * 3;
-      o[0] = ps.x[0]; o[1] = ps.x[1]; o[2] = ps.x[2];
+      chain_store<FROM>(p, ps, p.traj + (((size_t)k * p.B + s) * p.N + n) * 3);
     }
   }
   return false;
@@ -784,7 +833,7 @@ __device__ __forceinline__ bool step_epilogue(const KParams &p, PointState &ps, 
 // ----------------------------------------------------------------------------------------------
 // v0 "direct" kernel: every operand comes straight from global memory (L2-resident).  Any N % 32 == 0,
 // both precisions.  It is the general fallback and the exact-fp32 parity path.
-template <int PREC, int NW>
+template <int PREC, int NW, bool FROM = false>
 __global__ void __launch_bounds__(NW * 64) k_denoise(const KParams p) {
   constexpr int TSTRIDE = tile_units(PREC) * 64;  // uint4 elements per 32x32 weight tile
   constexpr int AREC = asms_bytes(PREC) / 16;     // uint4 per attention record
@@ -798,7 +847,7 @@ __global__ void __launch_bounds__(NW * 64) k_denoise(const KParams p) {
   const int depth = p.d.depth;
   PointState ps;
   unsigned vmask;
-  point_init(p, ps, s, n, ((unsigned long long)p.shape0 + (unsigned)s) * (unsigned)p.N + (unsigned)n, vmask);
+  point_init<FROM>(p, ps, s, n, ((unsigned long long)p.shape0 + (unsigned)s) * (unsigned)p.N + (unsigned)n, vmask);
   const float *cpart = p.cpart + ((size_t)s * NCLS + ps.sg) * INNER + hf * 64;
   const uint4 *asms_s = p.as_ms + (size_t)s * depth * AREC + lane;
 
@@ -823,7 +872,7 @@ __global__ void __launch_bounds__(NW * 64) k_denoise(const KParams p) {
     }
     float eps[3];
     post_eps(h, p.d.wout + hf * 64, p.d.bout, eps);
-    if (step_epilogue(p, ps, eps, step, t)) return;
+    if (step_epilogue<FROM>(p, ps, eps, step, t)) return;
   }
 }
 
@@ -1098,7 +1147,7 @@ __device__ __forceinline__ void pstate_load(const float *ps_lds, int pt, int PTS
   ps.sg = __float_as_int(ps_lds[12 * PTS + pt]);
 }
 
-template <int NW>
+template <int NW, bool FROM = false>
 __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe(const KParams p) {
   constexpr int PREC = DFX_PREC_BF16;
   constexpr int PIPE_NW = NW, PTS = PipeCfg<NW>::PTS;
@@ -1159,7 +1208,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe(const KParams p) {
   {
     PointState ps0;
     ps0.live = live;
-    point_init(p, ps0, s, n, gid, vmask);
+    point_init<FROM>(p, ps0, s, n, gid, vmask);
     pstate_store(ps_lds, pt, PTS, ps0, true);   // both half-waves hold the same point: identical values
   }
   __syncthreads();
@@ -1222,7 +1271,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe(const KParams p) {
         if (step > 0) {
           float eps[3];
           post_eps<true>(h, wout, p.d.bout, eps);
-          done = step_epilogue(p, ps, eps, step - 1, step_t(p, step - 1, s));
+          done = step_epilogue<FROM>(p, ps, eps, step - 1, step_t(p, step - 1, s));
           if (!done) pstate_store(ps_lds, pt, PTS, ps, false);   // both half-waves hold the same point and write the same x
         }
         if (step == p.nsteps) done = true;
@@ -1392,7 +1441,7 @@ __device__ __forceinline__ void issue_record_f32(const KParams &p, DmaStateF &st
   }
 }
 
-template <int NW>
+template <int NW, bool FROM = false>
 __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe_f32(const KParams p) {
   constexpr int PREC = DFX_PREC_F32;
   constexpr int PTS = PipeCfg<NW>::PTS, TS = tile_units(PREC) * 64;
@@ -1444,7 +1493,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe_f32(const KParams p
   {
     PointState ps0;
     ps0.live = live;
-    point_init(p, ps0, s, n, gid, vmask);
+    point_init<FROM>(p, ps0, s, n, gid, vmask);
     pstate_store(ps_lds, pt, PTS, ps0, true);
   }
   __syncthreads();
@@ -1488,7 +1537,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe_f32(const KParams p
         if (step > 0) {
           float eps[3];
           post_eps(h, wout, p.d.bout, eps);
-          done = step_epilogue(p, ps, eps, step - 1, step_t(p, step - 1, s));
+          done = step_epilogue<FROM>(p, ps, eps, step - 1, step_t(p, step - 1, s));
           if (!done) pstate_store(ps_lds, pt, PTS, ps, false);
         }
         if (step == p.nsteps) done = true;
@@ -1647,9 +1696,10 @@ __device__ __forceinline__ void coop_stage_consts(unsigned char *cc, const KPara
 
 // The 32 points of tile (s, n - pj): initial chain state -> its LDS home between step boundaries
 // (the state would otherwise sit in scratch memory for the whole chain: a global-memory round trip per field at every step boundary)
+template <bool FROM>
 __device__ __forceinline__ void coop_point_init(const KParams &p, float *ps_lds, int s, int n, int pj, unsigned &vmask) {
   PointState ps0;
-  point_init(p, ps0, s, n, ((unsigned long long)p.shape0 + (unsigned)s) * (unsigned)p.N + (unsigned)n, vmask);
+  point_init<FROM>(p, ps0, s, n, ((unsigned long long)p.shape0 + (unsigned)s) * (unsigned)p.N + (unsigned)n, vmask);
   pstate_store(ps_lds, pj, 32, ps0, true);
 }
 
@@ -1776,13 +1826,14 @@ __device__ __forceinline__ void coop_eps(float (&eps)[3], const v4f *home, const
   post_eps_tiles(h, reinterpret_cast<const float4 *>(cc + CC_WOUT) + (lane >> 5) * 64, p.d.bout, eps);
 }
 // ... the posterior update of the chain state parked at ps_lds, with the noise coop_draw_noise left in s_z (true: the kernel is done) ...
+template <bool FROM>
 __device__ __forceinline__ bool coop_posterior(const KParams &p, PointState &ps, const float (&eps)[3], const float *ps_lds, const float *s_z, int s, int n,
                                                int step, int t, int pj) {
   ps.s = s, ps.n = n, ps.gid = 0;   // (gid: the noise was drawn by another wave)
   pstate_load(ps_lds, pj, 32, ps, true);
   const float zr[3] = {s_z[pj], s_z[32 + pj], s_z[64 + pj]};
   const bool zok = p.mode != MODE_EPS;
-  return step_epilogue(p, ps, eps, step, t, zok ? zr : nullptr, zok ? s_z + 128 : nullptr);
+  return step_epilogue<FROM>(p, ps, eps, step, t, zok ? zr : nullptr, zok ? s_z + 128 : nullptr);
 }
 // ... and proj_in + pre_norm of the new state -> h's home (also before the first step)
 __device__ __forceinline__ void coop_enter_step(const PointState &ps, v4f *home, const unsigned char *cc, int lane) {
@@ -1807,6 +1858,7 @@ constexpr int CL_PS = CL_Z + 1024;                                 // per-point 
 constexpr int CL_TOTAL = CL_PS + 2048;
 static_assert(CL_TOTAL <= 160 * 1024, "LDS budget of the co-operative kernel");
 
+template <bool FROM>
 __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams p) {
   constexpr int TSTRIDE = COOP_TSTRIDE, AREC = COOP_AREC;
   uint4 (*s_xn)[64] = reinterpret_cast<uint4 (*)[64]>(pipe_smem + CL_XN);
@@ -1825,7 +1877,7 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams 
   float *ps_lds = reinterpret_cast<float *>(pipe_smem + CL_PS);
   v4f *home = reinterpret_cast<v4f *>(pipe_smem + CL_HS) + lane;
   unsigned vmask = 0;
-  if (w0) coop_point_init(p, ps_lds, s, n, pj, vmask);
+  if (w0) coop_point_init<FROM>(p, ps_lds, s, n, pj, vmask);
   const uint4 *asms_s = p.as_ms + (size_t)s * depth * AREC;
   coop_stage_consts(cc, p, s);   // (wave 0 reads them at every step boundary)
   __syncthreads();
@@ -1929,7 +1981,7 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams 
       coop_eps(eps, home, cc, p, lane);
       tr.stamp(18);
       PointState ps;
-      if (coop_posterior(p, ps, eps, ps_lds, s_z, s, n, step, t, pj)) break;   // (the other waves leave through the loop bound: nsteps = 1 in these modes)
+      if (coop_posterior<FROM>(p, ps, eps, ps_lds, s_z, s, n, step, t, pj)) break;   // (the other waves leave through the loop bound: nsteps = 1 in these modes)
       tr.stamp(19);
       pstate_store(ps_lds, pj, 32, ps, false);
       if (step + 1 < p.nsteps) coop_enter_step(ps, home, cc, lane);
@@ -1959,6 +2011,7 @@ constexpr int C2_PS = C2_Z + 2 * 1024;                             // 2 tiles x 
 constexpr int C2_TOTAL = C2_PS + 2 * 2048;
 static_assert(C2_TOTAL <= 160 * 1024, "LDS budget of the two-tile co-operative kernel");
 
+template <bool FROM>
 __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop2(const KParams p) {
   constexpr int AREC = COOP_AREC;
   uint4 *s_at = reinterpret_cast<uint4 *>(pipe_smem + C2_AT);
@@ -1979,7 +2032,7 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop2(const KParams
   float *ps_lds = reinterpret_cast<float *>(pipe_smem + C2_PS + (wave & 1) * 2048);   // (waves 0, 1)
   const int n_a = nbase + wave * 32 + pj;                                             // (waves 0, 1: this lane's point)
   unsigned vmask = 0;
-  if (arole) coop_point_init(p, ps_lds, s, n_a, pj, vmask);
+  if (arole) coop_point_init<FROM>(p, ps_lds, s, n_a, pj, vmask);
   const uint4 *asms_s = p.as_ms + (size_t)s * depth * AREC;
   coop_stage_consts(cc, p, s);
   __syncthreads();
@@ -2061,7 +2114,7 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop2(const KParams
       float eps[3];
       coop_eps(eps, home(wave), cc, p, lane);
       PointState ps;
-      if (coop_posterior(p, ps, eps, ps_lds, z_base(wave), s, n_a, step, t, pj)) break;   // (the other waves leave through the loop bound: nsteps = 1 in these modes)
+      if (coop_posterior<FROM>(p, ps, eps, ps_lds, z_base(wave), s, n_a, step, t, pj)) break;   // (the other waves leave through the loop bound: nsteps = 1 in these modes)
       pstate_store(ps_lds, pj, 32, ps, false);
       if (step + 1 < p.nsteps) coop_enter_step(ps, home(wave), cc, lane);
     }
@@ -2121,9 +2174,16 @@ struct VariantKernel {
 };
 const VariantKernel KERNELS[NUM_VARIANTS] = {
     {k_denoise_pipe<8>, PipeCfg<8>::L_TOTAL},     {k_denoise_pipe<4>, PipeCfg<4>::L_TOTAL},     {k_denoise_pipe<2>, PipeCfg<2>::L_TOTAL},
-    {k_denoise_coop, CL_TOTAL},                   {k_denoise_coop2, C2_TOTAL},                  {k_denoise_pipe_f32<8>, PipeCfg<8>::L_TOTAL},
+    {k_denoise_coop<false>, CL_TOTAL},            {k_denoise_coop2<false>, C2_TOTAL},           {k_denoise_pipe_f32<8>, PipeCfg<8>::L_TOTAL},
     {k_denoise_pipe_f32<4>, PipeCfg<4>::L_TOTAL}, {k_denoise_pipe_f32<2>, PipeCfg<2>::L_TOTAL}, {k_denoise<DFX_PREC_BF16, 4>, 0},
     {k_denoise<DFX_PREC_F32, 4>, 0},
+};
+// ... and their instantiations for partial chains (KParams::start != START_NOISE): the same plan, the same launch shape
+const VariantKernel KERNELS_FROM[NUM_VARIANTS] = {
+    {k_denoise_pipe<8, true>, PipeCfg<8>::L_TOTAL},     {k_denoise_pipe<4, true>, PipeCfg<4>::L_TOTAL},     {k_denoise_pipe<2, true>, PipeCfg<2>::L_TOTAL},
+    {k_denoise_coop<true>, CL_TOTAL},                   {k_denoise_coop2<true>, C2_TOTAL},                  {k_denoise_pipe_f32<8, true>, PipeCfg<8>::L_TOTAL},
+    {k_denoise_pipe_f32<4, true>, PipeCfg<4>::L_TOTAL}, {k_denoise_pipe_f32<2, true>, PipeCfg<2>::L_TOTAL}, {k_denoise<DFX_PREC_BF16, 4, true>, 0},
+    {k_denoise<DFX_PREC_F32, 4, true>, 0},
 };
 static_assert(info(Variant::Coop).threads == COOP_NW * 64 && info(Variant::Coop2).threads == COOP_NW * 64 && info(Variant::Pipe8).points == PipeCfg<8>::PTS,
               "denoiser_plan.h's table against the kernels' launch bounds");
@@ -2140,12 +2200,14 @@ int launch(const dfx_denoiser *d, const void *shape_ctx, KParams &p, hipStream_t
   // (the size check stays here, on the direct kernels' workgroup count as before; the planner itself takes any B, N)
   if (((long long)p.B * p.N / 32 + 3) / 4 > 0x7fffffffLL) return set_error(DFX_ERR_INVALID_ARG, "denoiser: B*N too large");
   const Plan plan = plan_launch({d->dev.prec, d->dev.w1_fold != 0, g_force_direct, force_from_code(g_force_nw), p.B, p.N, g_num_cus});
-  const VariantKernel &k = KERNELS[(int)plan.v];
+  const VariantKernel &k = (p.start != START_NOISE ? KERNELS_FROM : KERNELS)[(int)plan.v];
   if (k.lds > 0) {
     static PerDeviceOnce attrs;
     DFX_HIP_TRY(attrs.run([] {
       hipError_t e = hipSuccess;
       for (const VariantKernel &vk : KERNELS)
+        if (e == hipSuccess && vk.lds > 0) e = set_max_lds(reinterpret_cast<const void *>(vk.kernel), vk.lds);
+      for (const VariantKernel &vk : KERNELS_FROM)
         if (e == hipSuccess && vk.lds > 0) e = set_max_lds(reinterpret_cast<const void *>(vk.kernel), vk.lds);
       return e;
     }));
@@ -2307,6 +2369,56 @@ int dfx_sample_chain(const dfx_denoiser *d, const void *shape_ctx, const int32_t
   p.seg = seg; p.noise = step_noise; p.xT_noise = x_T_noise; p.out = pred; p.traj = traj; p.seed = seed; p.shape0 = shape_offset;
   p.B = B; p.N = N; p.t0 = d->dev.T - 1; p.nsteps = d->dev.T; p.ret_interval = ret_interval >= 1 ? ret_interval : 1;
   p.mode = MODE_CHAIN;
+  return launch(d, shape_ctx, p, as_stream(stream));
+}
+
+// Partial chains: the last n_steps timesteps (n_steps-1 .. 0) from a caller's state, or from q_sample of a caller's clean cloud at t = n_steps-1
+static int chain_from(const dfx_denoiser *d, const void *shape_ctx, const int32_t *seg, const float *x, int n_steps, int start,
+                      const float *start_noise, const float *step_noise, uint64_t seed, uint64_t shape_offset, const int32_t *hold,
+                      int ret_interval, float *traj, float *pred, int B, int N, dfx_stream_t stream, const char *who) {
+  const int rc = check_common(d, shape_ctx, seg, B, N, who);
+  if (rc < 0) return rc;
+  DFX_REQUIRE(n_steps >= 1 && n_steps <= d->dev.T, "%s: n_steps=%d outside [1,%d]", who, n_steps, d->dev.T);
+  if (rc) return DFX_OK;
+  DFX_REQUIRE(x, "%s: null start cloud", who);
+  DFX_REQUIRE(pred, "%s: null pred", who);
+  DFX_REQUIRE(!traj || ret_interval >= 1, "%s: ret_interval must be >= 1 when traj is given", who);
+  KParams p{};
+  p.x_in = x; p.seg = seg; p.noise = step_noise; p.xT_noise = start_noise; p.out = pred; p.traj = traj; p.seed = seed; p.shape0 = shape_offset;
+  p.B = B; p.N = N; p.t0 = n_steps - 1; p.nsteps = n_steps; p.ret_interval = ret_interval >= 1 ? ret_interval : 1;
+  p.mode = MODE_CHAIN; p.start = start; p.hold = hold;
+  return launch(d, shape_ctx, p, as_stream(stream));
+}
+
+int dfx_sample_chain_from(const dfx_denoiser *d, const void *shape_ctx, const int32_t *seg, const float *x_init, int n_steps,
+                          const float *step_noise, uint64_t seed, uint64_t shape_offset, const int32_t *hold, int ret_interval,
+                          float *traj, float *pred, int B, int N, dfx_stream_t stream) {
+  return chain_from(d, shape_ctx, seg, x_init, n_steps, START_GIVEN, nullptr, step_noise, seed, shape_offset, hold, ret_interval, traj, pred,
+                    B, N, stream, "sample_chain_from");
+}
+
+int dfx_refine_chain(const dfx_denoiser *d, const void *shape_ctx, const int32_t *seg, const float *x_start, int n_steps,
+                     const float *start_noise, const float *step_noise, uint64_t seed, uint64_t shape_offset, const int32_t *hold,
+                     int ret_interval, float *traj, float *pred, int B, int N, dfx_stream_t stream) {
+  return chain_from(d, shape_ctx, seg, x_start, n_steps, START_QSAMPLE, start_noise, step_noise, seed, shape_offset, hold, ret_interval, traj,
+                    pred, B, N, stream, "refine_chain");
+}
+
+int dfx_sample_chain_ddim_from(const dfx_denoiser *d, const void *shape_ctx, const int32_t *seg, const int32_t *steps, int n_steps,
+                               float eta, const float *x_init, const float *step_noise, uint64_t seed, uint64_t shape_offset,
+                               const int32_t *hold, int ret_interval, float *traj, float *pred, int B, int N, dfx_stream_t stream) {
+  const int rc = check_common(d, shape_ctx, seg, B, N, "sample_chain_ddim_from");
+  if (rc < 0) return rc;
+  KParams p{};
+  if (int e = fill_ddim(d, p, steps, n_steps, eta, "sample_chain_ddim_from")) return e;
+  DFX_REQUIRE(steps[0] == 0, "sample_chain_ddim_from: the step list must start at 0 (the t == 0 sample is 'pred')");
+  if (rc) return DFX_OK;
+  DFX_REQUIRE(x_init, "sample_chain_ddim_from: null start cloud");
+  DFX_REQUIRE(pred, "sample_chain_ddim_from: null pred");
+  DFX_REQUIRE(!traj || ret_interval >= 1, "sample_chain_ddim_from: ret_interval must be >= 1 when traj is given");
+  p.x_in = x_init; p.seg = seg; p.noise = step_noise; p.out = pred; p.traj = traj; p.seed = seed; p.shape0 = shape_offset;
+  p.B = B; p.N = N; p.t0 = p.ddim_t[0]; p.nsteps = n_steps; p.ret_interval = ret_interval >= 1 ? ret_interval : 1;
+  p.mode = MODE_CHAIN; p.start = START_GIVEN; p.hold = hold;
   return launch(d, shape_ctx, p, as_stream(stream));
 }
 

@@ -201,7 +201,7 @@ int dfx_debug_bare_mfma(int iters, float *ms_out, double *tflops_out, dfx_stream
   return DFX_OK;
 }
 
-int dfx_version(void) { return 107; }
+int dfx_version(void) { return 108; }
 int dfx_abi_version(void) { return DFX_ABI_VERSION; }
 
 const char *dfx_last_error(void) { return dfx::err_buf(); }

@@ -183,6 +183,50 @@ def drift_anchors(encoder, diffusion, codes, scale, parts=(0, 2), axis=1, valid_
             "anchors": mean_pp.transpose(1, 2).reshape(B, K, npoints, 3)}
 
 
+# ---------------------------------------------------------------------------------------------------- variations of a given cloud
+def held_parts(valid_id, parts, n_class):
+    """(B, n_class) 0/1: the parts a variation keeps -- every present part that is not in ``parts`` (``parts=None``: nothing is held, the
+    whole cloud is regenerated)."""
+    if parts is None:
+        return torch.zeros_like(valid_id)
+    parts = sorted({int(p) for p in parts})
+    if any(not 0 <= p < n_class for p in parts):
+        raise ValueError(f"vary_shape: parts {parts} outside [0, {n_class})")
+    held = (valid_id != 0).to(valid_id.dtype)
+    held[:, parts] = 0
+    return held
+
+
+@torch.no_grad()
+def vary_shape(diffusion, ctx, seg, cloud, n_steps, parts=None, each=1, valid_id=None, seed=None, generator=None, ret_interval=None,
+               shape_offset=0):
+    """``each`` variations of every labelled cloud at strength ``n_steps`` (the usual diffusion recipe: noise to step n_steps-1, denoise
+    n_steps steps), ONE ``dfx_refine_chain`` launch over the B*each rows r = b*each + k.  ``ctx`` = [part_code (B,zdim,J), params (B,6,J)] and
+    ``seg`` (B,N) are the shapes' context and part ids, ``cloud`` (B,N,3) their points (a data-set shape, a scan, an earlier output).
+    ``parts``: the parts to regenerate -- the points of every other present part come back bit for bit (the kernel writes them from
+    ``cloud``); None regenerates everything.  Row r draws the Philox noise of global row ``shape_offset + r``, so the variations of a
+    shape differ, and a batch split over calls (``shape_offset`` = rows before it) gives the unsplit clouds.
+    Returns {'pred': (B, each, N, 3), 'seg_mask': (B, each, N), 'held': (B, J) 0/1} (+ 'traj': (n_keep, B, each, N, 3) with ``ret_interval``)."""
+    part_code, params = ctx[0], ctx[1]
+    B, J, K = part_code.shape[0], part_code.shape[-1], int(each)
+    device = part_code.device
+    seg = seg.to(device=device, dtype=torch.int32)
+    cloud = cloud.to(device=device, dtype=torch.float32)
+    N = seg.shape[1]
+    if tuple(cloud.shape) != (B, N, 3):
+        raise ValueError(f"vary_shape: cloud (B,N,3) = ({B},{N},3) expected, got {tuple(cloud.shape)}")
+    valid_id = torch.ones(B, J, device=device) if valid_id is None else valid_id.to(device=device, dtype=torch.float32)
+    held = held_parts(valid_id, parts, J)
+    rep = lambda t: t.repeat_interleave(K, 0)
+    pred, traj = diffusion.refine_chain([rep(part_code), rep(params)], rep(seg), rep(cloud.transpose(1, 2)), n_steps, valid_id=rep(valid_id),
+                                        seed=seed, generator=generator, ret_interval=ret_interval, shape_offset=shape_offset,
+                                        hold=rep(held) if parts is not None else None)
+    out = {"pred": pred.reshape(B, K, N, 3), "seg_mask": rep(seg).reshape(B, K, N), "held": held}
+    if traj is not None:
+        out["traj"] = traj.reshape(traj.shape[0], B, K, N, 3)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- part-level sampling
 def part_sampling_recipe(S, E, P, n_class, part_id):
     """Rows r = (s*E + e)*P + p of the final ``dfx_compose_latents`` call over the source rows [the S shapes | the S*E new styles]:

@@ -71,6 +71,18 @@ def last_kernel_variant():
     return _ffi.lib().dfx_last_kernel_variant().decode()
 
 
+def snapshot_times(T, ret_interval, n_steps=None, fused=False):
+    """Timesteps of the traj slots of a T-step chain, descending: slot k <-> t = (T // ret_interval - k) * ret_interval, the state after timestep t
+    ran (t = T: the first state).  ``n_steps``: the slots a partial chain of ``n_steps`` steps writes and returns -- those of the timesteps it
+    executes, t <= n_steps - 1, and the t = T slot for ``sample_chain_from`` over the whole chain; ``fused=True`` (``refine_chain``) never has
+    that one."""
+    nk = T // ret_interval
+    times = [(nk - k) * ret_interval for k in range(nk)]
+    if n_steps is None:
+        return times
+    return [t for t in times if t <= n_steps - 1 or (t == T == n_steps and not fused)]
+
+
 class ShapeContext:
     """Per-batch static operands living in one device buffer (dfx_shape_ctx_prepare)."""
 
@@ -321,9 +333,21 @@ class DenoiserEngine:
         return (out, xs) if want_xstart else out
 
     def sample_chain_ddim(self, ctx, seg, steps, eta, x_T_noise=None, step_noise=None, seed=None, ret_interval=None, shape_offset=0,
-                          generator=None):
+                          generator=None, x_init=None, n_steps=None, hold=None):
         """DDIM chain in one launch over the ascending step list ``steps`` (executed in reverse).  Returns
-        (pred, traj or None); traj slots follow ``snapshot_times``; only timesteps in ``steps`` are written."""
+        (pred, traj or None); traj slots follow ``snapshot_times``; only timesteps in ``steps`` are written.
+
+        ``x_init`` (B,3,N): a partial DDIM chain from that state instead of from noise -- ``x_init`` enters timestep ``steps[-1]``, every entry
+        lies below ``n_steps`` (default ``steps[-1] + 1``; resuming from the snapshot labelled t: ``n_steps = t`` and the list's entries below t),
+        ``hold`` as in ``sample_chain_from``; traj then holds the executed slots only."""
+        if x_init is not None:
+            if x_T_noise is not None:
+                raise RuntimeError("sample_chain_ddim: x_init and x_T_noise exclude each other")
+            steps = [int(v) for v in steps]
+            return self._chain_from("sample_chain_ddim", ctx, seg, x_init, (steps[-1] + 1 if steps else 1) if n_steps is None else n_steps, None,
+                                    step_noise, seed, ret_interval, shape_offset, hold, generator, steps, eta)
+        if hold is not None or n_steps is not None:
+            raise RuntimeError("sample_chain_ddim: hold / n_steps belong to the x_init route")
         seed = 0 if (x_T_noise is not None and step_noise is not None and seed is None) else resolve_seed(seed, generator)
         seg = self._seg(seg, self.device)
         B, N = seg.shape
@@ -351,7 +375,95 @@ class DenoiserEngine:
         _ffi.check(rc, "dfx_sample_chain_ddim")
         return pred, traj
 
-    def snapshot_times(self, ret_interval):
+    def snapshot_times(self, ret_interval, n_steps=None, fused=False):
+        """Timesteps of the traj slots, descending; with ``n_steps`` those a partial chain returns (module-level ``snapshot_times``)."""
+        return snapshot_times(self.num_timesteps, ret_interval, n_steps, fused)
+
+    # ---- partial chains: the last n_steps timesteps from a caller's cloud ----
+    @staticmethod
+    def hold_mask(hold, B, device=None):
+        """``hold`` as the (B,) int32 bitmask of the C-ABI (bit j = part j is held): from a (B,) integer bitmask or a (B, n_class) 0/1 tensor."""
+        if hold is None:
+            return None
+        hold = torch.as_tensor(hold)
+        if hold.dim() == 2:
+            if hold.shape[0] != B or hold.shape[1] > 31:
+                raise RuntimeError(f"hold: expected (B,) or (B,n_class) with B={B}, got {tuple(hold.shape)}")
+            bits = (hold != 0).to(torch.int32) << torch.arange(hold.shape[1], dtype=torch.int32, device=hold.device)
+            hold = bits.sum(1)
+        elif hold.dim() != 1 or hold.shape[0] != B or hold.is_floating_point():
+            raise RuntimeError(f"hold: expected a (B,) integer bitmask or a (B,n_class) 0/1 tensor with B={B}, got {tuple(hold.shape)} {hold.dtype}")
+        return hold.to(device=device if device is not None else hold.device, dtype=torch.int32).contiguous()
+
+    def _chain_from(self, what, ctx, seg, x, n_steps, start_noise, step_noise, seed, ret_interval, shape_offset, hold, generator, steps=None, eta=0.0):
+        """Common driver of sample_chain_from / refine_chain (steps None) and the x_init route of sample_chain_ddim."""
         T = self.num_timesteps
-        nk = T // ret_interval
-        return [(nk - k) * ret_interval for k in range(nk)]
+        n_steps = int(n_steps)
+        if not 1 <= n_steps <= T:
+            raise RuntimeError(f"{what}: n_steps={n_steps} outside [1,{T}]")
+        if x is None:
+            raise RuntimeError(f"{what}: the start cloud is None")
+        fused = what == "refine_chain"
+        drawn = step_noise is None or (fused and start_noise is None)
+        seed = resolve_seed(seed, generator) if (drawn or seed is not None) else 0
+        seg = self._seg(seg, self.device)
+        B, N = seg.shape
+        f = lambda t: None if t is None else t.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        x, start_noise, step_noise = f(x), f(start_noise), f(step_noise)
+        n_exec = n_steps if steps is None else len(steps)
+        if tuple(x.shape) != (B, 3, N):
+            raise RuntimeError(f"{what}: the start cloud must be (B,3,N) = {(B, 3, N)}, got {tuple(x.shape)}")
+        if start_noise is not None and tuple(start_noise.shape) != (B, 3, N):
+            raise RuntimeError(f"{what}: start_noise must be {(B, 3, N)}, got {tuple(start_noise.shape)}")
+        if step_noise is not None and tuple(step_noise.shape) != (n_exec, B, 3, N):
+            raise RuntimeError(f"{what}: step_noise must be {(n_exec, B, 3, N)}, got {tuple(step_noise.shape)}")
+        if steps is not None and (not steps or steps[0] != 0 or max(steps) >= n_steps):
+            raise RuntimeError(f"{what}: the step list must start at 0 and stay below n_steps={n_steps}, got {steps}")
+        hold = self.hold_mask(hold, B, self.device)
+        pad = self._pad(N)
+        if pad:
+            pred, traj = self._chain_from(what, ctx, self._pad_seg(seg, pad), self._pad_last(x, pad), n_steps, self._pad_last(start_noise, pad),
+                                          self._pad_last(step_noise, pad), seed, ret_interval, shape_offset, hold, None, steps, eta)
+            return pred[:, :N].contiguous(), None if traj is None else traj[:, :, :N].contiguous()
+        pred = torch.empty(B, N, 3, dtype=torch.float32, device=self.device)
+        traj, ri, keep = None, 0, []
+        if ret_interval:
+            ri = int(ret_interval)
+            times = self.snapshot_times(ri)
+            if steps is None:
+                keep = [k for k, t in enumerate(times) if t in self.snapshot_times(ri, n_steps, fused)]
+            else:
+                keep = [k for k, t in enumerate(times) if t in steps]
+            traj = torch.empty(len(times), B, N, 3, dtype=torch.float32, device=self.device)   # the kernels index the slots of the whole chain
+        L = _ffi.lib()
+        with torch.cuda.device(self.device):
+            tail = (int(seed), int(shape_offset), _ffi.ptr(hold), ri, _ffi.ptr(traj), _ffi.ptr(pred), B, N, _ffi.current_stream())
+            if steps is not None:
+                arr = (ctypes.c_int32 * len(steps))(*steps)
+                rc = L.dfx_sample_chain_ddim_from(self._h, _ffi.ptr(ctx.buf), _ffi.ptr(seg), arr, len(steps), float(eta), _ffi.ptr(x),
+                                                  _ffi.ptr(step_noise), *tail)
+            elif fused:
+                rc = L.dfx_refine_chain(self._h, _ffi.ptr(ctx.buf), _ffi.ptr(seg), _ffi.ptr(x), n_steps, _ffi.ptr(start_noise),
+                                        _ffi.ptr(step_noise), *tail)
+            else:
+                rc = L.dfx_sample_chain_from(self._h, _ffi.ptr(ctx.buf), _ffi.ptr(seg), _ffi.ptr(x), n_steps, _ffi.ptr(step_noise), *tail)
+        _ffi.check(rc, what)
+        if traj is not None:   # executed slots only (for the DDPM forms a contiguous tail of the buffer: a view)
+            contiguous = keep == list(range(len(times) - len(keep), len(times)))
+            traj = traj[len(times) - len(keep):] if contiguous else traj[keep]
+        return pred, traj
+
+    def sample_chain_from(self, ctx, seg, x, n_steps, step_noise=None, seed=None, ret_interval=None, shape_offset=0, hold=None, generator=None):
+        """The last ``n_steps`` timesteps (n_steps-1 .. 0) of the reverse chain from the state ``x`` (B,3,N), one launch: resume from a
+        snapshot (the traj slot labelled t takes ``n_steps = t``; the t = T slot takes T), or denoise a noisy cloud.  ``step_noise``
+        (n_steps,B,3,N) or None -> Philox, keyed as in ``sample_chain``: the same seed continues a chain bit for bit.  ``hold``: (B,) bitmask
+        or (B,n_class) 0/1 -- the points of held parts come back as they are in ``x``, in pred and in every snapshot.  Returns
+        (pred (B,N,3), traj or None); traj holds the slots ``snapshot_times(ret_interval, n_steps)`` only."""
+        return self._chain_from("sample_chain_from", ctx, seg, x, n_steps, None, step_noise, seed, ret_interval, shape_offset, hold, generator)
+
+    def refine_chain(self, ctx, seg, x_start, n_steps, start_noise=None, step_noise=None, seed=None, ret_interval=None, shape_offset=0, hold=None,
+                     generator=None):
+        """Variations of the CLEAN cloud ``x_start`` (B,3,N) at strength ``n_steps``: forward-noised to t = n_steps-1 in the kernel's prologue
+        (``start_noise`` (B,3,N) or Philox), then ``n_steps`` reverse steps -- bit-identical to ``q_sample`` + ``sample_chain_from``, one
+        launch.  traj holds the slots ``snapshot_times(ret_interval, n_steps, fused=True)``."""
+        return self._chain_from("refine_chain", ctx, seg, x_start, n_steps, start_noise, step_noise, seed, ret_interval, shape_offset, hold, generator)

@@ -300,6 +300,31 @@ class AnchoredDiffusion(nn.Module):
                                                 step_noise=step_noise, seed=seed, ret_interval=ret_interval,
                                                 shape_offset=shape_offset, generator=generator)
 
+    @torch.no_grad()
+    def sample_chain_from(self, ctx, anchor_assignment, x, n_steps, valid_id=None, step_noise=None, seed=None, ret_interval=None,
+                          shape_offset=0, hold=None, generator=None):
+        """The last ``n_steps`` timesteps of the reverse chain from the state ``x`` (B,3,N), one launch (``DenoiserEngine.sample_chain_from``):
+        resume from a snapshot of ``sample_chain`` (the slot labelled t takes ``n_steps = t``), or denoise a noisy cloud.  ``hold``: parts whose
+        points come back untouched.  With DDIM sampling the entries of ``self.steps`` below ``n_steps`` are executed."""
+        eng, sc = self.model.engine(), self._sc(ctx, valid_id)
+        if self.ddim_sampling:
+            return eng.sample_chain_ddim(sc, anchor_assignment, [s for s in self.steps if s < n_steps], self.ddim_eta, step_noise=step_noise,
+                                         seed=seed, ret_interval=ret_interval, shape_offset=shape_offset, generator=generator, x_init=x,
+                                         n_steps=n_steps, hold=hold)
+        return eng.sample_chain_from(sc, anchor_assignment, x, n_steps, step_noise=step_noise, seed=seed, ret_interval=ret_interval,
+                                     shape_offset=shape_offset, hold=hold, generator=generator)
+
+    @torch.no_grad()
+    def refine_chain(self, ctx, anchor_assignment, x_start, n_steps, valid_id=None, start_noise=None, step_noise=None, seed=None,
+                     ret_interval=None, shape_offset=0, hold=None, generator=None):
+        """Variations of the clean cloud ``x_start`` (B,3,N) at strength ``n_steps``: q_sample to t = n_steps-1 fused into the ``n_steps``-step
+        reverse chain, one launch (``DenoiserEngine.refine_chain``)."""
+        if self.ddim_sampling:
+            _unsupported("refine_chain with DDIM sampling (q_sample + sample_chain_from on the step list instead)")
+        return self.model.engine().refine_chain(self._sc(ctx, valid_id), anchor_assignment, x_start, n_steps, start_noise=start_noise,
+                                                step_noise=step_noise, seed=seed, ret_interval=ret_interval, shape_offset=shape_offset,
+                                                hold=hold, generator=generator)
+
     def training_losses(self, x_start, t, anchors=None, variance=None, ctx=None, reduce=True, anchor_assignment=None,
                         valid_id=None, flags=None, noise=None):
         """anchored_diffusion.py:760-853: {'mse_loss'} of the epsilon objective at per-shape timesteps ``t`` (B,)

@@ -331,6 +331,27 @@ class AnchorDiffAE(nn.Module):
             pred = {k: v.detach().cpu() if isinstance(v, torch.Tensor) else v for k, v in pred.items()}
             return [(pred, "sample")]
 
+    @torch.no_grad()
+    def refine(self, pcds, n_steps, parts=None, each=1, device="cuda", seed=None):
+        """``each`` variations of every shape of a batch at strength ``n_steps``: the clouds ``pcds["ref"]`` are noised to step n_steps-1 and
+        denoised again under the batch's own latents, taken as the reconstruction branch of ``forward`` takes them (the encoder on the
+        batch, one aligner noise per shape with cIMLE), in ONE launch (``editing.vary_shape``).  ``parts``: the parts to regenerate, the
+        points of the other parts come back untouched; None: the whole cloud.  ``pcds``: a val batch or ``data.PartCloudSet.batch``'s.
+        Returns ``vary_shape``'s dict ('pred' (B,each,N,3), 'seg_mask', 'held') + 'input_ref', 'present'."""
+        from . import editing
+        ref = pcds["ref"].to(device)
+        seg_mask = pcds["ref_seg_mask"].to(device)
+        valid_id = pcds.get("present", None)
+        valid_id = None if valid_id is None else valid_id.to(device)
+        if self.cimle:
+            noise, _ = self.encoder.sample_noise(pcds, device, 1)
+            ctx, _mean_pp, _logvar_pp, _, _, _latents = self.encoder(pcds, device, noise=noise)
+        else:
+            ctx, _mean_pp, _logvar_pp, _flag, _losses, _latents = self.encoder(pcds, device, epoch=0)
+        out = editing.vary_shape(self.diffusion, ctx, seg_mask, ref, n_steps, parts=parts, each=each, valid_id=valid_id, seed=seed)
+        out.update({"input_ref": ref, "present": valid_id})
+        return out
+
     # ------------------------------------------------------------------------------------------------------------------
     # Editing modes (anchor_gen.py:206-532).  Each is ONE dfx_compose_latents call (the latent rows of every edit: code lerp /
     # part swap, aligner, anchor edit, seg ids, per-point gathers) and ONE persistent chain launch over all B*K rows (the

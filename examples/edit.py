@@ -18,6 +18,12 @@ dfx_noise_opt_run call and one chain launch (editing.reconfigure_part).  Writes 
 samples new styles instead (the reference's tools/run_sample_one_part.py): --each new styles of part --resample-part per shape; among --candidates
 aligner noises per style the one that keeps the other parts where they were, or with --free-size the first / the --params most diverse ones
 (--selective); one dfx_part_search call for all shapes, one chain launch (editing.sample_part).  Writes resample.npy (shapes, each, params, N, 3).
+
+    python examples/edit.py --vary --steps-back 40 --parts 1 --each 4
+
+makes variations of EXISTING clouds instead (here: the shapes' own generated clouds): each cloud is noised --steps-back steps back and denoised again,
+--each times with different noise; only the points of --parts are regenerated (all parts without --parts), the other parts' points come back bit
+for bit.  One dfx_refine_chain launch for all shapes x each rows (editing.vary_shape).  Writes vary.npy (shapes, each, N, 3) and vary_base.npy.
 """
 import argparse
 import os
@@ -28,7 +34,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from difffacto_amd import editing, synth  # noqa: E402
+from difffacto_amd import editing, modules, synth  # noqa: E402
 from generate import NPOINTS, build  # noqa: E402
 
 
@@ -52,6 +58,9 @@ def main():
     ap.add_argument("--params", type=int, default=1, help="--resample-part --free-size: configurations per new style")
     ap.add_argument("--selective", action="store_true", help="--resample-part --free-size: the most diverse configurations instead of the first")
     ap.add_argument("--candidates", type=int, default=100, help="--resample-part: aligner noises searched per new style")
+    ap.add_argument("--vary", action="store_true", help="variations of the shapes' generated clouds: noise --steps-back steps, denoise again")
+    ap.add_argument("--steps-back", type=int, default=40, help="--vary: strength, 1 .. --timesteps")
+    ap.add_argument("--parts", type=int, nargs="*", default=None, help="--vary: regenerate these parts only, hold the others (default: all)")
     a = ap.parse_args()
 
     enc, diff = build(a.config, a.timesteps, a.precision, 0)
@@ -71,6 +80,23 @@ def main():
     g = torch.Generator().manual_seed(a.seed)
     codes = enc.sampler().flow_reverse(torch.randn(B, enc.zdim, enc.n_class, generator=g).cuda())   # part codes from the flow prior
     os.makedirs(a.out_dir, exist_ok=True)
+    if a.vary:
+        valid = torch.ones(B, enc.n_class, device="cuda")
+        ctx, _mean_pp, _logvar_pp, seg, valid, _lat = enc.compose_latents(codes, np.repeat(np.arange(B, dtype=np.int32)[:, None], enc.n_class, 1),
+                                                                          valid, N, noise_src=editing._noise(enc, B, "cuda", g))
+        base = modules.decode(diff, ctx, seg, valid_id=valid, seed=a.seed)["pred"]                     # the clouds to vary (B,N,3)
+        out = editing.vary_shape(diff, ctx, seg, base, a.steps_back, parts=a.parts, each=a.each, valid_id=valid, seed=a.seed + 1)
+        pred = out["pred"]
+        held = (out["held"][:, None, :].expand(B, a.each, -1).gather(2, out["seg_mask"].long()) != 0)   # (B,each,N): points of held parts
+        same = torch.equal(pred[held], base[:, None].expand_as(pred)[held])
+        np.save(os.path.join(a.out_dir, "vary.npy"), pred.cpu().numpy())
+        np.save(os.path.join(a.out_dir, "vary_base.npy"), base.cpu().numpy())
+        np.save(os.path.join(a.out_dir, "vary_seg.npy"), out["seg_mask"].cpu().numpy())
+        moved = float((pred - base[:, None]).abs().amax()) if pred.numel() else 0.0
+        print(f"vary: {B * a.each} rows in one launch, {a.steps_back} of {a.timesteps} steps back, parts {a.parts if a.parts is not None else 'all'}; "
+              f"held points {int(held.sum())} of {held.numel()} unchanged: {same}; largest move {moved:.3f}; clouds {tuple(pred.shape)}, "
+              f"finite: {bool(torch.isfinite(pred).all())} -> {a.out_dir}/vary.npy")
+        return
     if a.resample_part is not None:
         # the shapes' own configuration: the aligner's parameters under one noise draw per shape
         valid = torch.ones(B, enc.n_class)

@@ -226,6 +226,39 @@ int dfx_sample_chain_ddim(const dfx_denoiser *d, const void *shape_ctx, const in
                           int n_steps, float eta, const float *x_T_noise, const float *step_noise, uint64_t seed,
                           uint64_t shape_offset, int ret_interval, float *traj, float *pred, int B, int N, dfx_stream_t stream);
 
+/* Partial reverse chains (dfx_version() >= 108): the LAST n_steps timesteps, n_steps-1 .. 0, from a caller's cloud instead of from pure noise —
+ * variations of a cloud at a chosen strength, cleaning a noisy cloud, resuming from a snapshot.  1 <= n_steps <= T.  The step arithmetic is
+ * dfx_sample_chain's (the same kernels, instantiated with another prologue), so resuming a chain from one of its own snapshots with the same
+ * seed continues it bit for bit.
+ *   dfx_sample_chain_from       x_init (B,3,N) is the state entering timestep n_steps-1.  Snapshots are labelled by the timestep that has just
+ *                               run: traj slot k holds the state AFTER timestep t = (T / ret_interval - k) * ret_interval, so resuming from the
+ *                               slot labelled t takes n_steps = t; slot 0 (t = T, when ret_interval divides T) is the first state and takes n_steps = T.
+ *   dfx_refine_chain            x_start (B,3,N) is a CLEAN cloud: the prologue forward-noises it to t = n_steps-1,
+ *                               x = sqrt_acp[t] (x0 - a) + a + sqrt(1 - acp[t]) L z, in dfx_q_sample_f32's operation order — the result is bit-identical
+ *                               to dfx_q_sample_f32 followed by dfx_sample_chain_from.  start_noise (B,3,N) = z, or NULL -> Philox.
+ *   dfx_sample_chain_ddim_from  DDIM over the ascending HOST list `steps` (steps[0] == 0, every entry < T), executed in reverse from
+ *                               x_init, the state entering timestep steps[n-1]: the tail of a longer DDIM chain's list resumes that chain.
+ *   step_noise  (n_steps,B,3,N) / (n,B,3,N), step_noise[i] = z of the i-th EXECUTED step (t = n_steps-1-i), or NULL -> Philox
+ *   hold        NULL, or (B,) int32 on the device: bit j set = the points of part j (seg == j) are HELD — wherever the chain writes such a
+ *               point, in pred and in every snapshot, it writes the caller's x_init / x_start coordinates.  Held points still run through
+ *               the network (a point's update does not depend on other points, so the others are what they are without `hold`).
+ *   traj        NULL, or the (n_keep,B,N,3) buffer of dfx_sample_chain with the same slot meaning; only the slots of executed timesteps are written
+ *               (t <= n_steps-1, or the list's entries), the others are left untouched.  The t = T slot is written by dfx_sample_chain_from with
+ *               n_steps == T only; never by dfx_refine_chain (its first state is not a snapshot of anything) or the DDIM form.
+ * Philox keys, (seed, global point id, counter word, stream), global point id = (shape_offset + b) * N + n:
+ *     step noise of timestep t            (t, 0)          every chain entry point
+ *     x_T draw of dfx_sample_chain[_ddim] (T, 1)
+ *     start noise of dfx_refine_chain     (n_steps, 1)    stream 1 like the x_T draw (n_steps = T is that draw): never a step-noise counter */
+int dfx_sample_chain_from(const dfx_denoiser *d, const void *shape_ctx, const int32_t *seg, const float *x_init, int n_steps,
+                          const float *step_noise, uint64_t seed, uint64_t shape_offset, const int32_t *hold, int ret_interval,
+                          float *traj, float *pred, int B, int N, dfx_stream_t stream);
+int dfx_refine_chain(const dfx_denoiser *d, const void *shape_ctx, const int32_t *seg, const float *x_start, int n_steps,
+                     const float *start_noise, const float *step_noise, uint64_t seed, uint64_t shape_offset, const int32_t *hold,
+                     int ret_interval, float *traj, float *pred, int B, int N, dfx_stream_t stream);
+int dfx_sample_chain_ddim_from(const dfx_denoiser *d, const void *shape_ctx, const int32_t *seg, const int32_t *steps, int n_steps,
+                               float eta, const float *x_init, const float *step_noise, uint64_t seed, uint64_t shape_offset,
+                               const int32_t *hold, int ret_interval, float *traj, float *pred, int B, int N, dfx_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Chamfer-L2 — replaces the `chamfer` extension
  * (python/difffacto/metrics/chamfer_dist/chamfer.cu: forward :15-170, backward :173-230; bound in
