@@ -208,6 +208,9 @@ SIGNATURES = {
     "dfx_debug_bare_mfma": (_I, [_I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double), _P]),
     "dfx_debug_pipe_waves": (None, [_I]),
     "dfx_debug_plan_variant": (ctypes.c_char_p, [_I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]),
+    "dfx_debug_ff16_pack_w1": (None, [_P, _P, _P, _P, _I, _I, _P]),   # host pointers
+    "dfx_debug_ff16_pack_w2": (None, [_P, _I, _P]),
+    "dfx_debug_ff16_slot_ops": (None, [_P]),
     "dfx_debug_trace": (None, [_P, _I]),
     "dfx_set_event_timing": (None, [_I]),
     "dfx_last_kernel_ms": (_F, []),

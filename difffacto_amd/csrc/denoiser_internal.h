@@ -17,6 +17,8 @@
 //           W[row0 + i][k0 + (e&3) + 16q + 8(e>>2) + 4hf]
 //     f32  (v_mfma_f32_32x32x2_f32)  : 4 units (r4), element e<4  (register r = 4 r4 + e):
 //           W[row0 + i][k0 + e + 8 r4 + 4hf]
+//     bf16 feed-forward tiles (W1 bf16, W2 fp16; v_mfma_f32_16x16x32): 2 units = the two 16-row M-tiles over all 32 k,
+//           element order in denoiser_ff16.h (w1_decode, w2_decode).  The attention tiles (A_s, M_s) keep the 32x32x16 form.
 //
 // "cvec" order: a 128-vector indexed by channel stored as [hf][c][r] so that a lane reads its 64
 // values contiguously (offset hf*64).

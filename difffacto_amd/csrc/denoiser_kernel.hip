@@ -10,11 +10,14 @@
 // (128 channels x 32 points) stays in 64 accumulator VGPRs for the whole chain; every dense
 // contraction is a v_mfma_f32_32x32x16_bf16 (or the exact v_mfma_f32_32x32x2_f32) with the WEIGHT
 // tile as the A operand and the register-resident activation as the B operand, so consecutive GEMMs
-// chain register-to-register.  LayerNorm / softmax / GELU / posterior are fp32 VALU on the same
+// chain register-to-register.  The bf16 feed-forward (384 of a block's 400 MFMA tiles) runs on
+// v_mfma_f32_16x16x32_{bf16,f16} instead, two 16-point N-tiles per wavefront, between two sets of
+// 16-lane row swaps (denoiser_ff16.h).  LayerNorm / softmax / GELU / posterior are fp32 VALU on the same
 // registers; the 4-key attention needs no q/k/v at run time (folded into A_s / M_s at prepare time).
 #include <cmath>
 #include <type_traits>
 
+#include "denoiser_ff16.h"
 #include "denoiser_internal.h"
 #include "denoiser_plan.h"   // (ahead of the pragma: the planner's cost arithmetic is not contracted)
 
@@ -389,24 +392,107 @@ __device__ __forceinline__ void gelu16_f16_math(const h2 (&aa)[8], const h2 (&gg
   hid.f[1] = make_uint4(__builtin_bit_cast(unsigned, y[4]), __builtin_bit_cast(unsigned, y[5]), __builtin_bit_cast(unsigned, y[6]),
                         __builtin_bit_cast(unsigned, y[7]));
 }
-// h_tile += W2 fragment (A, from LDS / L2) x hid fragment (B)
-__device__ __forceinline__ v16f mma_hid(const uint4 &w, const uint4 &hid, v16f acc) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8h, w), __builtin_bit_cast(v8h, hid), acc, 0, 0, 0);
+// ---- the bf16 feed-forward on v_mfma_f32_16x16x32 (layout algebra: denoiser_ff16.h) --------------------------------------
+// The smaller shape costs the same cycles per FLOP and the same LDS bytes per FLOP (every fragment feeds two MFMAs, one per
+// 16-point N-tile), and the chip holds a higher clock on it under the power cap.  Everything outside GEMM1 / GELU / GEMM2 keeps
+// one point per lane; 16-lane row swaps move xn and h between the two forms, exactly (they move bits).
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
+typedef unsigned v2u __attribute__((ext_vector_type(2)));
+// x, y -> (x0, y0, x2, y2), (x1, y1, x3, y3) by 16-lane rows; its own inverse
+__device__ __forceinline__ void row_swap(unsigned &x, unsigned &y) {
+  const v2u r = __builtin_amdgcn_permlane16_swap(x, y, false, false);
+  x = r[0], y = r[1];
+}
+// LayerNorm3's output (one point per lane) -> xn[c].f[n] = GEMM1's B operand of N-tile n, K step c: 16 swaps
+__device__ __forceinline__ void ff16_rows(Act<DFX_PREC_BF16> (&xn)[4]) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    v4u x = __builtin_bit_cast(v4u, xn[c].f[0]), y = __builtin_bit_cast(v4u, xn[c].f[1]);
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      unsigned a = x[v], b = y[v];
+      row_swap(a, b);
+      x[v] = a, y[v] = b;
+    }
+    xn[c].f[0] = __builtin_bit_cast(v8bf, x), xn[c].f[1] = __builtin_bit_cast(v8bf, y);
+  }
+}
+__device__ __forceinline__ void ff16_rows(Act<DFX_PREC_F32> (&)[4]) {}
+// one 32-channel tile of h: quads 2t + n <-> the accumulators of M-tile t, N-tile n (8 swaps, in place; the same call brings it back)
+__device__ __forceinline__ void ff16_rows(v16f &h) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      unsigned a = __float_as_uint(h[8 * t + r]), b = __float_as_uint(h[8 * t + 4 + r]);
+      row_swap(a, b);
+      h[8 * t + r] = __uint_as_float(a), h[8 * t + 4 + r] = __uint_as_float(b);
+    }
+}
+__device__ __forceinline__ void ff16_rows(v16f (&h)[4]) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) ff16_rows(h[c]);
+}
+__device__ __forceinline__ v4f quad(const v16f &x, int q) { return v4f{x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]}; }
+__device__ __forceinline__ void set_quad(v16f &x, int q, const v4f &v) { x[4 * q] = v[0], x[4 * q + 1] = v[1], x[4 * q + 2] = v[2], x[4 * q + 3] = v[3]; }
+// GEMM1: quads 2n + mt of acc (a or g) += W1 fragment of M-tile mt (A) x xn unit n (B), n = 0, 1; first: C = 0
+__device__ __forceinline__ void mma16_w1(v16f &acc, int mt, const uint4 &w, const Act<DFX_PREC_BF16> &x, bool first) {
+#pragma unroll
+  for (int n = 0; n < 2; ++n) {
+    const v4f c = first ? v4f{0.f, 0.f, 0.f, 0.f} : quad(acc, 2 * n + mt);
+    set_quad(acc, 2 * n + mt, __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, w), x.f[n], c, 0, 0, 0));
+  }
+}
+// GEMM2: quads 2 mt + n of one tile of h (after ff16_rows) += W2 fragment of M-tile mt (A, fp16) x hid unit n (B)
+__device__ __forceinline__ void mma16_w2(v16f &ht, int mt, const uint4 &w, const uint4 &hid0, const uint4 &hid1) {
+  set_quad(ht, 2 * mt, __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(v8h, w), __builtin_bit_cast(v8h, hid0), quad(ht, 2 * mt), 0, 0, 0));
+  set_quad(ht, 2 * mt + 1, __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(v8h, w), __builtin_bit_cast(v8h, hid1), quad(ht, 2 * mt + 1), 0, 0, 0));
 }
 
 // One hidden chunk (32 units) of the GEGLU feed-forward (attention.py:50-57,77-94):
 //   a = W1a xn + b1a; g = W1g xn + b1g; hid = a * gelu(g); h += W2[:, chunk] hid.  Hidden stays in registers.
-template <int PREC>
-__device__ __forceinline__ void ff_chunk(v16f (&h)[4], const Act<PREC> (&xn)[4], const uint4 *ck, const uint4 *ck2,
+// bf16 (direct kernel): xn and h in the 16x16x32 form (ff16_rows), `b1` = this lane row's eight initialisers of a (g: + 32)
+__device__ __forceinline__ void ff_chunk(v16f (&h)[4], const Act<DFX_PREC_BF16> (&xn)[4], const uint4 *ck, const uint4 *ck2,
                                          const float *b1, bool fold) {
-  constexpr int TSTRIDE = tile_units(PREC) * 64;
-  v16f a, g;
-  if (PREC == DFX_PREC_BF16 && fold) {
-    a = zero16(), g = zero16();   // b1' rides on the constant-one K slot (bias_slot_one)
-  } else {                        // fp32, and bf16 engines whose weights ruled the fold out (DenoiserDev::w1_fold = 0): plain W1', b1' initialisers
-    load16(a, b1);
-    load16(g, b1 + 32);
+  v16f a = zero16(), g = zero16();   // fold: b1' rides on the constant-one K slot (bias_slot_one)
+  if (!fold) {                       // engines whose weights ruled the fold out (DenoiserDev::w1_fold = 0): plain W1', b1' initialisers
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const v4f ia = *reinterpret_cast<const v4f *>(b1 + 4 * m), ig = *reinterpret_cast<const v4f *>(b1 + 32 + 4 * m);
+      set_quad(a, m, ia), set_quad(a, 2 + m, ia), set_quad(g, m, ig), set_quad(g, 2 + m, ig);
+    }
   }
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      mma16_w1(a, m, ck[(0 + c) * 128 + m * 64], xn[c], false);
+      mma16_w1(g, m, ck[(4 + c) * 128 + m * 64], xn[c], false);
+    }
+  v16f hid;
+#pragma unroll
+  for (int r = 0; r < 16; ++r)   // g and `a` arrive pre-scaled, hid carries the same factors, W2 is fp16 (denoiser_internal.h)
+    hid[r] = a[r] * gelu_fast(g[r] * (1.0f / FF_G_SCALE)) * FF_G_SCALE;
+  HidAct hf16;
+  h2 y[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) y[i] = pk_f16(hid[2 * i], hid[2 * i + 1]);
+  hf16.f[0] = make_uint4(__builtin_bit_cast(unsigned, y[0]), __builtin_bit_cast(unsigned, y[1]), __builtin_bit_cast(unsigned, y[2]),
+                         __builtin_bit_cast(unsigned, y[3]));
+  hf16.f[1] = make_uint4(__builtin_bit_cast(unsigned, y[4]), __builtin_bit_cast(unsigned, y[5]), __builtin_bit_cast(unsigned, y[6]),
+                         __builtin_bit_cast(unsigned, y[7]));
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int m = 0; m < 2; ++m) mma16_w2(h[t], m, ck2[(8 + t) * 128 + m * 64], hf16.f[0], hf16.f[1]);
+}
+// fp32 (direct kernel)
+__device__ __forceinline__ void ff_chunk(v16f (&h)[4], const Act<DFX_PREC_F32> (&xn)[4], const uint4 *ck, const uint4 *ck2,
+                                         const float *b1, bool) {
+  constexpr int PREC = DFX_PREC_F32, TSTRIDE = tile_units(PREC) * 64;
+  v16f a, g;
+  load16(a, b1);
+  load16(g, b1 + 32);
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     mma_tile<PREC>(a, ck + (0 + c) * TSTRIDE, xn[c]);
@@ -414,29 +500,7 @@ __device__ __forceinline__ void ff_chunk(v16f (&h)[4], const Act<PREC> (&xn)[4],
   }
   v16f hid;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    if (PREC == DFX_PREC_BF16)   // g arrives pre-scaled, hid carries the same factor (denoiser_internal.h)
-      hid[r] = a[r] * gelu_for<PREC>(g[r] * (1.0f / FF_G_SCALE)) * FF_G_SCALE;
-    else
-      hid[r] = a[r] * gelu_for<PREC>(g[r]);
-  }
-  if (PREC == DFX_PREC_BF16) {   // `a` arrives pre-scaled, W2 is fp16 (denoiser_internal.h)
-    HidAct hf16;
-    h2 y[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) y[i] = pk_f16(hid[2 * i], hid[2 * i + 1]);
-    hf16.f[0] = make_uint4(__builtin_bit_cast(unsigned, y[0]), __builtin_bit_cast(unsigned, y[1]), __builtin_bit_cast(unsigned, y[2]),
-                           __builtin_bit_cast(unsigned, y[3]));
-    hf16.f[1] = make_uint4(__builtin_bit_cast(unsigned, y[4]), __builtin_bit_cast(unsigned, y[5]), __builtin_bit_cast(unsigned, y[6]),
-                           __builtin_bit_cast(unsigned, y[7]));
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const uint4 *w = ck2 + (8 + t) * TSTRIDE;
-      h[t] = mma_hid(w[0], hf16.f[0], h[t]);
-      h[t] = mma_hid(w[64], hf16.f[1], h[t]);
-    }
-    return;
-  }
+  for (int r = 0; r < 16; ++r) hid[r] = a[r] * gelu_erf(g[r]);
   Act<PREC> ha;
   ha.set(hid);
 #pragma unroll
@@ -480,8 +544,10 @@ struct Tracer {
 // two MFMAs are four MFMAs apart: a dependent accumulate right behind its predecessor waits for it when the wave is alone on its SIMD);
 // W1 unit order (c, q, part) -> tile part*4 + c, unit q (half 0: c = 0,1; half 1: c = 2,3).  Attention record: A_s tiles
 // 0..3, M_s tiles 4..7.
-__device__ __forceinline__ constexpr int w2_frag(int i) { return (8 + (i & 3)) * 128 + (i >> 2) * 64; }   // tile i & 3, unit i >> 2: four accumulators in rotation
-__device__ __forceinline__ constexpr int w1_frag(int i, int half) { return ((i & 1) * 4 + 2 * half + (i >> 2)) * 128 + ((i >> 1) & 1) * 64; }
+// (FF: denoiser_ff16.h — a W1 / W2 unit is the 16-row A fragment of one M-tile over all 32 K slots, used for both N-tiles)
+using ff16::w1_frag;
+using ff16::w2_frag;
+using ff16::ff_frag;
 __device__ __forceinline__ constexpr int as_frag(int i) { return (i >> 1) * 128 + (i & 1) * 64; }
 __device__ __forceinline__ constexpr int ms_frag(int i) { return (4 + (i & 3)) * 128 + (i >> 2) * 64; }
 
@@ -490,31 +556,30 @@ __device__ __forceinline__ constexpr int ms_frag(int i) { return (4 + (i & 3)) *
 // and the wave has nothing else to issue — so the burst starts without the LDS round trip (~300 cycles per slot) and the
 // VALU-bound V slot in between carries no extra LDS instructions.  Needs the next record complete in LDS one management
 // barrier earlier: the ring runs three records ahead in five slots.
-// Interleaved M slots: every MFMA is followed by ONE LDS read that refills the fragment register it has just consumed with
-// the fragment needed eight MFMAs later (in place: the MFMA reads its A operand at issue), so the wavefront's read
+// Interleaved M slots: every fragment's MFMAs (one in the attention slots, the two N-tiles' in the feed-forward's) are followed by ONE
+// LDS read that refills the fragment register they have just consumed with the fragment needed eight fragments later (in place:
+// an MFMA reads its A operand at issue), so the wavefront's read
 // instructions issue while the matrix pipe works instead of in bursts during which it drains.  The last eight refills are
 // the tail prefetch for the next M slot.  `issue.at(i, n)` issues the wave's ring-DMA pieces between the MFMAs.
 
-// MFMA order of a full FF record (GEMM2 of chunk j-1 and GEMM1 of chunk j are independent): eight groups of
-//     GEMM2 MFMA k (accumulator h[k & 3])  |  GEMM1 MFMA 2k (a)  |  GEMM1 MFMA 2k+1 (g)
-// so that an accumulator is touched every third MFMA at the earliest (the r01 order — 8 x GEMM2, then 16 x GEMM1 with its two
-// accumulators alternating — made every GEMM1 MFMA depend on the one two before it).  Measured: no difference (B = 1: 87.7 vs
+// Fragment order of a full FF record (GEMM2 of chunk j-1 and GEMM1 of chunk j are independent; ff16::ff_frag): eight groups of
+//     GEMM2 fragment k (tile h[k & 3])  |  GEMM1 fragment 2k (a)  |  GEMM1 fragment 2k+1 (g)
+// so that an accumulator is touched every third fragment at the earliest (the r01 order — 8 x GEMM2, then 16 x GEMM1 with its two
+// accumulators alternating — made every GEMM1 MFMA depend on the one two before it).  Measured on the 32x32x16 form, one MFMA per
+// fragment: no difference (B = 1: 87.7 vs
 // 87.0 ms per chain, B = 128: within box noise) — a lone wavefront's M slot takes 41 cycles per MFMA in either order (slot trace:
 // 984 cycles), so the accumulate latency is not what stretches it; the order stays because it costs nothing and one ring loop
 // is simpler than three.
-// m-th MFMA of the record -> its A fragment (uint4 index relative to the lane's record pointer)
-__device__ __forceinline__ constexpr int ff_frag(int m) {
-  const int k = m / 3, r = m % 3;
-  if (r == 0) return w2_frag(k);
-  const int e = 2 * k + r - 1;             // GEMM1 MFMA 0..15: half e >> 3, index e & 7 within the half
-  return w1_frag(e & 7, e >> 3);
-}
 // what the next M slot of this wavefront starts with (tail prefetch): a full record (mixed order), the block's last record
 // (GEMM2 only) or the next block's attention record (A_s)
 enum { NEXT_FULL = 0, NEXT_LAST = 1, NEXT_AS = 2 };
 template <int NEXT>
 __device__ __forceinline__ constexpr int next_frag(int i) { return NEXT == NEXT_FULL ? ff_frag(i) : NEXT == NEXT_LAST ? w2_frag(i) : as_frag(i); }
 
+// On 16x16x32 tiles (denoiser_ff16.h): every fragment m = 0..23 of a full record feeds TWO MFMAs back to back, one per 16-point N-tile —
+// 48 MFMAs of 8 passes for the 24 of 16 passes before, still 24 ds_read_b128 and the same LDS bytes per FLOP; P[m & 7] is refilled behind
+// the second MFMA of its pair.  GEMM1: 2 (a, g) x 2 M-tiles x 4 K steps (K steps 0..3 in order per accumulator quad); GEMM2: 8 M-tiles
+// of h, one K = 32 instruction per quad and chunk (v_mfma_f32_16x16x32_f16), chunks 0..15 in order — the order of every kernel on this pack.
 template <bool S3, bool S1, int NEXT, class Issue>
 __device__ __forceinline__ void ff_m(v16f (&h)[4], const Act<DFX_PREC_BF16> (&xn)[4], v16f &a, v16f &g,
                                      const HidAct &hid, const uint4 *ck, uint4 (&P)[8], const uint4 *ck_next, Tracer &tr,
@@ -522,20 +587,19 @@ __device__ __forceinline__ void ff_m(v16f (&h)[4], const Act<DFX_PREC_BF16> (&xn
   __builtin_amdgcn_sched_barrier(0);
   tr.stamp(4);
   if (MFMA_PRIO) __builtin_amdgcn_s_setprio(MFMA_PRIO);
-  auto gemm1 = [&](int e, const uint4 &w) {   // GEMM1 MFMA e = 0..15
-    const int i = e & 7, half = e >> 3;
-    v16f &acc = (i & 1) ? g : a;
-    if (e < 2) {   // first MFMA of a / g: C = 0 (inline constant) — b1' rides on the constant-one K slot (bias_slot_one), no initialiser reads
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(w), xn[2 * half + (i >> 2)].f[(i >> 1) & 1], zero16(), 0, 0, 0);
-      return;
-    }
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(w), xn[2 * half + (i >> 2)].f[(i >> 1) & 1], acc, 0, 0, 0);
+  auto gemm1 = [&](int e, const uint4 &w) {   // GEMM1 fragment e = 0..15; K step 0 starts from C = 0 (inline constant): b1' rides on the constant-one K slot (bias_slot_one), no initialiser reads
+    const ff16::Op op = ff16::gemm1_op(e);
+    mma16_w1(op.part ? g : a, op.mt, w, xn[op.c], op.c == 0);
+  };
+  auto gemm2 = [&](int i, const uint4 &w) {   // GEMM2 fragment i = 0..7
+    const ff16::Op op = ff16::gemm2_op(i);
+    mma16_w2(h[op.c], op.mt, w, hid.f[0], hid.f[1]);
   };
   if (S3 && S1) {
 #pragma unroll
-    for (int m = 0; m < 24; ++m) {   // P is a ring of eight fragment registers: MFMA m takes P[m & 7], refilled in place with fragment m + 8
+    for (int m = 0; m < 24; ++m) {   // P is a ring of eight fragment registers: fragment m sits in P[m & 7], refilled in place with fragment m + 8
       const int k = m / 3, r = m % 3;
-      if (r == 0) h[k & 3] = mma_hid(P[m & 7], hid.f[k >> 2], h[k & 3]);
+      if (r == 0) gemm2(k, P[m & 7]);
       else gemm1(2 * k + r - 1, P[m & 7]);
       issue.at(m, 24);
       P[m & 7] = m + 8 < 24 ? ck[ff_frag(m + 8)] : ck_next[next_frag<NEXT>(m + 8 - 24)];
@@ -550,15 +614,15 @@ __device__ __forceinline__ void ff_m(v16f (&h)[4], const Act<DFX_PREC_BF16> (&xn
   } else {                          // last FF record of a block: GEMM2 only
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      h[i & 3] = mma_hid(P[i], hid.f[i >> 2], h[i & 3]);
+      gemm2(i, P[i]);
       issue.at(i, 8);
       P[i] = ck_next[next_frag<NEXT>(i)];
     }
   }
-  // keep the program order MFMA, read, MFMA, read, ...
+  // keep the program order MFMA, MFMA, read, MFMA, MFMA, read, ...
 #pragma unroll
   for (int i = 0; i < (S3 && S1 ? 24 : S1 ? 16 : 8); ++i) {
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
     __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
   }
   __builtin_amdgcn_sched_barrier(0);
@@ -864,10 +928,13 @@ __global__ void __launch_bounds__(NW * 64) k_denoise(const KParams p) {
       ln_to_act<PREC>(h, xn);
       const bool fold = p.d.w1_fold != 0;   // (wave-uniform)
       if (fold) bias_slot_one(xn, hf);
+      constexpr bool FF16 = PREC == DFX_PREC_BF16;   // the bf16 feed-forward runs on 16x16x32 tiles: b1' in that order (k_pack_b1)
+      if (FF16) ff16_rows(xn), ff16_rows(h);
 #pragma unroll 1
       for (int u = 0; u < FF_CHUNKS; ++u)
-        ff_chunk<PREC>(h, xn, bp.chunks + (size_t)u * CHUNK_TILES * TSTRIDE + lane,
-                       bp.chunks + (size_t)(u + FF_SKEW) * CHUNK_TILES * TSTRIDE + lane, bp.bconst + u * 64 + hf * 16, fold);
+        ff_chunk(h, xn, bp.chunks + (size_t)u * CHUNK_TILES * TSTRIDE + lane,
+                 bp.chunks + (size_t)(u + FF_SKEW) * CHUNK_TILES * TSTRIDE + lane, bp.bconst + u * 64 + (FF16 ? (lane >> 4) * 8 : hf * 16), fold);
+      if (FF16) ff16_rows(h);
       add_cvec(h, bp.bconst + BCONST_B2_OFF + hf * 64);
     }
     float eps[3];
@@ -1261,9 +1328,11 @@ __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe(const KParams p) {
       // ---- V0: finish the previous block / step, start this one ----
       DFX_SLOT(!grpA && step < p.nsteps);
       issue_in_m.m_begin();
-      if (seq > 0)  // b2 of the previous block (other block-constant buffer)
+      if (seq > 0) {  // the previous block's h back to one point per lane (32 swaps), + its b2 (other block-constant buffer)
+        ff16_rows(h);
         add_cvec(h, reinterpret_cast<const float *>(pipe_smem + L_BCONST + ((seq - 1) & 1) * BCONST_BYTES) +
                         BCONST_B2_OFF + hf * 64);
+      }
       if (b == 0) {
         PointState ps;
         ps.s = s, ps.n = n, ps.gid = gid, ps.live = live;
@@ -1304,6 +1373,8 @@ __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe(const KParams p) {
       v16f a, g;
       HidAct hid;
       bias_slot_one(xn, hf);   // b1' enters GEMM1 through channel 127's K slot: no accumulator initialisers
+      ff16_rows(xn);           // 16 + 32 row swaps: xn and h in the feed-forward's 16x16x32 form until the next V0
+      ff16_rows(h);
       DFX_SLOT(grpA);
       DFX_NEXT_RECORD();
       ff_m<false, true, NEXT_FULL>(h, xn, a, g, hid, ck, P, DFX_PEEK_RECORD(), tr, issue_in_m);
@@ -1779,6 +1850,7 @@ __device__ __forceinline__ void coop_phase_a(v4f *home, const uint4 *s_at, uint4
   Act<PREC> xo[4];
   ln_to_act<PREC>(h, xo);
   bias_slot_one(xo, hf);
+  ff16_rows(xo);   // unit n of tile c = GEMM1's B operand of N-tile n, K step c
 #pragma unroll
   for (int c = 0; c < 4; ++c) s_xn[2 * c][lane] = __builtin_bit_cast(uint4, xo[c].f[0]), s_xn[2 * c + 1][lane] = __builtin_bit_cast(uint4, xo[c].f[1]);
   hs_store4(home, h);
@@ -1798,16 +1870,17 @@ __device__ __forceinline__ void coop_draw_noise(const KParams &p, float *s_z, in
   if (lane < 8) s_z[128 + lane] = p.d.tab[(size_t)t * 8 + lane];
 }
 
-// GEMM1 of one chunk on one tile: (a, g) = W1 fragments R[cur .. cur + 15] (coop_load_w1's order) x xn3
+// GEMM1 of one chunk on one tile: (a, g) = W1 fragments R[cur .. cur + 15] (coop_load_w1's order: M-tiles 0, 1 of a, of g, per K step c) x xn3
 __device__ __forceinline__ void coop_gemm1(v16f &a, v16f &g, const uint4 (&R)[32], int cur, const uint4 (*s_xn)[64], int lane) {
   a = zero16(), g = zero16();   // b1' rides on the constant-one K slot (bias_slot_one)
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    const v8bf x0 = __builtin_bit_cast(v8bf, s_xn[2 * c][lane]), x1 = __builtin_bit_cast(v8bf, s_xn[2 * c + 1][lane]);
-    a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(R[cur + 4 * c + 0]), x0, a, 0, 0, 0);
-    g = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(R[cur + 4 * c + 2]), x0, g, 0, 0, 0);
-    a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(R[cur + 4 * c + 1]), x1, a, 0, 0, 0);
-    g = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(R[cur + 4 * c + 3]), x1, g, 0, 0, 0);
+    Act<DFX_PREC_BF16> x;
+    x.f[0] = __builtin_bit_cast(v8bf, s_xn[2 * c][lane]), x.f[1] = __builtin_bit_cast(v8bf, s_xn[2 * c + 1][lane]);
+    mma16_w1(a, 0, R[cur + 4 * c + 0], x, c == 0);
+    mma16_w1(g, 0, R[cur + 4 * c + 2], x, c == 0);
+    mma16_w1(a, 1, R[cur + 4 * c + 1], x, c == 0);
+    mma16_w1(g, 1, R[cur + 4 * c + 3], x, c == 0);
   }
 }
 // ... and its GELU: hid = a gelu(g) -> the chunk's two uint4 rows of the GELU output
@@ -1950,6 +2023,7 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams 
       if (tile_owner) {
         v16f ht;
         hs_load(ht, home + wave * 256);
+        ff16_rows(ht);   // quads = the accumulators of the tile's two M-tiles x two N-tiles; back before the store
         // hid / LDS-resident W2 fragments: a ring three chunks deep (one chunk = two dependent MFMAs = less than one LDS round trip),
         // fenced per chunk — left alone hipcc sinks every read next to its MFMA and the chain runs at LDS latency
         uint4 hq[4][2], wq[4][2];
@@ -1966,10 +2040,11 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams 
         for (int u = 0; u < FF_CHUNKS; ++u) {
           if (u + 3 < FF_CHUNKS) fetch(u + 3);
           const uint4 f0 = u < COOP_W2_FIRST ? R[2 * u] : wq[u & 3][0], f1 = u < COOP_W2_FIRST ? R[2 * u + 1] : wq[u & 3][1];
-          ht = mma_hid(f0, hq[u & 3][0], ht);
-          ht = mma_hid(f1, hq[u & 3][1], ht);
+          mma16_w2(ht, 0, f0, hq[u & 3][0], hq[u & 3][1]);
+          mma16_w2(ht, 1, f1, hq[u & 3][0], hq[u & 3][1]);
           __builtin_amdgcn_sched_barrier(0);
         }
+        ff16_rows(ht);
         hs_store_plus(home + wave * 256, ht, s_bc + BCONST_B2_OFF + hf * 64 + wave * 16);
       }
     }
@@ -1999,7 +2074,8 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams 
 //             the 32 fragment registers phase H has freed (chunks 0..7 requested behind round 0, chunks 8..15 behind round 1's MFMAs: the second
 //             tile's GELU covers their latency), so k_denoise_coop's 64 KiB LDS copy of W2 is gone and the second tile's h home, xn3 and GELU
 //             outputs take its place (153 KiB)
-// The next block's attention record, c_t row and block constants are requested behind barrier 2 (the record is only read in phase A) by all waves.
+// The next block's attention record, c_t row and block constants are requested behind barrier 2 (the record is only read in phase A) by all waves,
+// four chunks into phase G: the address arithmetic of the pieces needs registers, and right behind the barrier all 32 fragment registers are live.
 constexpr int C2_XN = 0;                                           // 2 tiles x 8 x 64 uint4
 constexpr int C2_HID = C2_XN + 2 * 8 * 1024;                       // 2 tiles x [16][2][64] uint4
 constexpr int C2_BC = C2_HID + 2 * FF_CHUNKS * 2048;               // 2 x block constants, by block parity
@@ -2086,12 +2162,15 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop2(const KParams
       }
       __syncthreads();   // 2: hid of all chunks of both tiles is in LDS; nobody reads the attention record any more
       // the next block's operands (next step's c_t row behind the last block)
-      if (b + 1 < depth) stage_block(b + 1, t, (seq + 1) & 1);
-      else if (step + 1 < p.nsteps) stage_block(0, step_t(p, step + 1, s), (seq + 1) & 1);
+      auto stage_next = [&] {
+        if (b + 1 < depth) stage_block(b + 1, t, (seq + 1) & 1);
+        else if (step + 1 < p.nsteps) stage_block(0, step_t(p, step + 1, s), (seq + 1) & 1);
+      };
       // ---- phase G: wave (gt, ct) accumulates output tile ct of tile gt, chunk after chunk (the accumulation order of the pipelined kernel), + b2
       {
         v16f ht;
         hs_load(ht, home(gt) + ct * 256);
+        ff16_rows(ht);
         uint4 hq[4][2];   // hid fragments: a ring three chunks deep, fenced per chunk (see k_denoise_coop)
         unsigned hoff = C2_HID + gt * FF_CHUNKS * 2048 + lane * 16;
         asm volatile("" : "+v"(hoff));
@@ -2102,10 +2181,15 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop2(const KParams
 #pragma unroll
         for (int u = 0; u < FF_CHUNKS; ++u) {
           if (u + 3 < FF_CHUNKS) fetch(u + 3);
-          ht = mma_hid(R[2 * u], hq[u & 3][0], ht);
-          ht = mma_hid(R[2 * u + 1], hq[u & 3][1], ht);
+          mma16_w2(ht, 0, R[2 * u], hq[u & 3][0], hq[u & 3][1]);
+          mma16_w2(ht, 1, R[2 * u + 1], hq[u & 3][0], hq[u & 3][1]);
           __builtin_amdgcn_sched_barrier(0);
+          if (u == 3) {   // (here and not at the barrier: the address arithmetic of the pieces needs registers, and the first chunks' fragments have just freed some)
+            stage_next();
+            __builtin_amdgcn_sched_barrier(0);
+          }
         }
+        ff16_rows(ht);
         hs_store_plus(home(gt) + ct * 256, ht, s_bc + BCONST_B2_OFF + hf * 64 + ct * 16);
       }
     }

@@ -18,11 +18,15 @@
 #include <cstring>
 #include <vector>
 
+#include "denoiser_ff16.h"
 #include "denoiser_internal.h"
 
 using namespace dfx;
 
 namespace {
+
+static_assert(ff16::CH == INNER && ff16::HID == FF_HID && ff16::CHUNKS == FF_CHUNKS && ff16::REC_TILES == CHUNK_TILES && ff16::SKEW == FF_SKEW,
+              "denoiser_ff16.h against denoiser_internal.h");
 
 int g_w1_fold_mode = -1;                       // dfx_debug_w1_fold: -1 = decide per engine from its weights, 0 = never, 1 = always
 constexpr float W1_FOLD_KEEP_127 = 4.0f;       // channel 127 stays the folded one while its column's ratio is at most this (bit-compatible with round 5's packs)
@@ -90,36 +94,29 @@ __device__ __forceinline__ void tile_store(void *dst, long long gi, float v) {
   else reinterpret_cast<float *>(dst)[gi] = v;
 }
 
-// W1 (1024 x 128) with norm3.weight folded in -> tiles part*4+c of chunk record u
+// W1 (1024 x 128) with norm3.weight folded in -> tiles part*4+c of chunk record u.  bf16: element order (the A operand of
+// v_mfma_f32_16x16x32_bf16, for every kernel of the engine) and value from denoiser_ff16.h
 template <int PREC>
 __global__ void k_pack_w1(const float *__restrict__ W1, const float *__restrict__ g3, void *__restrict__ dst, const float *__restrict__ b1,
                           const float *__restrict__ be3, int fold) {
   const long long gi = blockIdx.x * 256LL + threadIdx.x;
-  if (gi >= (long long)FF_CHUNKS * 2 * 4 * 1024) return;
+  if (gi >= ff16::W1_PACK_THREADS) return;
+  if (PREC == DFX_PREC_BF16) {
+    // fold (denoiser_kernel.hip: bias_slot_one): the normalised row sums to zero, so channel 127 is redundant (xhat_127 = - sum of the
+    // others): its K slot carries the constant 1 and the weight there is b1' = b1 + W1 beta3, every other weight has W1'[.][127] subtracted.
+    // Exact in real arithmetic; GEMM1 then needs no accumulator initialisers.
+    const ff16::Src s = ff16::w1_source(gi, ff16::LAYOUT_16X16X32);
+    const float sc = s.row < FF_HID ? FF_A_SCALE : FF_G_SCALE;   // (denoiser_internal.h)
+    tile_store<PREC>(dst, s.di, ff16::w1_value(W1, g3, b1, be3, s.row, s.col, fold) * sc);
+    return;
+  }
   const int tile = (int)(gi >> 10);
   int i, kk;
   tile_decode<PREC>((int)(gi & 1023), i, kk);
   const int c = tile & 3, part = (tile >> 2) & 1, u = tile >> 3;
   const int row = part * FF_HID + 32 * u + i, col = 32 * c + kk;
   const long long di = ((long long)(u * CHUNK_TILES + part * 4 + c) << 10) + (gi & 1023);
-  const float sc = PREC != DFX_PREC_BF16 ? 1.0f : part == 0 ? FF_A_SCALE : FF_G_SCALE;   // (denoiser_internal.h)
-  // bf16 path (denoiser_kernel.hip: bias_slot_one): the normalised row sums to zero, so channel 127 is redundant (xhat_127 = - sum of the
-  // others): its K slot carries the constant 1 and the weight there is b1' = b1 + W1 beta3, every other weight has W1'[.][127] subtracted.
-  // Exact in real arithmetic; GEMM1 then needs no accumulator initialisers.
-  if (PREC == DFX_PREC_BF16 && fold) {
-    const float w127 = W1[(size_t)row * INNER + 127] * g3[127];
-    float v;
-    if (col == 127) {
-      float acc = 0.f;
-      for (int k = 0; k < INNER; ++k) acc = fmaf(W1[(size_t)row * INNER + k], be3[k], acc);
-      v = b1[row] + acc;
-    } else {
-      v = W1[(size_t)row * INNER + col] * g3[col] - w127;
-    }
-    tile_store<PREC>(dst, di, v * sc);
-    return;
-  }
-  tile_store<PREC>(dst, di, W1[(size_t)row * INNER + col] * g3[col] * sc);
+  tile_store<PREC>(dst, di, W1[(size_t)row * INNER + col] * g3[col]);
 }
 
 // How much coarser the fold makes a row of W1' = W1 diag(gamma3) when channel k is the redundant one: every weight of row r becomes
@@ -151,31 +148,36 @@ __global__ void k_swap_channels(const float *__restrict__ src, float *__restrict
   dst[gi] = src[(size_t)r * cols + c];
 }
 
-// b1' = b1 + W1 beta3, stored [u][part][hf][16]
+// b1' = b1 + W1 beta3, stored [u][part][hf][16]; quads16 (bf16 engines): [u][part][R][m][4] = hidden unit 16m + 4R + r, the order of a lane row's
+// two accumulator quads under v_mfma_f32_16x16x32 (denoiser_ff16.h)
 __global__ void k_pack_b1(const float *__restrict__ W1, const float *__restrict__ b1, const float *__restrict__ be3,
-                          float *__restrict__ dst, float a_scale, float g_scale) {
+                          float *__restrict__ dst, float a_scale, float g_scale, int quads16) {
   const int gi = blockIdx.x * 256 + threadIdx.x;
   if (gi >= FF_CHUNKS * 2 * 32) return;
   const int r = gi & 15, hf = (gi >> 4) & 1, part = (gi >> 5) & 1, u = gi >> 6;
-  const int row = part * FF_HID + 32 * u + rho(r, hf);
+  const int unit = quads16 ? 16 * ((gi >> 2) & 1) + 4 * ((gi >> 3) & 3) + (gi & 3) : rho(r, hf);
+  const int row = part * FF_HID + 32 * u + unit;
   float acc = 0.f;
   for (int k = 0; k < INNER; ++k) acc = fmaf(W1[(size_t)row * INNER + k], be3[k], acc);
   dst[gi] = (b1[row] + acc) * (part == 0 ? a_scale : g_scale);
 }
 
-// W2 (128 x 512) -> tiles 8+ct of stage record u+FF_SKEW (see denoiser_internal.h)
+// W2 (128 x 512) -> tiles 8+ct of stage record u+FF_SKEW (see denoiser_internal.h; bf16: fp16 in the order of denoiser_ff16.h)
 template <int PREC>
 __global__ void k_pack_w2(const float *__restrict__ W2, void *__restrict__ dst) {
   const long long gi = blockIdx.x * 256LL + threadIdx.x;
-  if (gi >= (long long)FF_CHUNKS * 4 * 1024) return;
+  if (gi >= ff16::W2_PACK_THREADS) return;
+  if (PREC == DFX_PREC_BF16) {
+    const ff16::Src s = ff16::w2_source(gi, ff16::LAYOUT_16X16X32);
+    reinterpret_cast<_Float16 *>(dst)[s.di] = (_Float16)(W2[(size_t)s.row * FF_HID + s.col] * (1.0f / (FF_A_SCALE * FF_G_SCALE)));
+    return;
+  }
   const int tile = (int)(gi >> 10);
   int i, kk;
   tile_decode<PREC>((int)(gi & 1023), i, kk);
   const int ct = tile & 3, u = tile >> 2;
   const long long di = ((long long)((u + FF_SKEW) * CHUNK_TILES + 8 + ct) << 10) + (gi & 1023);
-  const float w = W2[(size_t)(32 * ct + i) * FF_HID + 32 * u + kk];
-  if (PREC == DFX_PREC_BF16) reinterpret_cast<_Float16 *>(dst)[di] = (_Float16)(w * (1.0f / (FF_A_SCALE * FF_G_SCALE)));
-  else tile_store<PREC>(dst, di, w);
+  tile_store<PREC>(dst, di, W2[(size_t)(32 * ct + i) * FF_HID + 32 * u + kk]);
 }
 
 // proj_in x-columns, pre_norm affine, post_norm-folded proj_out, all in cvec order
@@ -645,7 +647,7 @@ int dfx_denoiser_create(dfx_denoiser **out, const dfx_denoiser_weights *w, int T
     TRY_LAUNCH("b2_cvec");
     k_pack_b1<<<nblk(FF_CHUNKS * 2 * 32), 256, 0, st>>>(k.ff0_w, k.ff0_b, k.norm3_b, c.bconst,
                                                         precision == DFX_PREC_BF16 ? FF_A_SCALE : 1.0f,
-                                                        precision == DFX_PREC_BF16 ? FF_G_SCALE : 1.0f);
+                                                        precision == DFX_PREC_BF16 ? FF_G_SCALE : 1.0f, precision == DFX_PREC_BF16);
     TRY_LAUNCH("pack_b1");
     if (precision == DFX_PREC_BF16) {
       k_pack_w1<DFX_PREC_BF16><<<nblk((long long)FF_CHUNKS * 8 * 1024), 256, 0, st>>>(k.ff0_w, k.norm3_w, c.chunks, k.ff0_b, k.norm3_b, w1_fold);
@@ -708,6 +710,29 @@ int dfx_denoiser_w1_fold(const dfx_denoiser *d, float *ratio) {
 }
 void dfx_debug_w1_fold(int mode) { g_w1_fold_mode = mode < 0 ? -1 : mode != 0; }
 int dfx_debug_w1_fold_channel(const dfx_denoiser *d) { return d ? d->w1_fold_channel : -1; }
+
+// Host-only views of denoiser_ff16.h (no GPU): what k_pack_w1 / k_pack_w2 write for a bf16 engine, as fp32 before the scale and the rounding,
+// into `out` (FF_STAGES x CHUNK_TILES x 1024 floats, untouched where nothing is packed); layout = ff16::LAYOUT_*
+void dfx_debug_ff16_pack_w1(const float *W1, const float *g3, const float *b1, const float *be3, int fold, int layout, float *out) {
+  for (long long gi = 0; gi < ff16::W1_PACK_THREADS; ++gi) {
+    const ff16::Src s = ff16::w1_source(gi, layout);
+    out[s.di] = ff16::w1_value(W1, g3, b1, be3, s.row, s.col, fold);
+  }
+}
+void dfx_debug_ff16_pack_w2(const float *W2, int layout, float *out) {
+  for (long long gi = 0; gi < ff16::W2_PACK_THREADS; ++gi) {
+    const ff16::Src s = ff16::w2_source(gi, layout);
+    out[s.di] = W2[(size_t)s.row * FF_HID + s.col];
+  }
+}
+// The fragments of a full FF record's M slot in issue order (24 rows of {uint4 offset, gemm (1 | 2), part (0 = a, 1 = g | -1), M-tile, K step | output tile})
+void dfx_debug_ff16_slot_ops(int32_t *out) {
+  for (int m = 0; m < 24; ++m) {
+    const int k = m / 3, r = m % 3;
+    const ff16::Op op = r == 0 ? ff16::gemm2_op(k) : ff16::gemm1_op(2 * k + r - 1);
+    out[5 * m + 0] = ff16::ff_frag(m), out[5 * m + 1] = r == 0 ? 2 : 1, out[5 * m + 2] = op.part, out[5 * m + 3] = op.mt, out[5 * m + 4] = op.c;
+  }
+}
 
 int dfx_denoiser_get_tables(const dfx_denoiser *d, float *host_out) {
   DFX_REQUIRE(d && host_out, "get_tables: null argument");

@@ -32,7 +32,7 @@ extern "C" {
 
 /* arithmetic of the dense contraction (LayerNorm, softmax, GELU, posterior are fp32 in both) */
 #define DFX_PREC_F32 0  /* v_mfma_f32_32x32x2_f32: exact fp32, the parity gate            */
-#define DFX_PREC_BF16 1 /* v_mfma_f32_32x32x16_bf16: bf16 operands, fp32 accumulate       */
+#define DFX_PREC_BF16 1 /* v_mfma_f32_32x32x16 / 16x16x32: bf16 operands, fp32 accumulate */
 
 typedef void *dfx_stream_t;
 #define DFX_MAX_SIDE_STREAMS 64   /* see dfx_denoiser_train_forward */

@@ -104,6 +104,15 @@ void dfx_debug_pipe_waves(int nw);
  * and dfx_debug_pipe_waves(pipe_waves_code); *grid_out (may be NULL) = its workgroups.  A pure function of its arguments: the process-global
  * switches are not read. */
 const char *dfx_debug_plan_variant(int prec, int w1_fold, int force_direct, int pipe_waves_code, int B, int N, long long *grid_out);
+/* Host-side views (no GPU) of the bf16 feed-forward layout (csrc/denoiser_ff16.h).  dfx_debug_ff16_pack_w1 / _w2: what the pack kernels write
+ * into a block's 17 x 12 x 1024-element streaming records for W1 (1024 x 128; gamma3, b1, beta3 as in the engine, fold = the W1 bias fold) and W2
+ * (128 x 512), as fp32 before scale and rounding; layout 0 = the 32x32x16 A-operand order (the pack before the 16x16x32 feed-forward), 1 = the
+ * 16x16x32 order the bf16 kernels read.  Elements that carry no weight are left untouched.  dfx_debug_ff16_slot_ops: the 24 fragments of a full
+ * record's M slot in issue order, 5 ints each: {offset in 16-byte units from the lane's record pointer, GEMM (1 | 2), accumulator (0 = a,
+ * 1 = g, -1 = h), M-tile, K step (GEMM1) or output tile of h (GEMM2)}. */
+void dfx_debug_ff16_pack_w1(const float *W1, const float *g3, const float *b1, const float *be3, int fold, int layout, float *out);
+void dfx_debug_ff16_pack_w2(const float *W2, int layout, float *out);
+void dfx_debug_ff16_slot_ops(int32_t *out);
 /* Slot-boundary clock stamps of two wavefronts of workgroup 0 (device buffer of 2*capacity uint64; NULL = off).
  * Only effective in a library built with -DDFX_TRACE (tools/experiments/trace_slots.py builds one). */
 void dfx_debug_trace(void *device_buf, int capacity);
