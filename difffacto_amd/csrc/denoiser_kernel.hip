@@ -30,6 +30,7 @@ namespace {
 typedef float v16f __attribute__((ext_vector_type(16)));
 typedef float v8f __attribute__((ext_vector_type(8)));
 typedef float v4f __attribute__((ext_vector_type(4)));
+typedef float v2f __attribute__((ext_vector_type(2)));
 typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
 typedef _Float16 v8h __attribute__((ext_vector_type(8)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
@@ -137,16 +138,27 @@ __device__ __forceinline__ void ln_stats(const v16f (&h)[4], float &mean, float 
 // bf16 path: single pass over the registers (sum and sum of squares on four independent chains each), variance as
 // E[x^2] - mean^2 in fp32 — the normalised value is rounded to bf16 right after, so the cancellation error
 // (<= 2^-24 E[x^2] / var relative) is far below the operand rounding — and one FMA per element for the normalisation.
+//
+// Packed fp32 (v_pk_add_f32 / v_pk_fma_f32: two IEEE operations per instruction, at the issue cost of one): the fp32 work of the bf16 kernels
+// outside the feed-forward loop is written on register PAIRS — chains (0, 1) and (2, 3) here take registers (4k, 4k+1) and (4k+2, 4k+3) in
+// the order they always did, so every half is the operation it was and the bits are the same (tests/test_gpu_chain_bits.py).  The library is
+// built with -fno-slp-vectorize: only what is spelled on v2f is packed, and none of it sits in an M or V slot of the feed-forward.
+__device__ __forceinline__ v2f pair(const v16f &x, int i) { return v2f{x[2 * i], x[2 * i + 1]}; }
+__device__ __forceinline__ void set_pair(v16f &x, int i, const v2f &v) { x[2 * i] = v[0], x[2 * i + 1] = v[1]; }
+__device__ __forceinline__ v2f splat2(float v) { return v2f{v, v}; }
 __device__ __forceinline__ void ln_stats_fast(const v16f (&h)[4], float &mean, float &rstd) {
-  float s[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
+  v2f s01 = {0.f, 0.f}, s23 = s01, q01 = s01, q23 = s01;
 #pragma unroll
   for (int c = 0; c < 4; ++c)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      s[r & 3] += h[c][r];
-      q[r & 3] = fmaf(h[c][r], h[c][r], q[r & 3]);
+    for (int k = 0; k < 4; ++k) {
+      const v2f a = pair(h[c], 2 * k), b = pair(h[c], 2 * k + 1);
+      s01 += a;
+      s23 += b;
+      q01 = __builtin_elementwise_fma(a, a, q01);
+      q23 = __builtin_elementwise_fma(b, b, q23);
     }
-  float st = (s[0] + s[1]) + (s[2] + s[3]), qt = (q[0] + q[1]) + (q[2] + q[3]);
+  float st = (s01[0] + s01[1]) + (s23[0] + s23[1]), qt = (q01[0] + q01[1]) + (q23[0] + q23[1]);
   st += xhalf(st);
   qt += xhalf(qt);
   mean = st * (1.0f / 128.0f);
@@ -160,11 +172,12 @@ __device__ __forceinline__ void ln_to_act(const v16f (&h)[4], Act<PREC> (&xn)[4]
   if (PREC == DFX_PREC_BF16) {
     ln_stats_fast(h, mean, rstd);
     const float nmr = -mean * rstd;
+    const v2f rstd2 = splat2(rstd), nmr2 = splat2(nmr);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       v16f t;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) t[r] = fmaf(h[c][r], rstd, nmr);
+      for (int i = 0; i < 8; ++i) set_pair(t, i, __builtin_elementwise_fma(pair(h[c], i), rstd2, nmr2));
       xn[c].set(t);
     }
     return;
@@ -201,11 +214,18 @@ __device__ __forceinline__ float gelu_erf(float x) {  // F.gelu default (attenti
   return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
 }
 
+template <bool PK = false>   // PK: the bf16 kernels' form, two adds per instruction (ln_stats_fast)
 __device__ __forceinline__ void add_cvec(v16f (&h)[4], const float *__restrict__ v /* + hf*64 applied */) {
 #pragma unroll
   for (int c = 0; c < 4; ++c)
 #pragma unroll
     for (int r4 = 0; r4 < 4; ++r4) {
+      if (PK) {
+        const v4f t = *reinterpret_cast<const v4f *>(v + c * 16 + r4 * 4);
+        set_pair(h[c], 2 * r4, pair(h[c], 2 * r4) + v2f{t[0], t[1]});
+        set_pair(h[c], 2 * r4 + 1, pair(h[c], 2 * r4 + 1) + v2f{t[2], t[3]});
+        continue;
+      }
       const float4 t = *reinterpret_cast<const float4 *>(v + c * 16 + r4 * 4);
       h[c][r4 * 4 + 0] += t.x;
       h[c][r4 * 4 + 1] += t.y;
@@ -251,7 +271,6 @@ __device__ __forceinline__ void philox_normal3(unsigned long long seed, unsigned
 
 // proj_in (13 -> 128) + pre_norm.  x-columns on the VALU; the 10 per-part-constant inputs
 // (anchors | variances | onehot, attention.py:398-408) are pre-folded into cpart[seg].
-template <bool FAST = false>
 __device__ __forceinline__ void proj_in_prenorm(v16f (&h)[4], const float (&x)[3], const float *cpart,
                                                 const float4 *winx, const float2 *pregb) {
 #pragma unroll
@@ -267,14 +286,63 @@ __device__ __forceinline__ void proj_in_prenorm(v16f (&h)[4], const float (&x)[3
       }
     }
   float mean, rstd;
-  if (FAST) ln_stats_fast(h, mean, rstd);
-  else ln_stats(h, mean, rstd);
+  ln_stats(h, mean, rstd);
 #pragma unroll
   for (int c = 0; c < 4; ++c)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const float2 gb = pregb[c * 16 + r];
       h[c][r] = fmaf((h[c][r] - mean) * rstd, gb.x, gb.y);  // affine kept: h is the residual stream
+    }
+}
+
+// The bf16 chain kernels' step-boundary tables, as their prologues lay them out in LDS (pair_tables): per PAIR of channels (2i, 2i+1) — the
+// registers (2i, 2i+1) of a tile of h — the operands of one packed instruction side by side and no padding word:
+//     W_in x-columns  6 floats  wx(2i) wx(2i+1) | wy(2i) wy(2i+1) | wz(2i) wz(2i+1)
+//     pre_norm        4 floats  gamma(2i) gamma(2i+1) | beta(2i) beta(2i+1)
+//     W_out           6 floats  wx(2i) wy(2i) | wx(2i+1) wy(2i+1) | wz(2i) wz(2i+1)      (eps_x and eps_y are one packed chain, eps_z a scalar one)
+// Two pairs = three ds_read_b128 for W_in and for W_out (four before, one float4 per channel with a padding word).
+constexpr int PAIR_WIN = 6, PAIR_PREGB = 4, PAIR_WOUT = 6;
+// channel pair `i` (0..63) of the engine's tables -> the three pair tables; the caller's barrier publishes them
+__device__ __forceinline__ void pair_tables(const DenoiserDev &d, int i, float *winp, float *pregp, float *woutp) {
+  const float4 wa = d.win_x[2 * i], wb = d.win_x[2 * i + 1], oa = d.wout[2 * i], ob = d.wout[2 * i + 1];
+  const float2 ga = d.pre_gb[2 * i], gb = d.pre_gb[2 * i + 1];
+  float *w = winp + i * PAIR_WIN, *g = pregp + i * PAIR_PREGB, *o = woutp + i * PAIR_WOUT;
+  w[0] = wa.x, w[1] = wb.x, w[2] = wa.y, w[3] = wb.y, w[4] = wa.z, w[5] = wb.z;
+  g[0] = ga.x, g[1] = gb.x, g[2] = ga.y, g[3] = gb.y;
+  o[0] = oa.x, o[1] = oa.y, o[2] = ob.x, o[3] = ob.y, o[4] = oa.z, o[5] = ob.z;
+}
+// 12 floats = two pairs' W_in / W_out entries, as three 16-byte reads
+struct Pair2 {
+  v4f q[3];
+  __device__ __forceinline__ v2f at(int k) const { return v2f{q[k >> 1][2 * (k & 1)], q[k >> 1][2 * (k & 1) + 1]}; }   // k-th 64-bit operand, 0..5
+};
+__device__ __forceinline__ Pair2 load_pair2(const float *t) {
+  const v4f *q = reinterpret_cast<const v4f *>(t);
+  return Pair2{{q[0], q[1], q[2]}};
+}
+// proj_in of four channels = registers 4j .. 4j+3 of one tile: the three-FMA chain of every channel, two channels per instruction
+__device__ __forceinline__ void proj_in4_pk(v16f &ht, int j, const v2f (&x2)[3], const v4f &cp, const Pair2 &w) {
+  set_pair(ht, 2 * j, __builtin_elementwise_fma(w.at(2), x2[2], __builtin_elementwise_fma(w.at(1), x2[1], __builtin_elementwise_fma(w.at(0), x2[0], v2f{cp[0], cp[1]}))));
+  set_pair(ht, 2 * j + 1, __builtin_elementwise_fma(w.at(5), x2[2], __builtin_elementwise_fma(w.at(4), x2[1], __builtin_elementwise_fma(w.at(3), x2[0], v2f{cp[2], cp[3]}))));
+}
+// proj_in_prenorm of the bf16 chain kernels (single-pass statistics), on the pair tables of this half-wave (`winp`, `pregp`: + hf * 32 pairs)
+__device__ __forceinline__ void proj_in_prenorm_pk(v16f (&h)[4], const float (&x)[3], const float *cpart, const float *winp, const float *pregp) {
+  const v2f x2[3] = {splat2(x[0]), splat2(x[1]), splat2(x[2])};
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      proj_in4_pk(h[c], j, x2, *reinterpret_cast<const v4f *>(cpart + c * 16 + j * 4), load_pair2(winp + (c * 4 + j) * 2 * PAIR_WIN));
+  float mean, rstd;
+  ln_stats_fast(h, mean, rstd);
+  const v2f mean2 = splat2(mean), rstd2 = splat2(rstd);
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const v4f gb = *reinterpret_cast<const v4f *>(pregp + (c * 8 + i) * PAIR_PREGB);
+      set_pair(h[c], i, __builtin_elementwise_fma((pair(h[c], i) - mean2) * rstd2, v2f{gb[0], gb[1]}, v2f{gb[2], gb[3]}));  // affine kept: h is the residual stream
     }
 }
 
@@ -325,7 +393,7 @@ __device__ __forceinline__ void attention(v16f (&h)[4], const uint4 *rec, const 
   pa.set(sim);
 #pragma unroll
   for (int t = 0; t < 4; ++t) mma_tile<PREC>(h[t], rec + (4 + t) * TSTRIDE, pa);
-  add_cvec(h, ct);
+  add_cvec<PREC == DFX_PREC_BF16>(h, ct);
 }
 
 // GELU for the bf16 path: x * sigmoid(x (c1 + c3 x^2)) with (c1, c3) = (1.60031416, 0.06940179) fitted to the
@@ -514,8 +582,8 @@ __device__ __forceinline__ void ff_chunk(v16f (&h)[4], const Act<DFX_PREC_F32> (
 // (tools/ubench/agpr_overlap.hip, stage_mix.hip, lds_bw.hip):
 //   * a VALU instruction next to MFMAs costs ~3.1 cycles of SIMD issue (transcendentals ~10), every MFMA takes
 //     ~18 cycles of VALU issue away: T(SIMD) ~ max(32.6 nMFMA, 3.1 nVALU + 10 nTRANS + 18 nMFMA);
-//   * packed fp32 VALU (v_pk_mul/fma/add_f32) serialises against the matrix pipe: never next to MFMAs
-//     (the library is built with -fno-slp-vectorize, +10 %);
+//   * packed fp32 VALU (v_pk_mul/fma/add_f32) serialises against the matrix pipe: never in an M or V slot of the feed-forward
+//     (the library is built with -fno-slp-vectorize, +10 %); the V0 / V2 slots and the step boundary do use it (ln_stats_fast);
 //   * LDS delivers ~240 B/clk/CU with eight wavefronts reading; one wavefront sustains ~32 B/clk (latency bound).
 __device__ __forceinline__ v8bf as_bf(const uint4 &u) { return __builtin_bit_cast(v8bf, u); }
 
@@ -710,26 +778,52 @@ __device__ __forceinline__ void attn_softmax(v16f &sim, Act<DFX_PREC_BF16> &pa, 
 }
 
 // post_norm (affine folded into W_out) + proj_out (128 -> 3) on the VALU.
-template <bool FAST = false>
 __device__ __forceinline__ void post_eps(const v16f (&h)[4], const float4 *wout, const float (&bout)[4],
                                          float (&eps)[3]) {
   float mean, rstd;
-  if (FAST) ln_stats_fast(h, mean, rstd);
-  else ln_stats(h, mean, rstd);
-  const float nmr = -mean * rstd;
+  ln_stats(h, mean, rstd);
   float e0 = 0.f, e1 = 0.f, e2 = 0.f;
 #pragma unroll
   for (int c = 0; c < 4; ++c)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const float4 w = wout[c * 16 + r];
-      const float v = FAST ? fmaf(h[c][r], rstd, nmr) : (h[c][r] - mean) * rstd;
+      const float v = (h[c][r] - mean) * rstd;
       e0 = fmaf(w.x, v, e0);
       e1 = fmaf(w.y, v, e1);
       e2 = fmaf(w.z, v, e2);
     }
   eps[0] = e0 + xhalf(e0) + bout[0];
   eps[1] = e1 + xhalf(e1) + bout[1];
+  eps[2] = e2 + xhalf(e2) + bout[2];
+}
+// four channels (registers 4j .. 4j+3 of a tile, normalised two at a time) of the three eps chains: (e_x, e_y) packed, e_z scalar, channel after
+// channel as ever
+__device__ __forceinline__ void post_eps4_pk(const v16f &ht, int j, const v2f &rstd2, const v2f &nmr2, const Pair2 &w, v2f &e01, float &e2) {
+  const v2f va = __builtin_elementwise_fma(pair(ht, 2 * j), rstd2, nmr2), vb = __builtin_elementwise_fma(pair(ht, 2 * j + 1), rstd2, nmr2);
+  e01 = __builtin_elementwise_fma(w.at(0), splat2(va[0]), e01);
+  e2 = fmaf(w.at(2)[0], va[0], e2);
+  e01 = __builtin_elementwise_fma(w.at(1), splat2(va[1]), e01);
+  e2 = fmaf(w.at(2)[1], va[1], e2);
+  e01 = __builtin_elementwise_fma(w.at(3), splat2(vb[0]), e01);
+  e2 = fmaf(w.at(5)[0], vb[0], e2);
+  e01 = __builtin_elementwise_fma(w.at(4), splat2(vb[1]), e01);
+  e2 = fmaf(w.at(5)[1], vb[1], e2);
+}
+// post_eps of the bf16 chain kernels, on the W_out pair table of this half-wave (`woutp`: + hf * 32 pairs)
+__device__ __forceinline__ void post_eps_pk(const v16f (&h)[4], const float *woutp, const float (&bout)[4], float (&eps)[3]) {
+  float mean, rstd;
+  ln_stats_fast(h, mean, rstd);
+  const float nmr = -mean * rstd;
+  const v2f rstd2 = splat2(rstd), nmr2 = splat2(nmr);
+  v2f e01 = {0.f, 0.f};
+  float e2 = 0.f;
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) post_eps4_pk(h[c], j, rstd2, nmr2, load_pair2(woutp + (c * 4 + j) * 2 * PAIR_WOUT), e01, e2);
+  eps[0] = e01[0] + xhalf(e01[0]) + bout[0];
+  eps[1] = e01[1] + xhalf(e01[1]) + bout[1];
   eps[2] = e2 + xhalf(e2) + bout[2];
 }
 
@@ -935,7 +1029,7 @@ __global__ void __launch_bounds__(NW * 64) k_denoise(const KParams p) {
         ff_chunk(h, xn, bp.chunks + (size_t)u * CHUNK_TILES * TSTRIDE + lane,
                  bp.chunks + (size_t)(u + FF_SKEW) * CHUNK_TILES * TSTRIDE + lane, bp.bconst + u * 64 + (FF16 ? (lane >> 4) * 8 : hf * 16), fold);
       if (FF16) ff16_rows(h);
-      add_cvec(h, bp.bconst + BCONST_B2_OFF + hf * 64);
+      add_cvec<FF16>(h, bp.bconst + BCONST_B2_OFF + hf * 64);
     }
     float eps[3];
     post_eps(h, p.d.wout + hf * 64, p.d.bout, eps);
@@ -980,9 +1074,9 @@ constexpr int RECORDS_PER_BLOCK = 1 + FF_STAGES;
 // LDS map (bytes)
 constexpr int L_RING = 0;
 constexpr int L_BCONST = L_RING + NSLOT * SLOT_BYTES;  // 2 x block-constant record (b1', b2)
-constexpr int L_WINX = L_BCONST + 2 * BCONST_BYTES;    // float4[128]
-constexpr int L_PREGB = L_WINX + 2048;                 // float2[128]
-constexpr int L_WOUT = L_PREGB + 1024;                 // float4[128]
+constexpr int L_WINX = L_BCONST + 2 * BCONST_BYTES;    // float4[128]; bf16 kernel: pair table (pair_tables), 1.5 KiB of it
+constexpr int L_PREGB = L_WINX + 2048;                 // float2[128]; bf16 kernel: pair table
+constexpr int L_WOUT = L_PREGB + 1024;                 // float4[128]; bf16 kernel: pair table, 1.5 KiB of it
 constexpr int L_CPART = L_WOUT + 2048;                 // float[4][128]
 constexpr int L_DUMMY = L_CPART + 2048;                // sink for padding DMAs (one wave's pieces)
 constexpr int PSTATE_FIELDS = 13;                      // x[3] anc[3] var[3] L[3] seg
@@ -1256,17 +1350,11 @@ __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe(const KParams p) {
   issue_record<NW>(p, dma, wave, voff, lds0, s);
 
   // ---- chain-invariant small operands -> LDS (plain loads; not part of the ring) ----
-  {
-    float4 *winx = reinterpret_cast<float4 *>(pipe_smem + L_WINX);
-    float2 *pregb = reinterpret_cast<float2 *>(pipe_smem + L_PREGB);
-    float4 *wout = reinterpret_cast<float4 *>(pipe_smem + L_WOUT);
+  {   // (W_in, pre_norm, W_out: the pair tables of proj_in_prenorm_pk / post_eps_pk, inside the regions of the one-float4-per-channel form)
     float *cp = reinterpret_cast<float *>(pipe_smem + L_CPART);
     const int tid = threadIdx.x;
-    if (tid < 128) {
-      winx[tid] = p.d.win_x[tid];
-      pregb[tid] = p.d.pre_gb[tid];
-      wout[tid] = p.d.wout[tid];
-    }
+    if (tid < 64)
+      pair_tables(p.d, tid, reinterpret_cast<float *>(pipe_smem + L_WINX), reinterpret_cast<float *>(pipe_smem + L_PREGB), reinterpret_cast<float *>(pipe_smem + L_WOUT));
     for (int i = tid; i < NCLS * INNER; i += NW * 64) cp[i] = p.cpart[(size_t)s * NCLS * INNER + i];
   }
   unsigned vmask;
@@ -1280,9 +1368,9 @@ __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe(const KParams p) {
   }
   __syncthreads();
 
-  const float4 *winx = reinterpret_cast<const float4 *>(pipe_smem + L_WINX) + hf * 64;
-  const float2 *pregb = reinterpret_cast<const float2 *>(pipe_smem + L_PREGB) + hf * 64;
-  const float4 *wout = reinterpret_cast<const float4 *>(pipe_smem + L_WOUT) + hf * 64;
+  const float *winx = reinterpret_cast<const float *>(pipe_smem + L_WINX) + hf * 32 * PAIR_WIN;
+  const float *pregb = reinterpret_cast<const float *>(pipe_smem + L_PREGB) + hf * 32 * PAIR_PREGB;
+  const float *wout = reinterpret_cast<const float *>(pipe_smem + L_WOUT) + hf * 32 * PAIR_WOUT;
 
   Issuer<NW> issue_in_m{p, dma, wave, voff, lds0, s, {}};
   // slot boundary; `mgmt` = this barrier is a record's management barrier for this wave's group
@@ -1330,8 +1418,8 @@ __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe(const KParams p) {
       issue_in_m.m_begin();
       if (seq > 0) {  // the previous block's h back to one point per lane (32 swaps), + its b2 (other block-constant buffer)
         ff16_rows(h);
-        add_cvec(h, reinterpret_cast<const float *>(pipe_smem + L_BCONST + ((seq - 1) & 1) * BCONST_BYTES) +
-                        BCONST_B2_OFF + hf * 64);
+        add_cvec<true>(h, reinterpret_cast<const float *>(pipe_smem + L_BCONST + ((seq - 1) & 1) * BCONST_BYTES) +
+                              BCONST_B2_OFF + hf * 64);
       }
       if (b == 0) {
         PointState ps;
@@ -1339,14 +1427,14 @@ __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe(const KParams p) {
         pstate_load(ps_lds, pt, PTS, ps, step > 0);
         if (step > 0) {
           float eps[3];
-          post_eps<true>(h, wout, p.d.bout, eps);
+          post_eps_pk(h, wout, p.d.bout, eps);
           done = step_epilogue<FROM>(p, ps, eps, step - 1, step_t(p, step - 1, s));
           if (!done) pstate_store(ps_lds, pt, PTS, ps, false);   // both half-waves hold the same point and write the same x
         }
         if (step == p.nsteps) done = true;
         if (!done) {
           const float *cpart = reinterpret_cast<const float *>(pipe_smem + L_CPART) + ps.sg * INNER + hf * 64;
-          proj_in_prenorm<true>(h, ps.x, cpart, winx, pregb);
+          proj_in_prenorm_pk(h, ps.x, cpart, winx, pregb);
         }
       }
       if (done) break;
@@ -1367,7 +1455,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe(const KParams p) {
       // ---- V2: + c_t, LN3 ----
       DFX_SLOT(!grpA);
       issue_in_m.m_begin();
-      add_cvec(h, reinterpret_cast<const float *>(rec - lane + 1088) + hf * 64);
+      add_cvec<true>(h, reinterpret_cast<const float *>(rec - lane + 1088) + hf * 64);
       ln_to_act<PREC>(h, xn);
       // ---- feed-forward: M(F0) V M(F1) V ... M(F16) ----
       v16f a, g;
@@ -1665,85 +1753,85 @@ __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe_f32(const KParams p
 }
 
 // The step boundary runs on one wavefront with nobody to hide its LDS latency behind: the same arithmetic as post_eps /
-// proj_in_prenorm (operation for operation — the results are bit-identical), with the operand reads of a whole 16-channel tile
-// issued ahead of the tile before's arithmetic (hipcc, short of registers over the whole kernel, otherwise reads one operand at a time).
+// proj_in_prenorm_pk (operation for operation — the results are bit-identical), with the operand reads of half a 16-channel tile
+// issued ahead of the half before's arithmetic (hipcc, short of registers over the whole kernel, otherwise reads one operand at a time).
 // (fences: an empty asm that consumes the batch's results and clobbers memory — reads cannot cross it, the arithmetic is tied to it by its
 // data; a sched_barrier alone orders only what instruction selection has already laid out, and that is every read first.)
-#define DFX_TIE8(a) asm volatile("" : "+v"((a)[0]), "+v"((a)[1]), "+v"((a)[2]), "+v"((a)[3]), "+v"((a)[4]), "+v"((a)[5]), "+v"((a)[6]), "+v"((a)[7]) :: "memory")
-__device__ __forceinline__ void post_eps_tiles(const v16f (&h)[4], const float4 *wout, const float (&bout)[4], float (&eps)[3]) {
+#define DFX_TIE4(a) asm volatile("" : "+v"((a)[0]), "+v"((a)[1]), "+v"((a)[2]), "+v"((a)[3]) :: "memory")   // (four register pairs)
+__device__ __forceinline__ void post_eps_tiles(const v16f (&h)[4], const float *woutp, const float (&bout)[4], float (&eps)[3]) {
   float mean, rstd;
   ln_stats_fast(h, mean, rstd);
   const float nmr = -mean * rstd;
-  float e0 = 0.f, e1 = 0.f, e2 = 0.f;
-  float4 w[2][8];   // half a tile per batch
+  const v2f rstd2 = splat2(rstd), nmr2 = splat2(nmr);
+  v2f e01 = {0.f, 0.f};
+  float e2 = 0.f;
+  Pair2 w[2][2];   // half a tile per batch
 #pragma unroll
-  for (int r = 0; r < 8; ++r) w[0][r] = wout[r];
-  asm volatile("" : "+v"(e0), "+v"(e1), "+v"(e2) :: "memory");
+  for (int j = 0; j < 2; ++j) w[0][j] = load_pair2(woutp + j * 2 * PAIR_WOUT);
+  asm volatile("" : "+v"(e01), "+v"(e2) :: "memory");
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     if (k < 7) {
 #pragma unroll
-      for (int r = 0; r < 8; ++r) w[(k + 1) & 1][r] = wout[(k + 1) * 8 + r];
+      for (int j = 0; j < 2; ++j) w[(k + 1) & 1][j] = load_pair2(woutp + ((k + 1) * 2 + j) * 2 * PAIR_WOUT);
     }
 #pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      const float v = fmaf(h[k >> 1][(k & 1) * 8 + r], rstd, nmr);
-      e0 = fmaf(w[k & 1][r].x, v, e0);
-      e1 = fmaf(w[k & 1][r].y, v, e1);
-      e2 = fmaf(w[k & 1][r].z, v, e2);
-    }
-    asm volatile("" : "+v"(e0), "+v"(e1), "+v"(e2) :: "memory");
+    for (int j = 0; j < 2; ++j) post_eps4_pk(h[k >> 1], (k & 1) * 2 + j, rstd2, nmr2, w[k & 1][j], e01, e2);
+    asm volatile("" : "+v"(e01), "+v"(e2) :: "memory");
   }
-  eps[0] = e0 + xhalf(e0) + bout[0];
-  eps[1] = e1 + xhalf(e1) + bout[1];
+  eps[0] = e01[0] + xhalf(e01[0]) + bout[0];
+  eps[1] = e01[1] + xhalf(e01[1]) + bout[1];
   eps[2] = e2 + xhalf(e2) + bout[2];
 }
 
-__device__ __forceinline__ void proj_in_prenorm_tiles(v16f (&h)[4], const float (&x)[3], const float *cpart, const float4 *winx, const float2 *pregb) {
-  float4 w[2][8], cp[2][2];
+__device__ __forceinline__ void proj_in_prenorm_tiles(v16f (&h)[4], const float (&x)[3], const float *cpart, const float *winp, const float *pregp) {
+  const v2f x2[3] = {splat2(x[0]), splat2(x[1]), splat2(x[2])};
+  Pair2 w[2][2];
+  v4f cp[2][2];
   auto fetch = [&](int k) {
 #pragma unroll
-    for (int r4 = 0; r4 < 2; ++r4) cp[k & 1][r4] = *reinterpret_cast<const float4 *>(cpart + k * 8 + r4 * 4);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) w[k & 1][r] = winx[k * 8 + r];
+    for (int j = 0; j < 2; ++j) {
+      cp[k & 1][j] = *reinterpret_cast<const v4f *>(cpart + k * 8 + j * 4);
+      w[k & 1][j] = load_pair2(winp + (k * 2 + j) * 2 * PAIR_WIN);
+    }
   };
   fetch(0);
   asm volatile("" ::: "memory");
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     if (k < 7) fetch(k + 1);
-    float o[8];
+    v16f &ht = h[k >> 1];
 #pragma unroll
-    for (int r4 = 0; r4 < 2; ++r4) {
-      const float cpv[4] = {cp[k & 1][r4].x, cp[k & 1][r4].y, cp[k & 1][r4].z, cp[k & 1][r4].w};
+    for (int j = 0; j < 2; ++j) proj_in4_pk(ht, (k & 1) * 2 + j, x2, cp[k & 1][j], w[k & 1][j]);
+    v2f o[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float4 ww = w[k & 1][r4 * 4 + e];
-        o[r4 * 4 + e] = fmaf(ww.z, x[2], fmaf(ww.y, x[1], fmaf(ww.x, x[0], cpv[e])));
-      }
-    }
-    DFX_TIE8(o);
+    for (int i = 0; i < 4; ++i) o[i] = pair(ht, (k & 1) * 4 + i);
+    DFX_TIE4(o);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) h[k >> 1][(k & 1) * 8 + e] = o[e];
+    for (int i = 0; i < 4; ++i) set_pair(ht, (k & 1) * 4 + i, o[i]);
   }
-  float2 gb[2][8];
+  v4f gb[2][4];
 #pragma unroll
-  for (int r = 0; r < 8; ++r) gb[0][r] = pregb[r];
+  for (int i = 0; i < 4; ++i) gb[0][i] = *reinterpret_cast<const v4f *>(pregp + i * PAIR_PREGB);
   float mean, rstd;
   ln_stats_fast(h, mean, rstd);
   asm volatile("" : "+v"(mean), "+v"(rstd) :: "memory");
+  const v2f mean2 = splat2(mean), rstd2 = splat2(rstd);
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     if (k < 7) {
 #pragma unroll
-      for (int r = 0; r < 8; ++r) gb[(k + 1) & 1][r] = pregb[(k + 1) * 8 + r];
+      for (int i = 0; i < 4; ++i) gb[(k + 1) & 1][i] = *reinterpret_cast<const v4f *>(pregp + ((k + 1) * 4 + i) * PAIR_PREGB);
     }
-    float o[8];
+    v2f o[4];
 #pragma unroll
-    for (int r = 0; r < 8; ++r) o[r] = fmaf((h[k >> 1][(k & 1) * 8 + r] - mean) * rstd, gb[k & 1][r].x, gb[k & 1][r].y);
-    DFX_TIE8(o);
+    for (int i = 0; i < 4; ++i) {
+      const v4f g = gb[k & 1][i];
+      o[i] = __builtin_elementwise_fma((pair(h[k >> 1], (k & 1) * 4 + i) - mean2) * rstd2, v2f{g[0], g[1]}, v2f{g[2], g[3]});
+    }
+    DFX_TIE4(o);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) h[k >> 1][(k & 1) * 8 + e] = o[e];
+    for (int i = 0; i < 4; ++i) set_pair(h[k >> 1], (k & 1) * 4 + i, o[i]);
   }
 }
 
@@ -1752,16 +1840,13 @@ __device__ __forceinline__ void proj_in_prenorm_tiles(v16f (&h)[4], const float 
 constexpr int COOP_NW = 8, COOP_TILES = 4;
 static_assert(FF_CHUNKS == 2 * COOP_NW, "two rounds of one chunk per wavefront");
 constexpr int COOP_TSTRIDE = tile_units(DFX_PREC_BF16) * 64, COOP_AREC = asms_bytes(DFX_PREC_BF16) / 16;
-// chain-invariant operands in LDS (7 KiB): W_in x-columns (2 KiB) | pre_norm (1 KiB) | W_out (2 KiB) | cpart of the workgroup's shape (2 KiB)
+// chain-invariant operands in LDS (7 KiB): pair tables of W_in x-columns (1.5 of 2 KiB) | pre_norm (1 KiB) | W_out (1.5 of 2 KiB); cpart of the workgroup's shape (2 KiB)
 constexpr int CC_WINX = 0, CC_PREGB = 2048, CC_WOUT = 3072, CC_CPART = 5120, CC_BYTES = 7 * 1024;
 
 __device__ __forceinline__ void coop_stage_consts(unsigned char *cc, const KParams &p, int s) {   // (the caller's barrier publishes them)
-  float4 *c_winx = reinterpret_cast<float4 *>(cc + CC_WINX);
-  float2 *c_pregb = reinterpret_cast<float2 *>(cc + CC_PREGB);
-  float4 *c_wout = reinterpret_cast<float4 *>(cc + CC_WOUT);
   float *c_cp = reinterpret_cast<float *>(cc + CC_CPART);
   const int tid = threadIdx.x;
-  if (tid < 128) c_winx[tid] = p.d.win_x[tid], c_pregb[tid] = p.d.pre_gb[tid], c_wout[tid] = p.d.wout[tid];
+  if (tid < 64) pair_tables(p.d, tid, reinterpret_cast<float *>(cc + CC_WINX), reinterpret_cast<float *>(cc + CC_PREGB), reinterpret_cast<float *>(cc + CC_WOUT));
   c_cp[tid] = p.cpart[(size_t)s * NCLS * INNER + tid];
 }
 
@@ -1814,7 +1899,8 @@ __device__ __forceinline__ void hs_store_plus(v4f *hc, const v16f &h, const floa
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const v4f bb = *reinterpret_cast<const v4f *>(b + 4 * q);
-    hc[q * 64] = v4f{h[4 * q] + bb[0], h[4 * q + 1] + bb[1], h[4 * q + 2] + bb[2], h[4 * q + 3] + bb[3]};
+    const v2f lo = pair(h, 2 * q) + v2f{bb[0], bb[1]}, hi = pair(h, 2 * q + 1) + v2f{bb[2], bb[3]};   // (packed, as add_cvec<true>)
+    hc[q * 64] = v4f{lo[0], lo[1], hi[0], hi[1]};
   }
 }
 __device__ __forceinline__ void hs_load4(v16f (&h)[4], const v4f *home) {
@@ -1896,7 +1982,7 @@ __device__ __forceinline__ void coop_gelu_store(const v16f &a, const v16f &g, ui
 __device__ __forceinline__ void coop_eps(float (&eps)[3], const v4f *home, const unsigned char *cc, const KParams &p, int lane) {
   v16f h[4];
   hs_load4(h, home);
-  post_eps_tiles(h, reinterpret_cast<const float4 *>(cc + CC_WOUT) + (lane >> 5) * 64, p.d.bout, eps);
+  post_eps_tiles(h, reinterpret_cast<const float *>(cc + CC_WOUT) + (lane >> 5) * 32 * PAIR_WOUT, p.d.bout, eps);
 }
 // ... the posterior update of the chain state parked at ps_lds, with the noise coop_draw_noise left in s_z (true: the kernel is done) ...
 template <bool FROM>
@@ -1912,8 +1998,8 @@ __device__ __forceinline__ bool coop_posterior(const KParams &p, PointState &ps,
 __device__ __forceinline__ void coop_enter_step(const PointState &ps, v4f *home, const unsigned char *cc, int lane) {
   const int hf = lane >> 5;
   v16f h[4];
-  proj_in_prenorm_tiles(h, ps.x, reinterpret_cast<const float *>(cc + CC_CPART) + ps.sg * INNER + hf * 64, reinterpret_cast<const float4 *>(cc + CC_WINX) + hf * 64,
-                        reinterpret_cast<const float2 *>(cc + CC_PREGB) + hf * 64);
+  proj_in_prenorm_tiles(h, ps.x, reinterpret_cast<const float *>(cc + CC_CPART) + ps.sg * INNER + hf * 64, reinterpret_cast<const float *>(cc + CC_WINX) + hf * 32 * PAIR_WIN,
+                        reinterpret_cast<const float *>(cc + CC_PREGB) + hf * 32 * PAIR_PREGB);
   hs_store4(home, h);
 }
 

@@ -2,9 +2,15 @@
 // v_mfma_f32_32x32x16 that share their A fragment (two point tiles), the fragment refilled in place from LDS behind the pair.
 // Variants: C/D in the accumulator file or in VGPRs, B from the accumulator file or VGPRs, with / without the refill, NV packed
 // fp16 VALU fillers per MFMA.  Prints shader cycles per MFMA (floor: 32).
+// F32 rows: on top of the stream "refill per MFMA, 5 v_pk per MFMA", the same fp32 arithmetic (four fused multiply-adds on random operands
+// per MFMA) issued as 4 v_fma_f32 or as 2 v_pk_fma_f32 — what a packed fp32 instruction costs the full chip against the two scalar ones
+// it replaces.  M16 rows: every v_mfma_f32_32x32x16 replaced by the two v_mfma_f32_16x16x32 (one per 16-point N-tile, same A fragment)
+// of the chain kernels' feed-forward; "per MFMA" then means per such pair.
+// Usage: pair_issue [iters = 2000]
 // Build: hipcc --offload-arch=gfx950 -O3 pair_issue.hip -o _build/pair_issue
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include <cstdlib>
 typedef float v16f __attribute__((ext_vector_type(16)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 
@@ -13,7 +19,9 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 
 // ACC: 0 = C/D in VGPRs, 1 = accumulator file.  BA: B operand from the accumulator file.  LDS: refill behind every pair.
 // NV: 0, 3 or 5 fillers behind every MFMA.  PAIR: 1 = the two MFMAs of a pair share A; 0 = every MFMA its own A (+ its own refill)
-template <int ACC, int BA, int LDS, int NV, int PAIR>
+// F32: 0 = none, 1 = 4 v_fma_f32, 2 = 2 v_pk_fma_f32 behind every MFMA.  M16: 1 = pairs of 16x16x32 (C/D in the accumulator file)
+typedef float v2f __attribute__((ext_vector_type(2)));
+template <int ACC, int BA, int LDS, int NV, int PAIR, int F32 = 0, int M16 = 0>
 __global__ void __launch_bounds__(256, 1) k(unsigned long long *out, int iters) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
   for (int i = threadIdx.x; i < 32 * 1024 / 4; i += blockDim.x) {
@@ -27,6 +35,21 @@ __global__ void __launch_bounds__(256, 1) k(unsigned long long *out, int iters) 
   const v4f *fs = reinterpret_cast<const v4f *>(smem) + lane;
   v4f f0 = fs[64], f1 = fs[128], f2 = fs[192], f3 = fs[256], f4 = fs[320], f5 = fs[384], f6 = fs[448], f7 = fs[512], b0 = fs[0], b1 = fs[576];
   unsigned g0 = 0x3c003c00u ^ (threadIdx.x * 0x01230123u & 0x03ff03ffu), g1 = 0x38003800u ^ (threadIdx.x * 0x04560457u & 0x03ff03ffu), t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0;
+  // fp32 fillers: x <- x * u + w with |u| < 1, two (u, w) sets alternating between the two filler sites of a pair, so that x keeps moving
+  const unsigned hs = (threadIdx.x + 1) * 2654435761u;
+  auto rnd = [&](int i, float lo, float span) { return lo + span * (float)((hs >> (i * 3)) & 1023u) * (1.0f / 1024.0f); };
+  const v2f ua = {rnd(0, 0.5f, 0.45f), rnd(1, -0.95f, 0.45f)}, wa = {rnd(2, -1.f, 2.f), rnd(3, -1.f, 2.f)};
+  const v2f ub = {rnd(4, -0.95f, 0.45f), rnd(5, 0.5f, 0.45f)}, wb = {rnd(6, -1.f, 2.f), rnd(7, -1.f, 2.f)};
+  v2f x0 = {rnd(1, -1.f, 2.f), rnd(4, -1.f, 2.f)}, x1 = {rnd(3, -1.f, 2.f), rnd(6, -1.f, 2.f)};
+  float y0 = x0[0], y1 = x0[1], y2 = x1[0], y3 = x1[1];
+  v4f d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0, d2 = d0, d3 = d0, d4 = d0, d5 = d0, d6 = d0, d7 = d0;
+#define FILL32(u, w)                                                                                                                        \
+  do {                                                                                                                                      \
+    if (F32 == 1)                                                                                                                           \
+      asm volatile("v_fma_f32 %0, %0, %4, %6\n v_fma_f32 %1, %1, %5, %7\n v_fma_f32 %2, %2, %4, %6\n v_fma_f32 %3, %3, %5, %7\n"             \
+                   : "+v"(y0), "+v"(y1), "+v"(y2), "+v"(y3) : "v"(u[0]), "v"(u[1]), "v"(w[0]), "v"(w[1]));                                  \
+    if (F32 == 2) asm volatile("v_pk_fma_f32 %0, %0, %2, %3\n v_pk_fma_f32 %1, %1, %2, %3\n" : "+v"(x0), "+v"(x1) : "v"(u), "v"(w));        \
+  } while (0)
   const unsigned long long tA = __builtin_readcyclecounter();
 #define OPSV : [c0] "+v"(c0), [c1] "+v"(c1), [c2] "+v"(c2), [c3] "+v"(c3), [f0] "+v"(f0), [f1] "+v"(f1), [f2] "+v"(f2), [f3] "+v"(f3), [f4] "+v"(f4), [f5] "+v"(f5), \
                [f6] "+v"(f6), [f7] "+v"(f7), [t0] "+v"(t0), [t1] "+v"(t1), [t2] "+v"(t2), [t3] "+v"(t3), [t4] "+v"(t4) : [la] "v"(la), [b0] "v"(b0), [b1] "v"(b1), [g0] "v"(g0), [g1] "v"(g1)
@@ -37,13 +60,30 @@ __global__ void __launch_bounds__(256, 1) k(unsigned long long *out, int iters) 
 #define EMIT(str) do { if (ACC) asm volatile(str OPSA); else if (BA) asm volatile(str OPSVB); else asm volatile(str OPSV); } while (0)
 #define GRP(ca, cb, fr, fr2, off)                                                                     \
     EMIT("s_waitcnt lgkmcnt(7)\n v_mfma_f32_32x32x16_bf16 %[" ca "], %[" fr "], %[b0], %[" ca "]\n");  \
-    if (NV == 5) EMIT(FILL); if (NV == 3) EMIT(FILL3);                                                \
+    if (NV == 5) EMIT(FILL); if (NV == 3) EMIT(FILL3); FILL32(ua, wa);                                \
     EMIT("v_mfma_f32_32x32x16_bf16 %[" cb "], %[" fr2 "], %[b1], %[" cb "]\n");                        \
     if (LDS) EMIT("ds_read_b128 %[" fr "], %[la] offset:" #off "\n");                                 \
     if (LDS && !PAIR) EMIT("ds_read_b128 %[" fr2 "], %[la] offset:" #off "+16384\n");                  \
-    if (NV == 5) EMIT(FILL); if (NV == 3) EMIT(FILL3);
+    if (NV == 5) EMIT(FILL); if (NV == 3) EMIT(FILL3); FILL32(ub, wb);
+  // the same group on v_mfma_f32_16x16x32_bf16: accumulators d0..d7 (accumulator file), two MFMAs per fragment (b0 / b1 = the two N-tiles)
+#define OPS16 : [d0] "+a"(d0), [d1] "+a"(d1), [d2] "+a"(d2), [d3] "+a"(d3), [d4] "+a"(d4), [d5] "+a"(d5), [d6] "+a"(d6), [d7] "+a"(d7), [f0] "+v"(f0), [f1] "+v"(f1), \
+                [f2] "+v"(f2), [f3] "+v"(f3), [f4] "+v"(f4), [f5] "+v"(f5), [f6] "+v"(f6), [f7] "+v"(f7), [t0] "+v"(t0), [t1] "+v"(t1), [t2] "+v"(t2), [t3] "+v"(t3), \
+                [t4] "+v"(t4) : [la] "v"(la), [b0] "v"(b0), [b1] "v"(b1), [g0] "v"(g0), [g1] "v"(g1)
+#define EMIT16(str) asm volatile(str OPS16)
+#define GRP16(da, db, dc, dd, fr, fr2, off)                                                                                             \
+    EMIT16("s_waitcnt lgkmcnt(7)\n v_mfma_f32_16x16x32_bf16 %[" da "], %[" fr "], %[b0], %[" da "]\n"                                    \
+           " v_mfma_f32_16x16x32_bf16 %[" db "], %[" fr "], %[b1], %[" db "]\n");                                                        \
+    if (NV == 5) EMIT16(FILL); FILL32(ua, wa);                                                                                          \
+    EMIT16("v_mfma_f32_16x16x32_bf16 %[" dc "], %[" fr2 "], %[b0], %[" dc "]\n v_mfma_f32_16x16x32_bf16 %[" dd "], %[" fr2 "], %[b1], %[" dd "]\n"); \
+    if (LDS) EMIT16("ds_read_b128 %[" fr "], %[la] offset:" #off "\n");                                                                  \
+    if (LDS && !PAIR) EMIT16("ds_read_b128 %[" fr2 "], %[la] offset:" #off "+16384\n");                                                  \
+    if (NV == 5) EMIT16(FILL); FILL32(ub, wb);
   for (int it = 0; it < iters; ++it) {
-    if (PAIR) {
+    if (M16) {
+      GRP16("d0", "d1", "d2", "d3", "f0", "f1", 1024) GRP16("d4", "d5", "d6", "d7", "f2", "f3", 2048) GRP16("d0", "d1", "d2", "d3", "f4", "f5", 3072)
+      GRP16("d4", "d5", "d6", "d7", "f6", "f7", 4096) GRP16("d0", "d1", "d2", "d3", "f0", "f1", 5120) GRP16("d4", "d5", "d6", "d7", "f2", "f3", 6144)
+      GRP16("d0", "d1", "d2", "d3", "f4", "f5", 7168) GRP16("d4", "d5", "d6", "d7", "f6", "f7", 8192)
+    } else if (PAIR) {
       GRP("c0", "c1", "f0", "f0", 1024) GRP("c2", "c3", "f1", "f1", 2048) GRP("c0", "c1", "f2", "f2", 3072) GRP("c2", "c3", "f3", "f3", 4096)
       GRP("c0", "c1", "f4", "f4", 5120) GRP("c2", "c3", "f5", "f5", 6144) GRP("c0", "c1", "f6", "f6", 7168) GRP("c2", "c3", "f7", "f7", 8192)
     } else {
@@ -55,21 +95,24 @@ __global__ void __launch_bounds__(256, 1) k(unsigned long long *out, int iters) 
   const unsigned long long tB = __builtin_readcyclecounter();
   float s = 0;
   for (int i = 0; i < 16; ++i) s += c0[i] + c1[i] + c2[i] + c3[i];
+  s += y0 + y1 + y2 + y3 + x0[0] + x0[1] + x1[0] + x1[1];
+  for (int i = 0; i < 4; ++i) s += d0[i] + d1[i] + d2[i] + d3[i] + d4[i] + d5[i] + d6[i] + d7[i];
   s += f0[0] + f1[0] + f2[0] + f3[0] + f4[0] + f5[0] + f6[0] + f7[0] + __uint_as_float(t0 ^ t1 ^ t2 ^ t3 ^ t4);
   if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = tB - tA;
   if (s == 12345.678f) out[1] = 1;
 }
 
-template <int ACC, int BA, int LDS, int NV, int PAIR>
+int g_iters = 2000;
+template <int ACC, int BA, int LDS, int NV, int PAIR, int F32 = 0, int M16 = 0>
 void run(const char *name, int blocks) {
   unsigned long long *d;
   hipMalloc(&d, 16);
-  const int iters = 2000;
-  hipFuncSetAttribute(reinterpret_cast<const void *>(k<ACC, BA, LDS, NV, PAIR>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-  k<ACC, BA, LDS, NV, PAIR><<<blocks, 256, 64 * 1024>>>(d, 10);
+  const int iters = g_iters;
+  hipFuncSetAttribute(reinterpret_cast<const void *>(k<ACC, BA, LDS, NV, PAIR, F32, M16>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+  k<ACC, BA, LDS, NV, PAIR, F32, M16><<<blocks, 256, 64 * 1024>>>(d, 10);
   hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
   hipEventRecord(a);
-  k<ACC, BA, LDS, NV, PAIR><<<blocks, 256, 64 * 1024>>>(d, iters);
+  k<ACC, BA, LDS, NV, PAIR, F32, M16><<<blocks, 256, 64 * 1024>>>(d, iters);
   hipEventRecord(b);
   hipDeviceSynchronize();
   float ms; hipEventElapsedTime(&ms, a, b);
@@ -80,7 +123,8 @@ void run(const char *name, int blocks) {
   hipFree(d);
 }
 
-int main() {
+int main(int argc, char **argv) {
+  if (argc > 1) g_iters = atoi(argv[1]);
   for (int blocks : {1, 256}) {
     run<0, 0, 0, 0, 1>("C/D VGPR, B VGPR, no refill, no filler", blocks);
     run<1, 0, 0, 0, 1>("C/D AGPR, B VGPR, no refill, no filler", blocks);
@@ -92,6 +136,13 @@ int main() {
     run<1, 0, 1, 5, 1>("C/D AGPR, refill per pair, 5 v_pk per MFMA", blocks);
     run<0, 1, 1, 5, 1>("C/D VGPR, B AGPR, refill per pair, 5 v_pk per MFMA", blocks);
     run<1, 0, 1, 5, 0>("C/D AGPR, refill per MFMA, 5 v_pk per MFMA", blocks);
+    run<1, 0, 1, 5, 0, 1>("... + 4 v_fma_f32 per MFMA", blocks);
+    run<1, 0, 1, 5, 0, 2>("... + 2 v_pk_fma_f32 per MFMA", blocks);
+    run<1, 0, 0, 0, 0, 0, 1>("16x16x32 pairs, no refill, no filler", blocks);
+    run<1, 0, 1, 0, 0, 0, 1>("16x16x32 pairs, refill per pair (own A)", blocks);
+    run<1, 0, 1, 5, 0, 0, 1>("16x16x32 pairs, refill per pair, 5 v_pk per pair", blocks);
+    run<1, 0, 1, 5, 0, 1, 1>("... + 4 v_fma_f32 per pair", blocks);
+    run<1, 0, 1, 5, 0, 2, 1>("... + 2 v_pk_fma_f32 per pair", blocks);
   }
   return 0;
 }
