@@ -1,9 +1,9 @@
 // Fused GEGLU feed-forward of a transformer block for the TRAINING path (train_kernels.hip, bf16 matrix products, dropout on or off), with the
-// block's LayerNorms and — optionally, FfArgs::at_frags — its attention sub-block in the same kernels:
+// block's LayerNorms and its attention sub-block (FfArgs::at_frags) in the same kernels (ff_fwd in k_ff_fwd_chain, ff_bwd in k_ff_bwd):
 //
-//   forward    [h1 = hin + M_s softmax(A_s LN2(hin)) + b_o]   h2 = h1 + W2 (a * gelu(g)) + b2,   [a | g] = W1' xhat3(h1) + b1'   (LayerNorm3's affine
+//   forward    h1 = hin + M_s softmax(A_s LN2(hin)) + b_o,    h2 = h1 + W2 (a * gelu(g)) + b2,   [a | g] = W1' xhat3(h1) + b1'   (LayerNorm3's affine
 //              rides on W1' = W1 diag(gamma3), b1' = b1 + W1 beta3: PackArgs)  [last block: eps = W_out post_norm(h2) + b_out, TL_HEAD]
-//   backward   given dh2:  d[a | g], d xhat3 = W1'^T d[a | g],  dh1 = dh2 + LN3'(d xhat3)   [dh_in = dh1 + LN2'(A_s^T dsim)]      (attention.py:50-57, 77-94,
+//   backward   given dh2:  d[a | g], d xhat3 = W1'^T d[a | g],  dh1 = dh2 + LN3'(d xhat3),   dh_in = dh1 + LN2'(A_s^T dsim)        (attention.py:50-57, 77-94,
 //              column sums for the bias / LayerNorm2 gradients; xn2 / dh1 as bf16 fragments for k_attn_bwd_param                    179-204, 296-306)
 //   k_ff_wgrad dW1, db1, dW2 (and through them d gamma3 / d beta3) by a weight-stationary recompute of hid and d[a | g]
 //
@@ -28,7 +28,7 @@
 // A workgroup's four tiles belong to ONE shape (its folded attention fragments sit in LDS once); every memory phase issues all of its loads
 // before it consumes any; both kernels are spill-free (a scratch reload behind output stores waits for their acknowledgements); and between two
 // of these kernels the row-shaped tensors are TILE-MAJOR (RowMap below) so that a wavefront's row accesses cover whole cache lines — see the
-// notes at RowMap and in front of k_ff, and DESIGN.md 5.6.
+// notes at RowMap and in front of ff_bwd, and DESIGN.md 5.6.
 //
 // GELU: g * sigmoid(g (c1 + c3 g^2)) in fp32 with the hardware exp2 / rcp (max abs error 2.7e-4 against the erf form, the same
 // form as the direct sampling kernel) and its exact derivative  s + g s (1 - s) (c1 + 3 c3 g^2).
@@ -132,7 +132,7 @@ __global__ void k_ff_pack(PackBatch batch) {
   if (idx >= PACK_RECORDS * TILES * 2 * 64) return;
   const int lane = idx & 63, u = (idx >> 6) & 1, t = (idx >> 7) % TILES, j = idx / (TILES * 128);
   if (j == NCHUNK && t < T_FW2) return;   // the forward's 17th record: only its W2 tiles (hidden chunk 15) are read
-  if (t >= T_W1AT && t < T_FW1A) return;   // unused padding of the record (once W1a^T / W1g^T: k_ff<true> turns tiles 0 .. 7 around in LDS instead)
+  if (t >= T_W1AT && t < T_FW1A) return;   // unused padding of the record (once W1a^T / W1g^T: k_ff_bwd turns tiles 0 .. 7 around in LDS instead)
   const int i = lane & 31, hf = lane >> 5;
   __bf16 v[8];
 #pragma unroll
@@ -167,34 +167,35 @@ __global__ void k_ff_pack(PackBatch batch) {
 
 struct FfArgs {
   const uint4 *frags;
-  const float *b1p, *b2p;
-  const float *g3, *b3;  // LayerNorm3 affine: xn3 = LN3(h1) is computed here, forward and backward
-  const float *h1;       // (R, 128) input of the sub-block (behind the attention)
-  float *h2;             // forward: (R, 128) output (may alias h1)
-  const float *dh;       // backward: (R, 128) gradient at the block output
-  uint4 *pk;             // backward: [R / 32][2][4][2][64] the tile's xn3 / dh as MFMA fragments, for k_ff_wgrad
-  float *dh1;            // backward: (R, 128) gradient at h1 = dh + LN3'(W1^T d[a | g])
-  float *cpart;          // backward: [workgroups][3][128] column sums for d gamma3, d beta3, d b2
+  const float *b1p, *b2p;   // forward: PackArgs::b1ps; backward: PackArgs::b1p
+  const float *g3, *b3;  // LayerNorm3 affine
+  const float *h1;       // backward: the forward's h1_out
+  float *h2;             // forward: (R, 128) output
+  const float *dh;       // backward: gradient at the block output as bf16-pair tiles (TL_DH_HL's format, below; k_head_bwd writes it too)
+  uint4 *pk;             // backward, only without TL_H1_FRAG / TL_DH_HL: [R / 32][2][4][2][64] the tile's xn3 / dh as MFMA fragments for k_ff_wgrad
+  float *dh1;            // backward, only without at_frags: (R, 128) gradient at h1 = dh + LN3'(W1^T d[a | g])
+                         // (no launch sets either any more — see the note at ff_bwd on why its run-time flags stay)
+  float *cpart;          // backward: [workgroups][6][128] column sums: rows 0, 1 unused, d b2, d gamma2, d beta2, d b_o
   long long R;           // B * N
   int B, N;              // shapes, points per shape (multiple of 32).  A workgroup's NW tiles belong to ONE shape (grid = B x ceil(N / 32 / NW);
                          // wavefronts past a shape's last tile recompute it and store nothing), so that the shape's folded attention
                          // fragments can sit in LDS once per workgroup
-  // forward with the attention sub-block in front (train_attn_fused.h; at_frags != nullptr): h1 = hin + M_s softmax(A_s LN2(hin)) + b_o is
-  // computed here from hin and written out (the backward reads it), instead of being read back from a kernel of its own
+  // the attention sub-block (train_attn_fused.h) in front of the feed-forward: the forward computes h1 = hin + M_s softmax(A_s LN2(hin)) + b_o from hin
+  // and writes what the backward wants of it (TL_H1_FRAG, below)
   const uint4 *at_frags;   // [B][4 sets][4][2][64] folded (A_s, M_s) fragments of this block
   const float *valid;      // (B, 4)
   const float *g2, *b2n, *bo;
   const float *hin;        // (R, 128)
-  float *h1_out;           // (R, 128)
-  // backward with the attention's input gradient behind it (at_frags != nullptr): dh_in = dh1 + LN2'(A_s^T dsim) leaves through dh_in
-  // (may alias dh: a wavefront reads its rows of dh before it writes them) and cpart gets three more rows (d gamma2, d beta2, d b_o)
+  float *h1_out;           // the tiles of (R, 128)
+  // backward: the attention's input gradient behind the feed-forward's: dh_in = dh1 + LN2'(A_s^T dsim) leaves through dh_in (block 0: fp32 rows for
+  // the stem; the others: bf16-pair tiles, TL_DHIN_HL)
   float *dh_in;
-  // Layout of the row-shaped tensors only these kernels touch (bit 1 = tile-major, see tile_b_off): the residual stream between two blocks and the
+  // Layout of the row-shaped tensors only these kernels touch (tile-major or not, see RowMap): the residual stream between two blocks and the
   // gradient between two blocks' backward kernels; the ends (written by the stem, read by the head, and back) stay row-major
   unsigned tiled;          // TL_* bits
-  uint4 *pk2;              // with at_frags: [R / 32][2][4][2][64] the tile's xn2 and dh1 as bf16 fragments for k_attn_bwd_param (which
-                           // needs nothing else of them); dh1 itself is then not written
-  // dropout (k_ff<*, true>; dfx_dropout.h): the step's key, this block's two sites and ONE BIT per element of the two dropped tensors.
+  uint4 *pk2;              // backward: [R / 32][2][4][2][64] the tile's xn2 and dh1 as bf16 fragments for k_attn_bwd_param (which
+                           // needs nothing else of them; dh1 itself is not written)
+  // dropout (ff_fwd<true>, k_ff_bwd<true>; dfx_dropout.h): the step's key, this block's two sites and ONE BIT per element of the two dropped tensors.
   // The forward draws the factors and leaves the bits; the backward kernels read them (k_ff_wgrad needs them in the transposed orientation,
   // where a regeneration would cost four Philox calls per group).  dmask [R / 32][DM_WORDS][64 lanes]: word w < 8, half h = hidden chunk 2 w + h,
   // bit r of the half = register r of the chunk's accumulator (unit 32 j + rho(r, hf) of point pj); words 8, 9 = the to_out site, half h =
@@ -338,19 +339,8 @@ __device__ __forceinline__ void load16(v16f &v, const float *src) {
     v[4 * q + 0] = t[0], v[4 * q + 1] = t[1], v[4 * q + 2] = t[2], v[4 * q + 3] = t[3];
   }
 }
-// This lane's row of h in the B-operand layout (8 consecutive channels 32 c + 16 u + 8 hf .. per (c, u)), LayerNorm statistics
-// (two passes like torch) and the normalised, affine row as bf16 fragments.  gb = LDS table [gamma(128) | beta(128)].
-__device__ __forceinline__ void load_rows(const float *__restrict__ hrow, int hf, v8f (&x)[4][2]) {
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const float *p = hrow + 32 * c + k_nat(u, hf, 0);
-      const v4f lo = *reinterpret_cast<const v4f *>(p), hi = *reinterpret_cast<const v4f *>(p + 4);
-      x[c][u] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    }
-}
-// The same row in the accumulator layout (register r of tile c = channel 32 c + rho(r, hf)) without reading it again: the two
+// A lane's row in the B-operand layout (8 consecutive channels 32 c + 16 u + 8 hf .. per (c, u), load_rows below) -> the same row in the
+// accumulator layout (register r of tile c = channel 32 c + rho(r, hf)) without reading it again: the two
 // half-waves of a point hold complementary channel sets in either layout, and v_permlane32_swap trades the halves of two registers
 // in one instruction: (x[u][m], x[u][4 + m]) -> (d[8 u + m], d[8 u + 4 + m]).  The same call converts back.
 __device__ __forceinline__ void rows_to_acc(const v8f (&x)[4][2], v16f (&d)[4]) {
@@ -414,51 +404,9 @@ __device__ __forceinline__ void softmax_bwd_regs(const v16f &P, v16f &dP) {
     for (int j = 0; j < 4; ++j) dP[4 * g + j] = P[4 * g + j] * (dP[4 * g + j] - dot);
   }
 }
-__device__ __forceinline__ void ln_rows(const v8f (&x)[4][2], int hf, const float *gb, uint4 (&xn)[4][2], float &mu, float &rstd) {
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s += x[c][u][e];
-  s += xhalf(s);
-  mu = s * (1.0f / C);
-  float q = 0.f;
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float d = x[c][u][e] - mu;
-        q = fmaf(d, d, q);
-      }
-  q += xhalf(q);
-  rstd = 1.0f / sqrtf(q * (1.0f / C) + LN_EPS);
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int ch = 32 * c + k_nat(u, hf, 0);
-      const v4f g0 = *reinterpret_cast<const v4f *>(gb + ch), g1 = *reinterpret_cast<const v4f *>(gb + ch + 4);
-      const v4f b0 = *reinterpret_cast<const v4f *>(gb + C + ch), b1 = *reinterpret_cast<const v4f *>(gb + C + ch + 4);
-      v8f y;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        y[e] = fmaf((x[c][u][e] - mu) * rstd, g0[e], b0[e]);
-        y[4 + e] = fmaf((x[c][u][4 + e] - mu) * rstd, g1[e], b1[e]);
-      }
-      xn[c][u] = __builtin_bit_cast(uint4, __builtin_convertvector(y, v8bf));
-    }
-}
-__device__ __forceinline__ void ln_rows(const float *__restrict__ hrow, int hf, const float *gb, uint4 (&xn)[4][2], float &mu, float &rstd) {
-  v8f x[4][2];
-  load_rows(hrow, hf, x);
-  ln_rows(x, hf, gb, xn, mu, rstd);
-}
 
-// ln_rows in two pieces — the statistics, and ONE affine bf16 fragment — for callers that consume the fragments as they are made
+// LayerNorm of a lane's row (B-operand layout) in two pieces — the statistics (two passes like torch), and ONE normalised, affine bf16 fragment
+// (gb = LDS table [gamma(128) | beta(128)]) — for callers that consume the fragments as they are made
 __device__ __forceinline__ void ln_stats(const v8f (&x)[4][2], float &mu, float &rstd) {
   float s = 0.f;
 #pragma unroll
@@ -581,10 +529,6 @@ __device__ __forceinline__ void gelu_fd(float x, float &f, float &d) {
   f = x * s;
   d = fmaf(f * (1.0f - s), fmaf(0.20820537f, x2, 1.60031416f), s);   // s + x s (1 - s) (c1 + 3 c3 x^2)
 }
-__device__ __forceinline__ float gelu_f(float x) {
-  const float e = __builtin_amdgcn_exp2f(x * fmaf(-0.100125614f, x * x, -2.30876530f));
-  return x * __builtin_amdgcn_rcpf(1.0f + e);
-}
 // The same arithmetic on PAIRS of accumulator registers (round 5): gfx950's packed fp32 instructions (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32) do two
 // lanes' worth of an fp32 operation per issue slot — same IEEE results, half the VALU slots; only exp2 / rcp stay one element per instruction.  The loops
 // of the three feed-forward kernels spend as many SIMD cycles on this arithmetic as on their MFMAs.
@@ -598,10 +542,6 @@ __device__ __forceinline__ void gelu_fd2(v2f x, v2f &f, v2f &d) {
   const v2f s = rcp_2(splat2(1.0f) + e);
   f = x * s;
   d = __builtin_elementwise_fma(f * (splat2(1.0f) - s), __builtin_elementwise_fma(splat2(0.20820537f), x2, splat2(1.60031416f)), s);
-}
-__device__ __forceinline__ v2f gelu_f2(v2f x) {
-  const v2f e = exp2_2(x * __builtin_elementwise_fma(splat2(-0.100125614f), x * x, splat2(-2.30876530f)));
-  return x * rcp_2(splat2(1.0f) + e);
 }
 __device__ __forceinline__ v2f pair(const v16f &v, int i) { return v2f{v[2 * i], v[2 * i + 1]}; }
 __device__ __forceinline__ void set_pair(v16f &v, int i, v2f x) { v[2 * i] = x[0], v[2 * i + 1] = x[1]; }
@@ -647,13 +587,12 @@ __device__ __forceinline__ v16f mfma_f16(const uint4 &a, const uint4 &b, v16f c)
 }
 
 constexpr int B1P_FLOATS = NCHUNK * 64, B2P_FLOATS = 128;
-// per 32-point tile, for k_ff_wgrad: two sets of fragments [4 c][2 u][64 lanes] (8 KiB each) in memory; k_ff_wgrad derives the
-// transposed sets (PK_XNT, PK_DHT: channels on the lanes, points along the registers) in LDS
+// per 32-point tile, in k_ff_wgrad's LDS ring: two sets of fragments [4 c][2 u][64 lanes] (8 KiB each: the xhat3 fragments of the forward's h1 tile, the hi half
+// of the incoming gradient's pair tile) and the transposed sets it derives from them (PK_XNT, PK_DHT: channels on the lanes, points along the registers)
 enum { PK_XN = 0, PK_DH = 1, PK_XNT = 2, PK_DHT = 3 };
 constexpr int PK_TILE_U4 = 2 * 8 * 64;   // 16 KiB
 constexpr int NW_BWD = 4;   // wavefronts per workgroup, backward: 128 points; three 24 KiB slots (79 KiB: two workgroups per CU), one record per chunk
 constexpr int NW_FWD = 4;   // forward: 128 points and 77 KiB of LDS, TWO workgroups per CU — one's row loads / stores run under the other's chunk loop
-template <bool BWD> constexpr int nw_of() { return BWD ? NW_BWD : NW_FWD; }
 constexpr int NBUF = 3;   // LDS chunk buffers: the stream runs two chunks ahead of the compute
 // s_setprio experiments (round 6, same-box A/Bs, profiles/r06_ab_train_prio.txt): raising a wavefront's priority inside its VALU stretch (the sampling
 // kernel runs its V slots at 3) helped the forward (652 -> 637 us) and HURT the backward (278 -> 283 per block) and the weight-gradient kernel's
@@ -674,19 +613,6 @@ __device__ __forceinline__ v4s lds_tr16(unsigned lds_addr) {
 // (measured, B = 128 x 2048, backward / forward per block: 8 waves x 3 buffers 441 / 161 us; 4 waves x 2 buffers, two workgroups
 // per CU, 513 / 161 us; 8 x 2: 662 / 182 us)
 
-// stage `ntile_groups` runs of tiles of chunk j into LDS buffer `buf` (each wave copies every NW-th KiB)
-template <bool BWD>
-__device__ __forceinline__ void stage_chunk(const uint4 *frags, int j, unsigned lds_buf, int wave, unsigned voff) {
-  const char *src = reinterpret_cast<const char *>(frags + (size_t)j * CHUNK_U4);
-  constexpr int NK = (BWD ? BWD_TILES : FWD_TILES) * 2;   // KiB to copy
-  constexpr int NW = nw_of<BWD>();
-#pragma unroll
-  for (int k = 0; k < NK / NW; ++k) {
-    const int piece = k * NW + wave;                                     // destination KiB
-    const int spiece = BWD && piece >= 16 ? piece + 8 : piece;           // backward skips tiles 8..11 (W2)
-    dma1k(src + spiece * 1024, voff, lds_buf + piece * 1024);
-  }
-}
 // ff_fwd's record j: the forward's own twelve tiles of pack record j (T_FW1A ..: scaled W1a | W1g of chunk j, fp16 W2 of chunk j - 1)
 __device__ __forceinline__ void stage_record_fwd(const uint4 *frags, int j, unsigned lds_buf, int wave, unsigned voff) {
   const char *src = reinterpret_cast<const char *>(frags + (size_t)j * CHUNK_U4) + FWD_TILE0 * 2048;
@@ -706,20 +632,6 @@ __device__ __forceinline__ void stage_record_bwd(const uint4 *frags, int j, unsi
     dma1k(src + (p < 16 ? p : p + 8) * 1024, voff, lds_slot + p * 1024);
   }
 }
-// LDS tile index of pack tile t (backward: W2^T sits behind W1a | W1g in the slot)
-template <bool BWD>
-__device__ __forceinline__ constexpr int lt(int t) { return BWD && t >= T_W2T ? t - 4 : t; }
-
-// The same row in the accumulator layout straight from memory: register 4 q + m of tile c = channel 32 c + 8 q + 4 hf + m (= 32 c + rho(4 q + m, hf))
-__device__ __forceinline__ void load_rows_acc(const float *__restrict__ hrow, int hf, v16f (&d)[4]) {
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const v4f t = *reinterpret_cast<const v4f *>(hrow + 32 * c + 8 * q + 4 * hf);
-      d[c][4 * q + 0] = t[0], d[c][4 * q + 1] = t[1], d[c][4 * q + 2] = t[2], d[c][4 * q + 3] = t[3];
-    }
-}
 
 // ---- Tile-major rows (round 4).  With row-major (R, 128) fp32 tensors every row access of a wavefront — lane = point — touches 32 cache lines for 1 KiB
 // (16 bytes per row), and each line is requested by four different instructions: the memory phases ran at the rate of their L1 transactions.  Between two
@@ -727,20 +639,20 @@ __device__ __forceinline__ void load_rows_acc(const float *__restrict__ hrow, in
 // floats, the B-operand layout itself; a load or store instruction then covers whole lines — in BOTH register layouts the kernels use:
 //   B-operand layout, block (c, u), element e of lane (pj, hf) = channel 32 c + 16 u + 8 hf + e     -> ((c 2 + u) 2 + e / 4) 256 + lane 4 + e % 4
 //   accumulator layout, register 4 q + m of tile c, lane (pj, hf) = channel 32 c + 8 q + 4 hf + m  -> ((c 2 + q / 2) 2 + hf) 256 + (pj + 32 (q & 1)) 4 + m
-// (the same element either way).  Measured: k_ff<true> 356 -> 334 us, k_ff<false> 180 -> 165 us per block.
+// (the same element either way).  Measured (round 4): the backward kernel 356 -> 334 us, the forward 180 -> 165 us per block.
 enum { TL_HIN = 1, TL_H1 = 2, TL_H2 = 4, TL_DH = 8, TL_DHIN = 16, TL_DH_HL = 32, TL_DHIN_HL = 64, TL_H1_FRAG = 128, TL_HEAD = 256 };
 // ---- h1 as the backward wants it (round 5, TL_H1_FRAG; forward with the attention sub-block inside).  The backward kernels need two things of h1: the bf16
-// fragments of xhat3 = LayerNorm3's normalised row (k_ff<true>'s B operand and, turned around, LayerNorm3's backward; k_ff_wgrad's tiles) and the row's
+// fragments of xhat3 = LayerNorm3's normalised row (k_ff_bwd's B operand and, turned around, LayerNorm3's backward; k_ff_wgrad's tiles) and the row's
 // 1 / std.  So the forward stores exactly those in the tile's 16 KiB — [xhat3: 8 blocks (c, u) of 1 KiB = the PK_XN set][rstd: 32 floats] — instead of
 // the fp32 rows: 260 B per point written and read instead of 512, bit-identical operands (the backward rounded the same fp32 values to bf16), no
-// LayerNorm statistics in the backward's prologue, and k_ff<true> no longer writes the xhat3 half of FfArgs::pk (k_ff_wgrad reads these tiles).
+// LayerNorm statistics in the backward's prologue, and k_ff_bwd writes nothing for k_ff_wgrad (which reads these tiles).
 constexpr int H1F_RSTD = 2048;   // float offset of the tile's 32 rstd values
 // ---- The gradient between two blocks' backward kernels as a bf16 PAIR (round 5, TL_DH_HL / TL_DHIN_HL): hi = bf16(dh) and lo = bf16(dh - hi), i.e. dh to
 // 2^-17 relative, in the tile's own 16 KiB: [hi: 8 blocks (c, u) of 1 KiB, the bf16 B-operand fragments themselves][lo: 8 blocks (c, k) of 1 KiB in the
 // accumulator layout, registers 8 k .. 8 k + 7 of tile c as 8 bf16 per lane].  The backward kernel wants dh twice — rounded to bf16 as the operand of
 // d hid = W2^T dh in front of the chunk loop, and in full behind it for dh1 = dh + ... — and cannot hold it across the loop: as fp32 that was 2 x 512 B
 // per point, now 256 B (hi, which goes straight into the MFMA and is turned into the accumulator layout with permlane swaps behind the loop) + 256 B
-// (lo).  k_ff_wgrad reads the same hi blocks as its dh fragments (FwArgs::dhf), so k_ff<true> writes only the xhat3 half of FfArgs::pk: 768 B per
+// (lo).  k_ff_wgrad reads the same hi blocks as its dh fragments (FwArgs::dhf), so k_ff_bwd writes no fragments for it: 768 B per
 // point and block less traffic.  The ends of the stack (the head's output, the stem's input) stay fp32 row-major.
 
 struct RowMap {   // per tensor: one lane offset for each register layout (floats), tiled or not
@@ -759,17 +671,8 @@ __device__ __forceinline__ void load_rows(const float *__restrict__ tile, const 
       x[c][u] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
     }
 }
-__device__ __forceinline__ void load_rows_acc(const float *__restrict__ tile, const RowMap &m, v16f (&d)[4]) {
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const v4f t = *reinterpret_cast<const v4f *>(tile + m.a(c, q));
-      d[c][4 * q + 0] = t[0], d[c][4 * q + 1] = t[1], d[c][4 * q + 2] = t[2], d[c][4 * q + 3] = t[3];
-    }
-}
 
-// LDS map of k_ff: [ring: 3 slots x 24 KiB][b1 of all chunks 4 KiB][gamma3 | beta3 1 KiB][gamma2 | beta2 | b_o 1.5 KiB][b2 0.5 KiB] = 79 KiB, two
+// LDS map of k_ff_fwd_chain / k_ff_bwd: [ring: 3 slots x 24 KiB][b1 of all chunks 4 KiB][gamma3 | beta3 1 KiB][gamma2 | beta2 | b_o 1.5 KiB][b2 0.5 KiB] = 79 KiB, two
 // workgroups per CU.  The folded attention fragments of the workgroup's shape borrow ring space while the ring is idle: forward, slot 2
 // during the prologue ([A_s | M_s], 16 KiB; chunk 2 is only requested behind the prologue's last barrier); backward, 24 KiB at AT_OFF_BWD
 // behind the loop ([A_s | M_s^T | A_s^T]; the column-sum tiles of the epilogue use the 30 KiB in front of it).
@@ -783,16 +686,19 @@ constexpr int AT_OFF_BWD = 32768;
 // forward's prologue, ~6 in the backward's and ~45 in its epilogue — 58 % of a backward wavefront's life.  Now: rows first, tables and ring
 // behind them, ONE wait; attention fragments through LDS (LDS-DMA, no registers); the epilogue's second reads as two batches.  Vector-memory
 // operations complete in issue order (loads, stores and LDS-DMA alike), so stores may stay in flight across the counted waits of the loop.
-// The body of k_ff / k_ff_fwd_chain.  `first`: the lane's rows come from memory; otherwise (forward chain, blocks behind the first) they are `hc`, the
-// previous block's output, still in the accumulator registers it was computed in.  `hc` leaves with this block's output (forward).
-template <bool BWD, bool DROP>
-__device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (&hc)[4], int &trace_n) {
-  constexpr int NW = nw_of<BWD>();
+// The body of k_ff_bwd: one block's backward, the attention sub-block's input gradient included.
+// Every launch has at_frags, TL_H1_FRAG and TL_DH_HL set, yet `at`, `h1f` and `hl_in` stay run-time values, dummy-pointer selects included: with `at` a
+// compile-time constant (tried with the other two folded and without) hipcc schedules the larger straight-line regions so that the kernel spills — 0 -> 25
+// registers without dropout, 17 -> 49 .. 54 with, reloads inside the chunk loop — and the iteration at B = 128 x 2048 runs 3.91 -> 3.97 (p = 0) and 4.27 -> 4.41 ms (p = 0.2)
+// (profiles/ab_retire_split_attn.txt).  As written this is instruction for instruction the backward half of the body it was cut out of.
+template <bool DROP>
+__device__ __forceinline__ void ff_bwd(const FfArgs &a) {
+  constexpr int NW = NW_BWD;
   static_assert(NW == 4 && NW * 64 == 2 * C && FWD_TILES == BWD_TILES && B1P_FLOATS * 4 == NW * 1024, "table staging below assumes 256 threads");
-  constexpr int BUF_BYTES = (BWD ? BWD_TILES : FWD_TILES) * 2048;
+  constexpr int BUF_BYTES = BWD_TILES * 2048;
   extern __shared__ __attribute__((aligned(1024))) unsigned char ff_smem[];
   int lane_ = threadIdx.x & 63;
-  asm volatile("" : "+v"(lane_));   // (opaque per call: in the chain hipcc otherwise hoists every lane-derived offset out of the block loop and keeps ~40 registers alive)
+  asm volatile("" : "+v"(lane_));
   const int lane = lane_, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int hf = lane >> 5, pj = lane & 31;
   const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)ff_smem);
@@ -805,194 +711,96 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
   if (!live) ti = tps - 1;   // a workgroup's trailing wavefronts past the shape's end recompute its last tile and store nothing
   // rows: a wave-uniform base (scalar registers) + ONE lane offset for every row-shaped tensor
   const long long rowbase = ((long long)s * a.N + ti * 32) * C;
-  const RowMap m_hin(a.tiled & TL_HIN, lane, pj, hf), m_h1(a.tiled & TL_H1, lane, pj, hf), m_h2(a.tiled & TL_H2, lane, pj, hf);
+  const RowMap m_hin(a.tiled & TL_HIN, lane, pj, hf), m_h1(a.tiled & TL_H1, lane, pj, hf);
   const RowMap m_dh(a.tiled & TL_DH, lane, pj, hf), m_dhin(a.tiled & TL_DHIN, lane, pj, hf);
   const bool at = a.at_frags != nullptr;
 
-  constexpr int PIECES = FWD_TILES * 2 / NW;   // LDS-DMA instructions per wave and chunk: six, forward and backward
-  FFT_INIT_CHAIN(a, BWD ? 1 : 0, !BWD && !first ? trace_n : 0);   // (trace builds: the chain's later blocks append)
+  constexpr int PIECES = BWD_TILES * 2 / NW;   // LDS-DMA instructions per wave and chunk: six
+  FFT_INIT(a, 1);
   FFT(1);
   // ---- prologue, memory side: this lane's rows first (the oldest requests come back first), then the tables, then the ring ----
   v8f x[4][2], xd[4][2];
   const bool h1f = a.tiled & TL_H1_FRAG;
   uint4 xn[4][2];
   float mu, rstd = 0.f;
-  if (BWD && h1f) {   // what the forward left: the xhat3 fragments and 1 / std of this lane's row
+  if (h1f) {   // what the forward left: the xhat3 fragments and 1 / std of this lane's row
     const uint4 *hp = reinterpret_cast<const uint4 *>(a.h1 + rowbase) + lane;
 #pragma unroll
     for (int c = 0; c < 4; ++c) xn[c][0] = hp[(c * 2 + 0) * 64], xn[c][1] = hp[(c * 2 + 1) * 64];
     rstd = (a.h1 + rowbase)[H1F_RSTD + pj];
-  } else if (BWD || first) {
-    load_rows((BWD || !at ? a.h1 : a.hin) + rowbase, BWD || !at ? m_h1 : m_hin, x);   // (one load site: selected pointer and map, no branch)
+  } else {
+    load_rows(a.h1 + rowbase, m_h1, x);
   }
-  const bool hl_in = BWD && (a.tiled & TL_DH_HL), hl_out = BWD && (a.tiled & TL_DHIN_HL);
+  const bool hl_in = a.tiled & TL_DH_HL, hl_out = a.tiled & TL_DHIN_HL;
   uint4 dhb[4][2];
-  if (BWD) {
-    if (hl_in) {   // the bf16 fragments themselves
-      const uint4 *hp = reinterpret_cast<const uint4 *>(a.dh + rowbase) + lane;
+  if (hl_in) {   // the bf16 fragments themselves
+    const uint4 *hp = reinterpret_cast<const uint4 *>(a.dh + rowbase) + lane;
 #pragma unroll
-      for (int c = 0; c < 4; ++c) dhb[c][0] = hp[(c * 2 + 0) * 64], dhb[c][1] = hp[(c * 2 + 1) * 64];
-    } else {
-      load_rows(a.dh + rowbase, m_dh, xd);
-    }
+    for (int c = 0; c < 4; ++c) dhb[c][0] = hp[(c * 2 + 0) * 64], dhb[c][1] = hp[(c * 2 + 1) * 64];
+  } else {
+    load_rows(a.dh + rowbase, m_dh, xd);
   }
-  // dropout: this tile's bit words (one lane = one point half, the forward's mapping); the backward holds the eight feed-forward words across the loop
+  // dropout: this tile's bit words (one lane = one point half, the forward's mapping); the eight feed-forward words are held across the loop
   unsigned *dmk = DROP ? a.dmask + (size_t)(rowbase / (32 * C)) * DM_TILE + lane : nullptr;
-  const unsigned long long prow = (unsigned long long)(rowbase / C) + pj;   // this lane's row of the (R, .) tensors
-  unsigned dmw = 0;   // forward: the word being assembled; backward: the word of chunks (j & ~1, + 1), read out of the mask buffer in every even chunk
+  unsigned dmw = 0;   // the word of chunks (j & ~1, + 1), read out of the mask buffer in every even chunk
   float *b1s = reinterpret_cast<float *>(ff_smem + TAB_B1);
-  float *dump = reinterpret_cast<float *>(ff_smem + TAB_GB3);   // 1 KiB nobody reads
-  float *gb2 = reinterpret_cast<float *>(ff_smem + TAB_GB2);   // LayerNorm2 affine | to_out bias (attention sub-block fused in)
+  float *gb2 = reinterpret_cast<float *>(ff_smem + TAB_GB2);   // LayerNorm2 affine | to_out bias
   float *b2s = reinterpret_cast<float *>(ff_smem + TAB_B2);
-  // tables: every thread fetches gamma2 | beta2 of its channel, threads 0 .. 127 (waves 0, 1) b_o, the others b2 — unconditional loads
-  // through selected pointers (a branch here costs a wait for the rows: hipcc resolves the write-after-write on the other path with vmcnt(0))
-  const int tx = threadIdx.x, tc = tx & (C - 1);
+  // tables: every thread fetches gamma2 | beta2 of its channel, threads 0 .. 127 (waves 0, 1) b_o, the others a valid dummy (b1p; the forward's b2
+  // has no use here) — unconditional loads through selected pointers (a branch here costs a wait for the rows: hipcc resolves the
+  // write-after-write on the other path with vmcnt(0)).  LayerNorm3's affine rides on W1 / b1: no table for it
+  const int tc = threadIdx.x & (C - 1);
   const bool lo_half = wave < NW / 2;
-  // (LayerNorm3's affine rides on W1 / b1: no table for it.  Without the attention sub-block the loads go to a valid dummy, b1p)
   const float *tp0 = at ? a.g2 : a.b1p, *tp1 = at ? a.b2n : a.b1p;
-  const float *tp2 = lo_half ? (at ? a.bo : a.b1p) : (!BWD ? a.b2p : a.b1p);
+  const float *tp2 = lo_half ? (at ? a.bo : a.b1p) : a.b1p;
   const float tv0 = tp0[tc], tv1 = tp1[tc], tv2 = tp2[tc];
   dma1k(reinterpret_cast<const char *>(a.b1p) + wave * 1024, voff, lds0 + TAB_B1 + wave * 1024);
-  // (backward, dropout) the bit word of chunks (0, 1) -> this wave's 256 bytes of the mask buffer: LDS-DMA like the ring's pieces, so that the loop's counted
+  // (dropout) the bit word of chunks (0, 1) -> this wave's 256 bytes of the mask buffer: LDS-DMA like the ring's pieces, so that the loop's counted
   // waits cover it (loads of one kind complete in order; a load that returns to a register does not keep that order against them — HISTORY round 6 #11)
   const unsigned *dmt = DROP ? a.dmask + (size_t)(rowbase / (32 * C)) * DM_TILE : nullptr;   // wave-uniform: this tile's words
-  if (BWD && DROP) dma256(dmt, lane * 4, lds0 + TAB_GB3 + wave * 256);   // (as sixteen lanes x 16 bytes instead: measured, no difference)
-  if (BWD) {
-    stage_record_bwd(a.frags, 0, lds0, wave, voff);
-    stage_record_bwd(a.frags, 1, lds0, wave, voff);
-  } else {
-    if (at) {   // [A_s | M_s] of this shape -> slot 2
-      const char *src = reinterpret_cast<const char *>(a.at_frags + (size_t)s * SHAPE_U4);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) dma1k(src + (k * NW + wave) * 1024, voff, lds0 + 2 * BUF_BYTES + (k * NW + wave) * 1024);
-    }
-    stage_chunk<BWD>(a.frags, 0, lds0, wave, voff);
-    stage_chunk<BWD>(a.frags, 1, lds0 + BUF_BYTES, wave, voff);
-  }
+  if (DROP) dma256(dmt, lane * 4, lds0 + TAB_GB3 + wave * 256);   // (as sixteen lanes x 16 bytes instead: measured, no difference)
+  stage_record_bwd(a.frags, 0, lds0, wave, voff);
+  stage_record_bwd(a.frags, 1, lds0, wave, voff);
   unsigned vmask = 0;
   if (at) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) vmask |= (a.valid[s * 4 + j] != 0.f ? 1u : 0u) << j;
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // ONE round trip: rows, tables, attention fragments, the first two chunks
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // ONE round trip: rows, tables, the first two chunks
   {
-    // waves 0, 1: gamma2 | beta2 | b_o; waves 2, 3: b2 — their copies of gamma2 | beta2 go to the dump, or (backward: the dump is the mask buffer) on top of waves 0, 1's: the same values
-    float *d0 = lo_half || BWD ? gb2 : dump, *d2 = lo_half ? gb2 + 2 * C : b2s;
+    // waves 0, 1: gamma2 | beta2 | b_o; waves 2, 3: the dummy to the b2 table nobody reads, their copies of gamma2 | beta2 on top of waves 0, 1's (the same values)
+    float *d0 = gb2, *d2 = lo_half ? gb2 + 2 * C : b2s;
     d0[tc] = tv0, d0[C + tc] = tv1, d2[tc] = tv2;
   }
   __syncthreads();
   FFT(16);
-  // B operand of the products over the channels: xhat3 of LN3(h1) (bf16, natural K order) and, backward, dh rounded to bf16
-  v16f acc[4];   // forward: the residual stream h; backward: dxn3
-  if (!BWD && !first) acc_to_rows(hc, x);   // (chained forward: this block's input rows = the previous block's output, never re-read)
-  if (!BWD && at) {
-    // attention sub-block in registers: h1 = hin + M_s softmax(A_s LN2(hin)) + b_o, then straight on to LayerNorm3
-    const uint4 *fl = reinterpret_cast<const uint4 *>(ff_smem + 2 * BUF_BYTES) + lane;
-    v16f sim = zero16();
-    {
-      float mu2, rstd2;
-      ln_stats(x, mu2, rstd2);
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) sim = mfma(fl[F_AS * SET_U4 + (c * 2 + u) * 64], ln_frag(x[c][u], c, u, hf, gb2, mu2, rstd2), sim);
-    }
-    softmax_regs(sim, vmask);
-    const uint4 p0 = pack8(sim, 0), p1 = pack8(sim, 1);
-    rows_to_acc(x, acc);   // (also in the chain: keeping hc alive through the attention prologue beside x costs 64 registers)
-    unsigned attw = 0;
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) {
-      if (DROP) {
-        // h1 = hin + dropout(M_s P + b_o)  (attention.py:177: to_out = Sequential(Linear, Dropout)): the sub-block's output in a fresh accumulator,
-        // selected and scaled, then added to the residual; element (row, channel 32 ct + 8 q + 4 hf + m) = group row * 16 + 4 ct + q of the site
-        v16f t;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const v4f b = *reinterpret_cast<const v4f *>(gb2 + 2 * C + 32 * ct + 8 * q + 4 * hf);
-#pragma unroll
-          for (int m = 0; m < 4; ++m) t[4 * q + m] = b[m];
-        }
-        t = mfma(fl[F_MS * SET_U4 + (ct * 2 + 0) * 64], p0, t);
-        t = mfma(fl[F_MS * SET_U4 + (ct * 2 + 1) * 64], p1, t);
-        unsigned w[4][2];
-        drop_words(a.dk, a.site_att, prow * (C / 8) + 4 * ct, hf, w);
-        const unsigned bits = drop_apply(t, w, a.dk.thr);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[ct][r] = fmaf(a.dk.keep, t[r], acc[ct][r]);
-        attw |= bits << (16 * (ct & 1));
-        if (ct & 1) {
-          if (live) dmk[(8 + (ct >> 1)) * 64] = attw;
-          attw = 0;
-        }
-      } else {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const v4f b = *reinterpret_cast<const v4f *>(gb2 + 2 * C + 32 * ct + 8 * q + 4 * hf);
-#pragma unroll
-        for (int m = 0; m < 4; ++m) acc[ct][4 * q + m] += b[m];
-      }
-      acc[ct] = mfma(fl[F_MS * SET_U4 + (ct * 2 + 0) * 64], p0, acc[ct]);
-      acc[ct] = mfma(fl[F_MS * SET_U4 + (ct * 2 + 1) * 64], p1, acc[ct]);
-      }
-      if (live && !h1f) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          *reinterpret_cast<v4f *>(a.h1_out + rowbase + m_h1.a(ct, q)) = v4f{acc[ct][4 * q], acc[ct][4 * q + 1], acc[ct][4 * q + 2], acc[ct][4 * q + 3]};
-      }
-    }
-    acc_to_rows(acc, x);   // h1 in the B-operand layout for LayerNorm3
-    FFT(17);
-    __syncthreads();       // everybody is done with the attention fragments: slot 2 takes chunk 2 at the top of the loop
-    FFT(18);
-  } else if (!BWD) {
-    rows_to_acc(x, acc);   // h1 in the accumulator layout, from the same read
-  }
-  // LayerNorm3 on this lane's row of h1: statistics and the plain normalised row as bf16 fragments (gamma3 / beta3 ride on W1 / b1, PackArgs)
-  if (!(BWD && h1f)) {
+  v16f acc[4];   // dxn3
+  if (!h1f) {   // LayerNorm3 on this lane's row of h1: statistics and the plain normalised row as bf16 fragments
     ln_stats(x, mu, rstd);
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
       for (int u = 0; u < 2; ++u) xn[c][u] = xhat_frag(x[c][u], mu, rstd);
   }
-  if (!BWD && at && h1f && live) {   // h1 for the backward kernels: these fragments and 1 / std (TL_H1_FRAG)
-    uint4 *hp = reinterpret_cast<uint4 *>(a.h1_out + rowbase) + lane;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) hp[(c * 2 + 0) * 64] = xn[c][0], hp[(c * 2 + 1) * 64] = xn[c][1];
-    if (hf == 0) (a.h1_out + rowbase)[H1F_RSTD + pj] = rstd;
-  }
-  if (BWD) {
-    if (!hl_in) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) dhb[c][u] = __builtin_bit_cast(uint4, __builtin_convertvector(xd[c][u], v8bf));
-    }
+  if (!hl_in) {
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
-    // the tile for k_ff_wgrad: xhat3 and dh as bf16 B-operand fragments (points on the lanes), whole 1 KiB stores (left in flight); a bf16-pair
-    // gradient's hi half IS the second set: k_ff_wgrad reads it in place
-    if (live) {
-      uint4 *pk = a.pk + (size_t)(rowbase / (32 * C)) * PK_TILE_U4 + lane;
-      if (!h1f) {
+      for (int u = 0; u < 2; ++u) dhb[c][u] = __builtin_bit_cast(uint4, __builtin_convertvector(xd[c][u], v8bf));
+  }
 #pragma unroll
-        for (int c = 0; c < 4; ++c) pk[(PK_XN * 8 + c * 2 + 0) * 64] = xn[c][0], pk[(PK_XN * 8 + c * 2 + 1) * 64] = xn[c][1];
-      }
-      if (!hl_in) {
+  for (int c = 0; c < 4; ++c)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) pk[(PK_DH * 8 + c * 2 + 0) * 64] = dhb[c][0], pk[(PK_DH * 8 + c * 2 + 1) * 64] = dhb[c][1];
-      }
+    for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
+  if (live) {
+    uint4 *pk = a.pk + (size_t)(rowbase / (32 * C)) * PK_TILE_U4 + lane;
+    if (!h1f) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) pk[(PK_XN * 8 + c * 2 + 0) * 64] = xn[c][0], pk[(PK_XN * 8 + c * 2 + 1) * 64] = xn[c][1];
     }
-  } else {
+    if (!hl_in) {
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      v16f b2;
-      load16(b2, b2s + hf * 64 + c * 16);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[c][r] += b2[r];
+      for (int c = 0; c < 4; ++c) pk[(PK_DH * 8 + c * 2 + 0) * 64] = dhb[c][0], pk[(PK_DH * 8 + c * 2 + 1) * 64] = dhb[c][1];
     }
   }
   FFT(2);
@@ -1000,65 +808,25 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
 #pragma unroll 1
   for (int j = 0; j < NCHUNK; ++j) {
     // chunk j + 2 -> the slot of chunk j - 1 (every wave is past its last read: the barrier at the bottom)
-    if (!BWD) {
-      if (j + NBUF - 1 < NCHUNK) stage_chunk<BWD>(a.frags, j + NBUF - 1, lds0 + ((j + NBUF - 1) % NBUF) * BUF_BYTES, wave, voff);
-    } else {
-      // Dropout: odd chunks first request the bit word of the NEXT pair (its predecessor was read into a register in chunk j - 1): in front of the pieces,
-      // so "at most six outstanding" at this chunk's end covers it.  The word travels by LDS-DMA like the pieces because loads of one kind complete in
-      // order, and a load that returns to a register does not keep that order against them: until round 6 the word was such a load under a counted
-      // wait, and occasionally stale at B = 128 x 2048 (run-to-run differences of 2e-3 in every gradient below the first block's;
-      // tools/soak_train_streams.py with dropout).  LDS-DMA pieces among themselves, and stores against them, keep the counted waits valid.
-      if (DROP && (j & 1) && j + 1 < NCHUNK) dma256(dmt + ((j + 1) >> 1) * 64, lane * 4, lds0 + TAB_GB3 + wave * 256);
-      if (j + 2 < NCHUNK) stage_record_bwd(a.frags, j + 2, lds0, wave, voff);
-    }
+    // Dropout: odd chunks first request the bit word of the NEXT pair (its predecessor was read into a register in chunk j - 1): in front of the pieces,
+    // so "at most six outstanding" at this chunk's end covers it.  The word travels by LDS-DMA like the pieces because loads of one kind complete in
+    // order, and a load that returns to a register does not keep that order against them: until round 6 the word was such a load under a counted
+    // wait, and occasionally stale at B = 128 x 2048 (run-to-run differences of 2e-3 in every gradient below the first block's;
+    // tools/soak_train_streams.py with dropout).  LDS-DMA pieces among themselves, and stores against them, keep the counted waits valid.
+    if (DROP && (j & 1) && j + 1 < NCHUNK) dma256(dmt + ((j + 1) >> 1) * 64, lane * 4, lds0 + TAB_GB3 + wave * 256);
+    if (j + 2 < NCHUNK) stage_record_bwd(a.frags, j + 2, lds0, wave, voff);
     const uint4 *fr = reinterpret_cast<const uint4 *>(ff_smem + (j % NBUF) * BUF_BYTES) + lane;
     const uint4 *fs0 = fr - lane + w1_slot(lane, 0), *fs1 = fr - lane + w1_slot(lane, 1);
-    auto frag = [&](int t, int u) -> uint4 { return (t < T_W2 ? (u ? fs1 : fs0) : fr)[(lt<BWD>(t) * 2 + u) * 64]; };   // (W1a / W1g: w1_slot)
+    // LDS tile index of pack tile t: W2^T sits behind W1a | W1g in the slot (stage_record_bwd); W1a / W1g through w1_slot
+    auto frag = [&](int t, int u) -> uint4 { return (t < T_W2 ? (u ? fs1 : fs0) : fr)[((t >= T_W2T ? t - 4 : t) * 2 + u) * 64]; };
     // ---- [a | g] = b1 + W1 xn3 ----
     v16f av, gv;
     load16(av, b1s + ((j * 2 + 0) * 2 + hf) * 16);
     load16(gv, b1s + ((j * 2 + 1) * 2 + hf) * 16);
-    if (!BWD) {
-      // Forward: the chunk's 24 A fragments go through a ring of eight registers (the sampling kernel's scheme): MFMA m takes P[m & 7],
-      // which is refilled in place with fragment m + 8 — GEMM2's eight W2 fragments are requested during GEMM1's second half and have
-      // landed long before the GELU is done.  One exposed LDS round trip per chunk; left to itself hipcc requested every fragment one
-      // or two MFMAs ahead of its use and waited for it (lgkmcnt(0 / 1) in front of nearly every MFMA).
-      // GEMM1 MFMA m: k-tile c = m >> 2, unit u = (m >> 1) & 1, a / g = m & 1;  GEMM2 MFMA i: row tile ct = i & 3, unit u = i >> 2
-      auto f1 = [&](int m) -> uint4 { return frag(((m & 1) ? T_W1G : T_W1A) + (m >> 2), (m >> 1) & 1); };
-      auto f2 = [&](int i) -> uint4 { return frag(T_W2 + (i & 3), i >> 2); };
-      uint4 P[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) P[i] = f1(i);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int m = 0; m < 16; ++m) {
-        if (m & 1) gv = mfma(P[m & 7], xn[m >> 2][(m >> 1) & 1], gv);
-        else av = mfma(P[m & 7], xn[m >> 2][(m >> 1) & 1], av);
-        P[m & 7] = m + 8 < 16 ? f1(m + 8) : f2(m + 8 - 16);
-      }
-#pragma unroll
-      for (int m = 0; m < 16; ++m) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      v16f hv;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) set_pair(hv, i, pair(av, i) * gelu_f2(pair(gv, i)));
-      if (DROP) {
-        // dropout behind the GEGLU (attention.py:84): element (row, unit 32 j + 8 q + 4 hf + m) = group row * 64 + 4 j + q of the site; the scale rides on `a`
-        unsigned w[4][2];
-        drop_words(a.dk, a.site_ff, prow * (FH / 8) + 4 * j, hf, w);
-        const unsigned bits = drop_apply(hv, w, a.dk.thr);
-        dmw = (j & 1) ? dmw | (bits << 16) : bits;
-        if ((j & 1) && live) dmk[(j >> 1) * 64] = dmw;   // (a store in flight only tightens the counted waits below: operations complete in order)
-      }
-      const uint4 h0 = pack8(hv, 0), h1 = pack8(hv, 1);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) acc[i & 3] = mfma(P[i], (i >> 2) ? h1 : h0, acc[i & 3]);
-    } else {
-      // Backward, first burst: GEMM1 recompute (16 MFMAs) and d hid = W2^T dh (8) are independent of each other — one stream of 24
-      // MFMAs through the same ring of eight fragment registers (one exposed LDS round trip).
+    {
+      // First burst: GEMM1 recompute (16 MFMAs) and d hid = W2^T dh (8) are independent of each other — one stream of 24 MFMAs through a ring of
+      // eight fragment registers (the sampling kernel's scheme: MFMA m takes P[m & 7], which is refilled in place with fragment m + 8; one exposed
+      // LDS round trip.  Left to itself hipcc requested every fragment one or two MFMAs ahead of its use and waited for it)
       auto f1 = [&](int m) -> uint4 {
         return m < 16 ? frag(((m & 1) ? T_W1G : T_W1A) + (m >> 2), (m >> 1) & 1) : frag(T_W2T + ((m - 16) >> 1), (m - 16) & 1);
       };
@@ -1129,8 +897,8 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    // chunk j + 1 (and, backward, an odd chunk's bit word) must have landed: loads complete in order, so "at most PIECES outstanding" leaves only
-    // chunk j + 2's six pieces (whatever the order between loads and the backward's stores); no new pieces in the last two iterations -> drain
+    // chunk j + 1 (and an odd chunk's bit word) must have landed: loads complete in order, so "at most PIECES outstanding" leaves only
+    // chunk j + 2's six pieces (whatever the order between loads and the stores); no new pieces in the last two iterations -> drain
     FFT(13);
     if (j + 2 < NCHUNK) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PIECES) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1139,75 +907,8 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
     FFT(15);
   }
   FFT(3);
-  if (!BWD) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) hc[c] = acc[c];   // (dead in the single-block kernel)
-    if (a.tiled & TL_HEAD) {
-      // post_norm + proj_out on the accumulators (two-pass statistics like k_head_fwd's ln_row); xhat replaces h2 in acc
-      float sm = 0.f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sm += acc[c][r];
-      sm += xhalf(sm);
-      const float mup = sm * (1.0f / C);
-      float qs = 0.f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float d = acc[c][r] - mup;
-          qs = fmaf(d, d, qs);
-        }
-      qs += xhalf(qs);
-      const float rstdp = 1.0f / sqrtf(qs * (1.0f / C) + LN_EPS);
-      float e0 = 0.f, e1 = 0.f, e2 = 0.f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int ch = 32 * c + 8 * q + 4 * hf;
-          const v4f w0 = *reinterpret_cast<const v4f *>(a.head_tab + ch), w1 = *reinterpret_cast<const v4f *>(a.head_tab + C + ch);
-          const v4f w2 = *reinterpret_cast<const v4f *>(a.head_tab + 2 * C + ch);
-#pragma unroll
-          for (int m = 0; m < 4; ++m) {
-            const float xh = (acc[c][4 * q + m] - mup) * rstdp;
-            acc[c][4 * q + m] = xh;
-            e0 = fmaf(xh, w0[m], e0), e1 = fmaf(xh, w1[m], e1), e2 = fmaf(xh, w2[m], e2);
-          }
-        }
-      e0 += xhalf(e0), e1 += xhalf(e1), e2 += xhalf(e2);
-      if (!live) return;
-      if (hf == 0) {
-        float *ep = a.eps + (size_t)s * 3 * a.N + ti * 32 + pj;
-        ep[0] = e0 + a.head_tab[3 * C], ep[a.N] = e1 + a.head_tab[3 * C + 1], ep[2 * (size_t)a.N] = e2 + a.head_tab[3 * C + 2];
-        (a.h2 + rowbase)[H1F_RSTD + pj] = rstdp;
-      }
-      uint4 *hp = reinterpret_cast<uint4 *>(a.h2 + rowbase) + lane;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        uint4 hb[2];
-        acc_to_frags(acc[c], hb);
-        hp[(c * 2 + 0) * 64] = hb[0], hp[(c * 2 + 1) * 64] = hb[1];
-      }
-      FFT(9);
-      FFT_COUNT(trace_n);
-      return;
-    }
-    FFT_COUNT(trace_n);
-    if (!live) return;
-    float *out = a.h2 + rowbase;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<v4f *>(out + m_h2.a(c, q)) = v4f{acc[c][4 * q], acc[c][4 * q + 1], acc[c][4 * q + 2], acc[c][4 * q + 3]};
-    FFT(9);
-    FFT_COUNT(trace_n);
-    return;
-  }
-  // ---- backward epilogue.  The ring is idle (every wave is behind the loop's last barrier): the shape's [A_s | M_s^T | A_s^T] fragments are
-  // requested into it first, then the second reads of h1 and dh (accumulator layout) as one batch ----
+  // ---- epilogue.  The ring is idle (every wave is behind the loop's last barrier): the shape's [A_s | M_s^T | A_s^T] fragments are
+  // requested into it first, then the second read of dh (accumulator layout) as one batch ----
   if (at) {
     const char *src = reinterpret_cast<const char *>(a.at_frags + (size_t)s * SHAPE_U4);
 #pragma unroll
@@ -1235,7 +936,13 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
         }
       }
   } else {
-    load_rows_acc(a.dh + rowbase, m_dh, dv);
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const v4f t = *reinterpret_cast<const v4f *>(a.dh + rowbase + m_dh.a(c, q));
+        dv[c][4 * q + 0] = t[0], dv[c][4 * q + 1] = t[1], dv[c][4 * q + 2] = t[2], dv[c][4 * q + 3] = t[3];
+      }
   }
   unsigned attw[2] = {0, 0};
   if (DROP && at) attw[0] = dmk[8 * 64], attw[1] = dmk[9 * 64];   // the to_out site's bits of this tile (same batch of loads)
@@ -1284,7 +991,7 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
     t += xhalf(t);
     if (hf == 0) cred[(wave * NQ + which) * C + 32 * c + pj] = t * keep;
   };
-  // dh1 replaces dh in dv, tile by tile
+  // dh1 replaces dh in dv, tile by tile (it leaves only as fragments: pk2)
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     colsum(dv[c], 2, c);
@@ -1302,7 +1009,7 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
   }
   FFT(5);
   if (at) {
-    // ---- the attention sub-block's input gradient on the same rows (afused::k_attn_bwd_dx's arithmetic): recompute LN2 / sim / P from hin,
+    // ---- the attention sub-block's input gradient on the same rows: recompute LN2 / sim / P from hin,
     // dP = M_s^T dh1, softmax backward, dxn2 = A_s^T dsim, LayerNorm2 backward: dh_in = dh1 + ... ; column sums for d gamma2, d beta2, d b_o ----
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the attention fragments (requested a phase ago)
     __syncthreads();
@@ -1336,7 +1043,7 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
     }
     FFT(6);
     {
-      // LayerNorm2 of hin (ln_rows' arithmetic), a fragment at a time: xhat2 replaces the row in place, the affine bf16 fragment goes to
+      // LayerNorm2 of hin (ln_stats' / ln_frag's arithmetic), a fragment at a time: xhat2 replaces the row in place, the affine bf16 fragment goes to
       // k_attn_bwd_param and into sim = A_s xn2 straight away (no 32-register array of fragments beside the rows)
       float sm = 0.f;
 #pragma unroll
@@ -1458,7 +1165,7 @@ __device__ __forceinline__ void ff_run(const FfArgs &a, const bool first, v16f (
 //     are dead once converted);
 //   * in the chain, the NEXT block's tables, attention fragments and first two records are requested behind this block's last barrier, in front of
 //     its row stores (`next` / `has_next` / `staged`): the next block's first wait finds most of them landed.
-// Same rows, same tile layouts, same dropout bits as ff_run<false>; the attention sub-block and LayerNorm3 are its code.
+// Same rows, same tile layouts, same dropout bits as round 5's unskewed forward body, whose attention sub-block and LayerNorm3 these are.
 template <bool DROP>
 __device__ __forceinline__ void ff_fwd(const FfArgs &a, const FfArgs &next, const bool has_next, const bool first, const bool staged, v16f (&hc)[4], float (&tv)[3],
                                        int &trace_n) {
@@ -1467,7 +1174,7 @@ __device__ __forceinline__ void ff_fwd(const FfArgs &a, const FfArgs &next, cons
   constexpr int BUF_BYTES = FWD_TILES * 2048, PIECES = FWD_TILES * 2 / NW;
   extern __shared__ __attribute__((aligned(1024))) unsigned char ff_smem[];
   int lane_ = threadIdx.x & 63;
-  asm volatile("" : "+v"(lane_));   // (opaque per call: see ff_run)
+  asm volatile("" : "+v"(lane_));   // (opaque per call: in the chain hipcc otherwise hoists every lane-derived offset out of the block loop and keeps ~40 registers alive)
   const int lane = lane_, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int hf = lane >> 5, pj = lane & 31;
   const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)ff_smem);
@@ -1527,7 +1234,7 @@ __device__ __forceinline__ void ff_fwd(const FfArgs &a, const FfArgs &next, cons
   uint4 xn[4][2];
   float mu, rstd;
   {
-    // ---- attention sub-block in registers (ff_run<false>'s code): h1 = hin + [dropout] (M_s softmax(A_s LN2(hin)) + b_o) ----
+    // ---- attention sub-block in registers: h1 = hin + [dropout] (M_s softmax(A_s LN2(hin)) + b_o) ----
     const uint4 *fl = reinterpret_cast<const uint4 *>(ff_smem + 2 * BUF_BYTES) + lane;
     v16f sim = zero16();
     {
@@ -1696,7 +1403,7 @@ __device__ __forceinline__ void ff_fwd(const FfArgs &a, const FfArgs &next, cons
 #pragma unroll
   for (int c = 0; c < 4; ++c) hc[c] = acc[c];
   if (a.tiled & TL_HEAD) {
-    // post_norm + proj_out on the accumulators (ff_run<false>'s code)
+    // post_norm + proj_out on the accumulators (two-pass statistics)
     float sm = 0.f;
 #pragma unroll
     for (int c = 0; c < 4; ++c)
@@ -1760,24 +1467,13 @@ __device__ __forceinline__ void ff_fwd(const FfArgs &a, const FfArgs &next, cons
   FFT_COUNT(trace_n);
 }
 
-template <bool BWD, bool DROP>
-__global__ __launch_bounds__(nw_of<BWD>() * 64, 2) void k_ff(FfArgs a) {
-  v16f hc[4];
-  int tn = 0;
-  if constexpr (!BWD) {
-    if (a.at_frags) {   // (the attention sub-block inside: every shipped launch; dfx_debug_train_fused(2) keeps the round-5 body)
-      float tv[3];
-      ff_fwd<DROP>(a, a, false, true, false, hc, tv, tn);
-      return;
-    }
-  }
-  ff_run<BWD, DROP>(a, true, hc, tn);
-}
+template <bool DROP>
+__global__ __launch_bounds__(NW_BWD * 64, 2) void k_ff_bwd(FfArgs a) { ff_bwd<DROP>(a); }
 // The forward of ALL blocks in one launch (round 5): a point's way through the network depends on no other point (the attention's keys / values are the
 // four context tokens, folded into A_s / M_s), so a wavefront takes its 32 points through block after block with the residual stream in its accumulator
 // registers — as the sampling kernel does.  Every block still WRITES its output rows (the backward recomputes LayerNorm2 from them), but nobody reads them
 // back in the forward: 512 B per point and block less traffic, and the prologue's wait for the rows (a quarter of a single-block workgroup's life) is
-// paid once.  Same arithmetic on the same values as five launches of k_ff<false>: bit-identical.
+// paid once.  Same arithmetic on the same values as one launch per block (n = 1, the phase-trace build's): bit-identical.
 struct FfChain {
   FfArgs blk[DFX_MAX_DEPTH];
   int n;
@@ -1796,7 +1492,7 @@ __global__ __launch_bounds__(NW_FWD * 64, 2) void k_ff_fwd_chain(FfChain ch) {
 // Weight gradients of the feed-forward, weight-stationary:  dW1 = d[a | g]^T xn3 (1024 x 128),  dW2 = dh^T hid (128 x 512),
 // d b1 = column sums of d[a | g].  A 32-unit chunk of the hidden layer for a slab of rows belongs to TWO wavefronts on one SIMD: the
 // producer keeps the chunk's W1a / W1g / W2 fragments (96 registers), the consumer its twelve 32 x 32 gradient tiles (192 accumulator
-// registers), while the slab's 32-point tiles stream by (16 KiB each, written by k_ff<true>, L2 -> LDS with LDS-DMA, shared by the
+// registers), while the slab's 32-point tiles stream by (16 KiB each, written by k_ff_bwd, L2 -> LDS with LDS-DMA, shared by the
 // workgroup's four chunks).  Everything with the chunk's units on the lanes and the 32 points along the registers (the transposed
 // orientation: activations as the A operand, weights as B):
 //     producer   a^T, g^T = xn3 W1^T + b1 (16 MFMAs)   d hid^T = dh W2 (8)   GEGLU forward / backward on the registers -> 6 fragments in LDS
@@ -1806,14 +1502,14 @@ __global__ __launch_bounds__(NW_FWD * 64, 2) void k_ff_fwd_chain(FfChain ch) {
 struct FwArgs {
   const uint4 *frags;    // the k_ff_pack fragments: tiles T_W1A, T_W1G, T_W2T of each chunk are this kernel's B operands
   const float *b1;       // (1024) the FOLDED bias PackArgs::b1f (b1 + W1 beta3, `a` half times keep_a)
-  const uint4 *pk;       // [R / 32][2][4][2][64]: set PK_XN = the xhat3 fragments (k_ff<true>'s pk, or the forward's h1 tiles, TL_H1_FRAG: same place in the tile)
+  const uint4 *pk;       // [R / 32][2][4][2][64]: set PK_XN = the xhat3 fragments (the forward's h1 tiles, TL_H1_FRAG)
   float *part;           // [nslab][NCHUNK][12][16][64] fp32 gradient tiles in accumulator layout
   float *bpart;          // [nslab][NCHUNK][2][32] column sums of da, dg
   long long ntiles;      // R / 32
   int nslab;
   const unsigned *dmask; // k_ff_wgrad<true>: the forward's dropout bits (FfArgs::dmask); words 0 .. 7 of a tile (2 KiB) travel with the tile
   const uint4 *dhf;      // the dh fragments: tiles of 16 KiB whose FIRST 8 KiB they are — the block's incoming gradient as bf16-pair tiles (TL_DH_HL: the hi
-                         // halves), or k_ff<true>'s pk + the offset of its PK_DH set
+                         // halves)
 #ifdef DFX_TRACE_FF
   unsigned long long *trace;
 #endif
@@ -1823,7 +1519,7 @@ constexpr int WG_CHUNKS = 4, WG_NW = 2 * WG_CHUNKS;   // two wavefronts per chun
 // is longer than one tile's arithmetic); the consumers turn tile k around (two MFMAs with a 0/1 selection matrix per 32 x 32 tile, exact)
 // into one of two 16 KiB slots while they multiply tile k - 1
 // Round 6, measured and dropped: the consumers reading the turned operands straight out of the ring's tile with the LDS transpose read (ds_read_b64_tr_b16, as
-// k_ff<true>'s second product does; a ring of four slots, no selection MFMAs, no turned slots).  Bit-identical, 0 bank conflicts — and 2.3 % SLOWER
+// k_ff_bwd's second product does; a ring of four slots, no selection MFMAs, no turned slots).  Bit-identical, 0 bank conflicts — and 2.3 % SLOWER
 // (alternating same-box runs 225.0 / 226.0 against 230.0 / 231.7 us per block, profiles/r06_ab_train_wgrad_tr.txt): the turning is shared by the four consumers
 // (each turns a quarter, all read 16 whole fragments back with ds_read_b128), the transpose read doubled every consumer's read instructions in front of its
 // MFMAs, and the producer, not the consumer, is this kernel's critical wavefront.
@@ -2144,21 +1840,19 @@ inline void launch_pack(hipStream_t st, PackBatch &b, int depth) {
   b.depth = depth;
   k_ff_pack<<<dim3((total + 255) / 256, depth + (b.head_tab ? 1 : 0)), 256, 0, st>>>(b);
 }
-// workgroups of k_ff<*> (= rows of the backward's column-sum partials): one shape per workgroup
+// workgroups of k_ff_fwd_chain / k_ff_bwd (= rows of the backward's column-sum partials): one shape per workgroup
 inline long long ff_groups(int B, int N) { return (long long)B * ((N / 32 + NW_BWD - 1) / NW_BWD); }
-template <bool BWD, bool DROP>
-inline int launch_ff_t(hipStream_t st, const FfArgs &a) {
-  constexpr int LDS = FF_LDS;
+template <bool DROP>
+inline int launch_ff_bwd_t(hipStream_t st, const FfArgs &a) {
   static PerDeviceOnce attrs;
-  if (attrs.run([] { return set_max_lds(reinterpret_cast<const void *>(k_ff<BWD, DROP>), LDS); }) != hipSuccess) return -1;
-  constexpr int NW = nw_of<BWD>();
+  if (attrs.run([] { return set_max_lds(reinterpret_cast<const void *>(k_ff_bwd<DROP>), FF_LDS); }) != hipSuccess) return -1;
   const long long groups = ff_groups(a.B, a.N);
 #ifdef DFX_TRACE_FF
   FfArgs at = a;
   at.trace = ff_trace_buffer();
-  k_ff<BWD, DROP><<<(int)groups, NW * 64, LDS, st>>>(at);
+  k_ff_bwd<DROP><<<(int)groups, NW_BWD * 64, FF_LDS, st>>>(at);
 #else
-  k_ff<BWD, DROP><<<(int)groups, NW * 64, LDS, st>>>(a);
+  k_ff_bwd<DROP><<<(int)groups, NW_BWD * 64, FF_LDS, st>>>(a);
 #endif
   return 0;
 }
@@ -2177,9 +1871,8 @@ inline int launch_ff_chain_t(hipStream_t st, const FfChain &c) {
   return 0;
 }
 inline int launch_ff_chain(hipStream_t st, const FfChain &c) { return c.blk[0].dmask ? launch_ff_chain_t<true>(st, c) : launch_ff_chain_t<false>(st, c); }
-// dropout (FfArgs::dmask set) takes the DROP instantiations; the p = 0 kernels are the ones of round 4, untouched
-template <bool BWD>
-inline int launch_ff(hipStream_t st, const FfArgs &a) { return a.dmask ? launch_ff_t<BWD, true>(st, a) : launch_ff_t<BWD, false>(st, a); }
+// dropout (FfArgs::dmask set) takes the DROP instantiations
+inline int launch_ff_bwd(hipStream_t st, const FfArgs &a) { return a.dmask ? launch_ff_bwd_t<true>(st, a) : launch_ff_bwd_t<false>(st, a); }
 
 }  // namespace ffused
 }  // namespace dfx

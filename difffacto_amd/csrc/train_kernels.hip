@@ -738,35 +738,13 @@ __global__ __launch_bounds__(256) void k_stem_bwd(const float *__restrict__ dy, 
   }
   for (int i = threadIdx.x; i < 2048; i += 256) part[(size_t)blockIdx.x * 2048 + i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
 }
-__device__ __forceinline__ void ln_row(const float *__restrict__ xrow, int l, v4f &xh, float &rstd) {
-  const v4f v = reinterpret_cast<const v4f *>(xrow)[l];
-  const float mu = sum32(v[0] + v[1] + v[2] + v[3]) * (1.0f / C);
-  const v4f d = {v[0] - mu, v[1] - mu, v[2] - mu, v[3] - mu};
-  rstd = 1.0f / sqrtf(sum32(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]) * (1.0f / C) + LN_EPS);
-  xh = d * rstd;
-}
-__global__ __launch_bounds__(256) void k_head_fwd(const float *__restrict__ hfin, const float *__restrict__ g, const float *__restrict__ be,
-                                                   const float *__restrict__ W, const float *__restrict__ bias, float *__restrict__ eps, int N, long long R) {
-  const int l = threadIdx.x & 31, grp = threadIdx.x >> 5;
-  const v4f gv = reinterpret_cast<const v4f *>(g)[l], bv = reinterpret_cast<const v4f *>(be)[l];
-  const v4f w0 = reinterpret_cast<const v4f *>(W)[l], w1 = reinterpret_cast<const v4f *>(W + C)[l], w2 = reinterpret_cast<const v4f *>(W + 2 * C)[l];
-  for (long long r = (long long)blockIdx.x * 8 + grp; r < R; r += (long long)gridDim.x * 8) {
-    v4f xh;
-    float rstd;
-    ln_row(hfin + r * C, l, xh, rstd);
-    const v4f hn = xh * gv + bv;
-    const float s0 = sum32(hn[0] * w0[0] + hn[1] * w0[1] + hn[2] * w0[2] + hn[3] * w0[3]);
-    const float s1 = sum32(hn[0] * w1[0] + hn[1] * w1[1] + hn[2] * w1[2] + hn[3] * w1[3]);
-    const float s2 = sum32(hn[0] * w2[0] + hn[1] * w2[1] + hn[2] * w2[2] + hn[3] * w2[3]);
-    if (l < 3) eps[((r / N) * 3 + l) * N + (r % N)] = (l == 0 ? s0 : l == 1 ? s1 : s2) + bias[l];
-  }
-}
 // part[block] = [d W_out (3 x 128) | d gamma (128) | d beta (128) | d b_out (3) | 0 x 29] = 672 floats
 constexpr int HEAD_PART = 672;
 __global__ __launch_bounds__(256) void k_head_bwd(const float *__restrict__ deps, const float *__restrict__ hfin, const float *__restrict__ g,
                                                    const float *__restrict__ be, const float *__restrict__ W, float *__restrict__ dh,
-                                                   float *__restrict__ part, int N, long long R, bool hl) {
-  // hl: dh leaves as the bf16-pair tiles the fused backward kernels pass between the blocks (train_ff_fused.h, TL_DH_HL) instead of fp32 rows
+                                                   float *__restrict__ part, int N, long long R) {
+  // hfin: what the last block's forward kernel left of it (train_ff_fused.h, TL_HEAD); dh leaves as the bf16-pair tiles the fused backward kernels
+  // pass between the blocks (TL_DH_HL's format)
   __shared__ float red[8][HEAD_PART];
   const int l = threadIdx.x & 31, grp = threadIdx.x >> 5;
   const v4f gv = reinterpret_cast<const v4f *>(g)[l], bv = reinterpret_cast<const v4f *>(be)[l];
@@ -779,18 +757,13 @@ __global__ __launch_bounds__(256) void k_head_bwd(const float *__restrict__ deps
     const long long bb = r / N;
     const int n = (int)(r % N);
     const float d0 = deps[(bb * 3 + 0) * N + n], d1 = deps[(bb * 3 + 1) * N + n], d2 = deps[(bb * 3 + 2) * N + n];
-    v4f xh;
-    float rstd;
-    if (!hl) {
-      ln_row(hfin + r * C, l, xh, rstd);
-    } else {   // the last block's forward kernel left the normalised row as bf16 fragments + 1 / std (train_ff_fused.h, TL_HEAD): this thread's four channels
-      const char *tile = reinterpret_cast<const char *>(hfin + (r & ~31LL) * C);
-      const int pj = (int)(r & 31), c = l >> 3;
-      const uint2 hv = *reinterpret_cast<const uint2 *>(tile + ((c * 2 + ((l >> 2) & 1)) * 64 + pj + 32 * ((l >> 1) & 1)) * 16 + 8 * (l & 1));
-      xh = v4f{__builtin_bit_cast(float, hv.x << 16), __builtin_bit_cast(float, hv.x & 0xffff0000u), __builtin_bit_cast(float, hv.y << 16),
-               __builtin_bit_cast(float, hv.y & 0xffff0000u)};
-      rstd = reinterpret_cast<const float *>(tile)[dfx::ffused::H1F_RSTD + pj];
-    }
+    // the normalised row as bf16 fragments + 1 / std: this thread's four channels
+    const int pj = (int)(r & 31), c = l >> 3;
+    const char *htile = reinterpret_cast<const char *>(hfin + (r & ~31LL) * C);
+    const uint2 hv = *reinterpret_cast<const uint2 *>(htile + ((c * 2 + ((l >> 2) & 1)) * 64 + pj + 32 * ((l >> 1) & 1)) * 16 + 8 * (l & 1));
+    const v4f xh = {__builtin_bit_cast(float, hv.x << 16), __builtin_bit_cast(float, hv.x & 0xffff0000u), __builtin_bit_cast(float, hv.y << 16),
+                    __builtin_bit_cast(float, hv.y & 0xffff0000u)};
+    const float rstd = reinterpret_cast<const float *>(htile)[dfx::ffused::H1F_RSTD + pj];
     const v4f hn = xh * gv + bv;
     const v4f dhn = d0 * w0 + d1 * w1 + d2 * w2;
     a0 += d0 * hn, a1 += d1 * hn, a2 += d2 * hn;
@@ -800,20 +773,16 @@ __global__ __launch_bounds__(256) void k_head_bwd(const float *__restrict__ deps
     const float s1 = sum32(dyg[0] + dyg[1] + dyg[2] + dyg[3]) * (1.0f / C);
     const float s2 = sum32(dyg[0] * xh[0] + dyg[1] * xh[1] + dyg[2] * xh[2] + dyg[3] * xh[3]) * (1.0f / C);
     const v4f o = rstd * (dyg - s1 - xh * s2);
-    if (!hl) {
-      reinterpret_cast<v4f *>(dh + r * C)[l] = o;
-    } else {
-      // this thread's channels 4 l .. 4 l + 3 of point pj = r % 32: hi = element 4 (l & 1) .. of block (c, u) = (l >> 3, (l >> 2) & 1), half-wave (l >> 1) & 1;
-      // lo = registers 4 q .. 4 q + 3, q = (l >> 1) & 3, of accumulator tile c in half-wave l & 1 (block (c, q >> 1), second half of the tile)
-      typedef __bf16 v4bf __attribute__((ext_vector_type(4)));
-      const v4bf hi = __builtin_convertvector(o, v4bf);
-      const v4f rem = o - __builtin_convertvector(hi, v4f);
-      const v4bf lo = __builtin_convertvector(rem, v4bf);
-      char *tile = reinterpret_cast<char *>(dh + (r & ~31LL) * C);
-      const int pj = (int)(r & 31), c = l >> 3, q = (l >> 1) & 3;
-      *reinterpret_cast<uint2 *>(tile + ((c * 2 + ((l >> 2) & 1)) * 64 + pj + 32 * ((l >> 1) & 1)) * 16 + 8 * (l & 1)) = __builtin_bit_cast(uint2, hi);
-      *reinterpret_cast<uint2 *>(tile + 8192 + ((c * 2 + (q >> 1)) * 64 + pj + 32 * (l & 1)) * 16 + 8 * (q & 1)) = __builtin_bit_cast(uint2, lo);
-    }
+    // this thread's channels 4 l .. 4 l + 3 of point pj = r % 32: hi = element 4 (l & 1) .. of block (c, u) = (l >> 3, (l >> 2) & 1), half-wave (l >> 1) & 1;
+    // lo = registers 4 q .. 4 q + 3, q = (l >> 1) & 3, of accumulator tile c in half-wave l & 1 (block (c, q >> 1), second half of the tile)
+    typedef __bf16 v4bf __attribute__((ext_vector_type(4)));
+    const v4bf hi = __builtin_convertvector(o, v4bf);
+    const v4f rem = o - __builtin_convertvector(hi, v4f);
+    const v4bf lo = __builtin_convertvector(rem, v4bf);
+    char *tile = reinterpret_cast<char *>(dh + (r & ~31LL) * C);
+    const int q = (l >> 1) & 3;
+    *reinterpret_cast<uint2 *>(tile + ((c * 2 + ((l >> 2) & 1)) * 64 + pj + 32 * ((l >> 1) & 1)) * 16 + 8 * (l & 1)) = __builtin_bit_cast(uint2, hi);
+    *reinterpret_cast<uint2 *>(tile + 8192 + ((c * 2 + (q >> 1)) * 64 + pj + 32 * (l & 1)) * 16 + 8 * (q & 1)) = __builtin_bit_cast(uint2, lo);
   }
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -1740,7 +1709,10 @@ size_t carve(TrainWs &w, void *base, int B, int N, int depth) {
   for (int i = 0; i < depth; ++i) {
     w.at_part[i] = c.take<float>((size_t)B * w.at_split * 2 * dfx::afused::HJ * C);
     w.at_sum[i] = c.take<float>((size_t)B * 2 * dfx::afused::HJ * C);
-    const size_t groups = (size_t)dfx::ffused::ff_groups(B, N), a = groups * 6 * C, b = (size_t)dfx::afused::dx_groups((long long)R) * 3 * C;
+    // (b: what the retired separate attention-gradient kernel's partials took — min(ceil(R / 128), 1024) rows of 3 C; it still bounds the size
+    // from below, so that every later buffer keeps its offset)
+    const long long dxg = (R / 32 + 3) / 4;
+    const size_t groups = (size_t)dfx::ffused::ff_groups(B, N), a = groups * 6 * C, b = (size_t)(dxg < 1024 ? dxg : 1024) * 3 * C;
     w.cpart[i] = c.take<float>(a > b ? a : b);
     w.ffw_part[i] = c.take<float>((size_t)w.ffw_slabs * dfx::ffused::NCHUNK * 12 * 1024);
     w.ffw_bpart[i] = c.take<float>((size_t)w.ffw_slabs * dfx::ffused::NCHUNK * 64);
@@ -1755,15 +1727,14 @@ size_t carve(TrainWs &w, void *base, int B, int N, int depth) {
   return c.off;
 }
 
-// Fused feed-forward kernels (train_ff_fused.h) for bf16 products without dropout; dfx_debug_train_fused(0) restores the
+// Fused feed-forward kernels (train_ff_fused.h) for bf16 products; dfx_debug_train_fused(0) restores the
 // layer-by-layer path (A/B timing, and the reference for the fused path's own test).
 bool g_ff_fused = true;
-bool g_attn_in_ff = true;   // (debug: 2 in dfx_debug_train_fused keeps the attention forward as a kernel of its own)
 // Fused path: the context branch of the forward (time-embedding MLP, keys / values, attention folds) and the parameter-gradient
 // reductions of the backward run on the device's side stream (dfx::SideStream) beside the kernels over the points: they are chains of
 // small-grid launches that leave most of the chip idle.  Same kernels, same operands, same results; dfx_debug_train_streams(0) = one stream.
 int g_train_streams = 1;   // 0 = off, 1 = the default set, other values = explicit set of SS_* bits (train_plan.h; A/B)
-// These three are the debug switches' storage, read only where a plan is made (train_plan.h: plan_train, plan_train_streams).  The PATH is
+// These two are the debug switches' storage, read only where a plan is made (train_plan.h: plan_train, plan_train_streams).  The PATH is
 // planned ONCE per step, by the forward, and recorded per workspace on the host: the backward follows the record, not the switches, so
 // toggling dfx_debug_train_fused between a forward and its backward (the A/B tests do) cannot pair a fused backward with the activations
 // of a layer-by-layer forward.  The side-stream decisions are planned from the live switch by each call.
@@ -2298,9 +2269,8 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
     return dfx::check_launch("denoiser_train_forward");
   }
 
-  int forward_fused(const TrainFwdIo &io) {   // Fused, FusedSplitAttn
+  int forward_fused(const TrainFwdIo &io) {   // Fused
     int rc;
-    const bool split = plan.path == dfx::TrainPath::FusedSplitAttn;   // the attention forward as a kernel of its own, single-block launches, k_head_fwd
     // Two branches meet in front of the first block: the points (input rows, proj_in + pre_norm, the blocks' weight fragments) on the caller's
     // stream, the context (time embedding -> context rows -> keys / values of every block -> folded attention operands) on the side stream
     dfx::SideStream ss;
@@ -2325,8 +2295,8 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
       pb.blk[i] = dfx::ffused::PackArgs{wt->blk[i].ff0_w, wt->blk[i].ff0_b, wt->blk[i].ff2_w, wt->blk[i].ff2_b, w.ff_frags[i], w.ff_b1p[i], w.ff_b2p[i],
                                         dropout_p > 0.f ? 1.0f / (1.0f - dropout_p) : 1.0f, wt->blk[i].norm3_w, wt->blk[i].norm3_b,
                                         w.ff_b1p[i] + dfx::ffused::B1P_FLOATS, w.ff_b1p[i] + 2 * dfx::ffused::B1P_FLOATS};
-    if (!split)   // + the head's table: the last block's forward kernel computes eps itself
-      pb.head_w = wt->proj_out_w, pb.head_b = wt->proj_out_b, pb.head_g = wt->post_norm_w, pb.head_be = wt->post_norm_b, pb.head_tab = w.head_tab;
+    // + the head's table: the last block's forward kernel computes eps itself
+    pb.head_w = wt->proj_out_w, pb.head_b = wt->proj_out_b, pb.head_g = wt->post_norm_w, pb.head_be = wt->post_norm_b, pb.head_tab = w.head_tab;
     dfx::ffused::launch_pack(st, pb, wt->depth);
     // keys and values of every block: one product over the B x 4 context tokens
     if ((rc = lin(sc, plan.prec, w.ctx, CTXP, w.wkv, nullptr, w.kv, LDKV, BJ, LDKV, CTXP))) return rc;
@@ -2335,45 +2305,37 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
     for (int i = 0; i < wt->depth; ++i) fo.wq[i] = wt->blk[i].to_q, fo.wo[i] = wt->blk[i].to_out_w, fo.frags[i] = w.at_frags[i];
     dfx::afused::k_attn_fold<<<dim3(B, wt->depth), 256, 0, sc>>>(fo);
     if ((rc = ss.join())) return rc;
+    // All blocks in one launch (k_ff_fwd_chain; train_attn_fused.h, train_ff_fused.h): h1 = hin + attention(LN2(hin)), hout = h1 + FF(LN3(h1));
+    // q, P, att, xn2, xn3, [a | g], hid never exist in memory
     dfx::ffused::FfChain chain{};
+    chain.n = wt->depth;
     for (int i = 0; i < wt->depth; ++i) {
       const dfx_block_weights &bw = wt->blk[i];
       BlockAct &a = w.blk[i];
-      float *hout = i + 1 < wt->depth ? w.blk[i + 1].hin : w.hfin;
-      // the whole block in two launches (train_attn_fused.h, train_ff_fused.h): h1 = hin + attention(LN2(hin)), hout = h1 + FF(LN3(h1));
-      // q, P, att, xn2, xn3, [a | g], hid never exist in memory
-      dfx::ffused::FfArgs fa{};
+      dfx::ffused::FfArgs &fa = chain.blk[i];
       fa.frags = w.ff_frags[i], fa.b2p = w.ff_b2p[i], fa.g3 = bw.norm3_w, fa.b3 = bw.norm3_b;
-      fa.b1p = w.ff_b1p[i] + (split ? 0 : 2 * dfx::ffused::B1P_FLOATS);   // ff_fwd's table: scaled like its W1 tiles (PackArgs::b1ps)
-      fa.h1 = a.h1, fa.h2 = hout, fa.R = R, fa.B = B, fa.N = N;
-      if (split) {
-        dfx::afused::AttnArgs aa{};
-        aa.frags = w.at_frags[i], aa.valid = w.valid, aa.g2 = bw.norm2_w, aa.b2 = bw.norm2_b, aa.bo = bw.to_out_b;
-        aa.h = a.hin, aa.h1 = a.h1, aa.N = N, aa.R = R;
-        dfx::afused::k_attn_fwd_fused<<<(int)((R / 32 + dfx::afused::NW - 1) / dfx::afused::NW), dfx::afused::NW * 64, 0, st>>>(aa);
-      } else {   // attention sub-block inside the feed-forward kernel's prologue: h1 computed from hin, written once
-        // tile-major rows between the fused kernels (train_ff_fused.h): everything but the stem's output and the head's input
-        // (+ h1 itself only as what the backward kernels want of it: the xhat3 fragments and 1 / std, TL_H1_FRAG)
-        fa.tiled = dfx::ffused::TL_H1 | (i > 0 ? dfx::ffused::TL_HIN : 0) | (i + 1 < wt->depth ? dfx::ffused::TL_H2 : 0) | dfx::ffused::TL_H1_FRAG;
-        fa.at_frags = w.at_frags[i], fa.valid = w.valid, fa.g2 = bw.norm2_w, fa.b2n = bw.norm2_b, fa.bo = bw.to_out_b;
-        fa.hin = a.hin, fa.h1_out = a.h1;
-        if (i + 1 == wt->depth) fa.tiled |= dfx::ffused::TL_HEAD, fa.head_tab = w.head_tab, fa.eps = io.eps;   // post_norm + proj_out in this kernel's epilogue
-        if (dropout_p > 0.f) {   // the two sites of block i (the layer-by-layer path's numbering); bits -> a.p (R x 32 floats, unused by the fused path; 80 B per point needed)
-          fa.dk = dfx::drop_key(dropout_seed, dropout_p), fa.site_att = (unsigned)(2 * i), fa.site_ff = (unsigned)(2 * i + 1);
-          fa.dmask = reinterpret_cast<unsigned *>(a.p);
-        }
-#if !defined(DFX_TRACE_FF) || defined(DFX_TRACE_FF_CHAIN)   // (the phase-trace build stamps single-block launches unless asked for the chain)
-        chain.blk[i] = fa;   // all blocks in ONE launch (k_ff_fwd_chain): collected here, launched behind the last one
-        if (i + 1 == wt->depth) {
-          chain.n = wt->depth;
-          if (dfx::ffused::launch_ff_chain(st, chain)) return dfx::set_error(DFX_ERR_HIP, "train: fused forward chain launch");
-        }
-        continue;
-#endif
+      fa.b1p = w.ff_b1p[i] + 2 * dfx::ffused::B1P_FLOATS;   // ff_fwd's table: scaled like its W1 tiles (PackArgs::b1ps)
+      fa.h2 = i + 1 < wt->depth ? w.blk[i + 1].hin : w.hfin, fa.R = R, fa.B = B, fa.N = N;
+      // tile-major rows between the fused kernels (train_ff_fused.h): everything but the stem's output and the head's input
+      // (+ h1 itself only as what the backward kernels want of it: the xhat3 fragments and 1 / std, TL_H1_FRAG)
+      fa.tiled = dfx::ffused::TL_H1 | (i > 0 ? dfx::ffused::TL_HIN : 0) | (i + 1 < wt->depth ? dfx::ffused::TL_H2 : 0) | dfx::ffused::TL_H1_FRAG;
+      fa.at_frags = w.at_frags[i], fa.valid = w.valid, fa.g2 = bw.norm2_w, fa.b2n = bw.norm2_b, fa.bo = bw.to_out_b;
+      fa.hin = a.hin, fa.h1_out = a.h1;
+      if (i + 1 == wt->depth) fa.tiled |= dfx::ffused::TL_HEAD, fa.head_tab = w.head_tab, fa.eps = io.eps;   // post_norm + proj_out in this kernel's epilogue
+      if (dropout_p > 0.f) {   // the two sites of block i (the layer-by-layer path's numbering); bits -> a.p (R x 32 floats, unused by the fused path; 80 B per point needed)
+        fa.dk = dfx::drop_key(dropout_seed, dropout_p), fa.site_att = (unsigned)(2 * i), fa.site_ff = (unsigned)(2 * i + 1);
+        fa.dmask = reinterpret_cast<unsigned *>(a.p);
       }
-      if (dfx::ffused::launch_ff<false>(st, fa)) return dfx::set_error(DFX_ERR_HIP, "train: fused feed-forward launch");
     }
-    if (split) k_head_fwd<<<2048, 256, 0, st>>>(w.hfin, wt->post_norm_w, wt->post_norm_b, wt->proj_out_w, wt->proj_out_b, io.eps, N, R);
+#if !defined(DFX_TRACE_FF) || defined(DFX_TRACE_FF_CHAIN)
+    if (dfx::ffused::launch_ff_chain(st, chain)) return dfx::set_error(DFX_ERR_HIP, "train: fused forward chain launch");
+#else   // (the phase-trace build stamps single-block launches unless asked for the chain: chains of one block, rows re-read from memory)
+    for (int i = 0; i < wt->depth; ++i) {
+      dfx::ffused::FfChain one{};
+      one.blk[0] = chain.blk[i], one.n = 1;
+      if (dfx::ffused::launch_ff_chain(st, one)) return dfx::set_error(DFX_ERR_HIP, "train: fused feed-forward launch");
+    }
+#endif
     return dfx::check_launch("denoiser_train_forward");
   }
 
@@ -2437,10 +2399,9 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
     return dfx::check_launch("denoiser_train_backward");
   }
 
-  int backward_fused(const TrainBwdIo &io) {   // Fused, FusedSplitAttn
+  int backward_fused(const TrainBwdIo &io) {   // Fused
     int rc;
     const int prec = plan.prec;
-    const bool split = plan.path == dfx::TrainPath::FusedSplitAttn;   // the attention's input gradient as a kernel of its own, fp32 rows between the blocks
     const dfx_denoiser_weights *grads = io.grads;
     // Parameter-gradient reductions that nothing on the way back to the input waits for run on the side stream (joined before the return):
     // the head's and the stem's partial sums — in buffers of their own (w.hn, w.datt: free on the fused path), because the products behind
@@ -2452,7 +2413,7 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
     // proj_out, post_norm
     const int nbh = (int)((R + HEAD_ROWS - 1) / HEAD_ROWS);
     float *hp = w.hn;
-    k_head_bwd<<<nbh, 256, 0, st>>>(io.d_eps, w.hfin, wt->post_norm_w, wt->post_norm_b, wt->proj_out_w, w.dh, hp, N, R, !split);
+    k_head_bwd<<<nbh, 256, 0, st>>>(io.d_eps, w.hfin, wt->post_norm_w, wt->post_norm_b, wt->proj_out_w, w.dh, hp, N, R);
     auto head_sums = [&](hipStream_t s) {
       k_sum_parts<<<3 * C / 32, 1024, 0, s>>>(hp, mut(grads->proj_out_w), nbh, 3 * C, HEAD_PART);
       k_sum_parts_multi<<<2 * C / 32, 1024, 0, s>>>(hp + 3 * C, SumOuts{{mut(grads->post_norm_w), mut(grads->post_norm_b), nullptr, nullptr}}, nbh, C, HEAD_PART);
@@ -2472,60 +2433,40 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
       k_sum_parts_multi<<<3 * C / 32, 1024, 0, s>>>(part + C * 13, SumOuts{{mut(grads->proj_in_b), mut(grads->pre_norm_w), mut(grads->pre_norm_b), nullptr}}, nb, C, 2048);
     };
     for (int i = wt->depth - 1; i >= 0; --i) {
-      const dfx_block_weights &bw = wt->blk[i], &gw = grads->blk[i];
+      const dfx_block_weights &bw = wt->blk[i];
       BlockAct &a = w.blk[i];
-      // feed-forward: h2 = h1 + W2 hid + b2, hid = a gelu(g), [a | g] = W1 xn3 + b1
-      // one pass over the points: xn3 = LN3(h1) and [a | g] recomputed, d hid = W2^T dh, GEGLU backward, dxn3 = W1^T d[a | g], LayerNorm3
-      // backward -> dh1; hid, d[a | g] and xn3 leave the kernel once, as bf16, for the two weight-gradient products
+      // feed-forward and attention sub-block, one pass over the points (k_ff_bwd): [a | g] recomputed from the xhat3 fragments the forward left,
+      // d hid = W2^T dh, GEGLU backward, dxn3 = W1^T d[a | g], LayerNorm3 backward -> dh1, the attention's input gradient -> dh_in.
+      // The gradient travels from the head through the blocks as bf16-pair tiles (train_ff_fused.h, TL_DH_HL; k_head_bwd writes the pair format
+      // too), alternating between w.dh and w.dh2 (k_ff_wgrad reads block i's INCOMING gradient after k_ff_bwd has written the outgoing one);
+      // block 0 writes the fp32 rows the stem reads (dh_cur behind the loop).  + the layouts the forward left behind
+      const float *dh_in_blk = dh_cur;
       dfx::ffused::FfArgs fa{};
       fa.frags = w.ff_frags[i], fa.b1p = w.ff_b1p[i], fa.b2p = w.ff_b2p[i], fa.g3 = bw.norm3_w, fa.b3 = bw.norm3_b;
-      fa.h1 = a.h1, fa.dh = dh_cur, fa.pk = reinterpret_cast<uint4 *>(w.dwide), fa.dh1 = w.dh2, fa.cpart = w.cpart[i], fa.R = R, fa.B = B, fa.N = N;
-      const float *dh_in_blk = dh_cur;
-      if (!split) {   // the attention's input gradient in the same kernel (dh1 leaves as fragments for the parameter kernel)
-        // The gradient travels from the head through the blocks as bf16-pair tiles (train_ff_fused.h, TL_DH_HL; k_head_bwd writes the pair format
-        // too), alternating between w.dh and w.dh2 (k_ff_wgrad reads block i's INCOMING gradient after k_ff<true> has written the outgoing one);
-        // block 0 writes the fp32 rows the stem reads (dh_cur behind the loop).  + the layouts the forward left behind
-        fa.tiled = dfx::ffused::TL_H1 | (i > 0 ? dfx::ffused::TL_HIN | dfx::ffused::TL_DHIN | dfx::ffused::TL_DHIN_HL : 0) |
-                   (i + 1 < wt->depth ? dfx::ffused::TL_DH : 0) | dfx::ffused::TL_DH_HL | dfx::ffused::TL_H1_FRAG;
-        fa.at_frags = w.at_frags[i], fa.valid = w.valid, fa.g2 = bw.norm2_w, fa.b2n = bw.norm2_b, fa.bo = bw.to_out_b;
-        fa.hin = a.hin, fa.dh_in = dh_cur = (dh_cur == w.dh ? w.dh2 : w.dh);
-        fa.pk2 = reinterpret_cast<uint4 *>(w.dq);   // xn2 / dh1 as fragments for the parameter kernel (w.dq: free in this path)
-      }
-      if (dropout_p > 0.f) {   // the bits the forward left in a.p (the plan admits dropout only with the attention inside these kernels)
+      fa.h1 = a.h1, fa.dh = dh_in_blk, fa.cpart = w.cpart[i], fa.R = R, fa.B = B, fa.N = N;
+      fa.tiled = dfx::ffused::TL_H1 | (i > 0 ? dfx::ffused::TL_HIN | dfx::ffused::TL_DHIN | dfx::ffused::TL_DHIN_HL : 0) |
+                 (i + 1 < wt->depth ? dfx::ffused::TL_DH : 0) | dfx::ffused::TL_DH_HL | dfx::ffused::TL_H1_FRAG;
+      fa.at_frags = w.at_frags[i], fa.valid = w.valid, fa.g2 = bw.norm2_w, fa.b2n = bw.norm2_b, fa.bo = bw.to_out_b;
+      fa.hin = a.hin, fa.dh_in = dh_cur = (dh_cur == w.dh ? w.dh2 : w.dh);
+      fa.pk2 = reinterpret_cast<uint4 *>(w.dq);   // xn2 / dh1 as fragments for the parameter kernel (w.dq: free in this path)
+      if (dropout_p > 0.f) {   // the bits the forward left in a.p
         fa.dk = dfx::drop_key(dropout_seed, dropout_p), fa.site_att = (unsigned)(2 * i), fa.site_ff = (unsigned)(2 * i + 1);
         fa.dmask = reinterpret_cast<unsigned *>(a.p);
       }
-      if (dfx::ffused::launch_ff<true>(st, fa)) return dfx::set_error(DFX_ERR_HIP, "train: fused feed-forward backward launch");
+      if (dfx::ffused::launch_ff_bwd(st, fa)) return dfx::set_error(DFX_ERR_HIP, "train: fused feed-forward backward launch");
       if (i == 0 && so.stem_early) {   // w.dh is final: pre_norm / proj_in backward beside the rest of the block's parameter kernels
         if ((rc = ss.fork())) return rc;
         stem_backward(sp, w.datt);
       }
-      // (with the attention's input gradient in the same kernel, the six column sums of every block are one launch behind the loop)
-      if (split)
-        k_sum_parts_multi<<<3 * C / 32, 1024, 0, st>>>(w.cpart[i], SumOuts{{nullptr, nullptr, mut(gw.ff2_b), nullptr}}, (int)dfx::ffused::ff_groups(B, N), C, 3 * C);
-      // dW1, db1, dW2: weight-stationary, hid and d[a | g] recomputed from the tiles k_ff<true> left in w.dwide; the slab partials of every
-      // block are summed in one launch behind the loop
-      {
-        // (without the attention inside — dfx_debug_train_fused(2) — k_ff<true> reads fp32 rows and leaves both fragment sets in w.dwide)
-        dfx::ffused::FwArgs wa{w.ff_frags[i], w.ff_b1p[i] + dfx::ffused::B1P_FLOATS,
-                               split ? reinterpret_cast<const uint4 *>(w.dwide) : reinterpret_cast<const uint4 *>(a.h1), w.ffw_part[i], w.ffw_bpart[i],
-                               R / 32, w.ffw_slabs, dropout_p > 0.f ? reinterpret_cast<const unsigned *>(a.p) : nullptr,
-                               split ? reinterpret_cast<const uint4 *>(w.dwide) + dfx::ffused::PK_TILE_U4 / 2 : reinterpret_cast<const uint4 *>(dh_in_blk)};
-        if (dfx::ffused::launch_ff_wgrad(st, wa)) return dfx::set_error(DFX_ERR_HIP, "train: feed-forward weight-gradient launch");
-      }
-      // attention + LayerNorm2 (train_attn_fused.h): parameter side first (reads dh1 = w.dh2), then dh -> w.dh
-      dfx::afused::AttnArgs aa{};
-      aa.frags = w.at_frags[i], aa.valid = w.valid, aa.g2 = bw.norm2_w, aa.b2 = bw.norm2_b, aa.bo = bw.to_out_b;
-      aa.h = a.hin, aa.dh1 = w.dh2, aa.dh = w.dh, aa.part = w.at_part[i], aa.cpart = w.cpart[i], aa.N = N, aa.split = w.at_split, aa.R = R;
-      aa.pk2 = split ? nullptr : reinterpret_cast<const uint4 *>(w.dq);
-      if (split) {
-        dfx::afused::k_attn_bwd_param<false><<<B * w.at_split, dfx::afused::NW * 64, 0, st>>>(aa);
-        const int np = dfx::afused::dx_groups(R);
-        dfx::afused::k_attn_bwd_dx<<<np, dfx::afused::NW * 64, 0, st>>>(aa);
-        k_sum_parts_multi<<<3 * C / 32, 1024, 0, st>>>(w.cpart[i], SumOuts{{mut(gw.norm2_w), mut(gw.norm2_b), mut(gw.to_out_b), nullptr}}, np, C, 3 * C);
-      } else {
-        dfx::afused::k_attn_bwd_param<true><<<B * w.at_split, dfx::afused::NW * 64, 0, st>>>(aa);
-      }
+      // dW1, db1, dW2: weight-stationary, hid and d[a | g] recomputed from the forward's xhat3 fragments (a.h1) and the hi halves of the block's incoming
+      // gradient; the slab partials of every block are summed in one launch behind the loop (as are the six column sums k_ff_bwd left in cpart)
+      dfx::ffused::FwArgs wa{w.ff_frags[i], w.ff_b1p[i] + dfx::ffused::B1P_FLOATS, reinterpret_cast<const uint4 *>(a.h1), w.ffw_part[i], w.ffw_bpart[i],
+                             R / 32, w.ffw_slabs, dropout_p > 0.f ? reinterpret_cast<const unsigned *>(a.p) : nullptr,
+                             reinterpret_cast<const uint4 *>(dh_in_blk)};
+      if (dfx::ffused::launch_ff_wgrad(st, wa)) return dfx::set_error(DFX_ERR_HIP, "train: feed-forward weight-gradient launch");
+      // attention, parameter side (train_attn_fused.h): dA_s, dM_s per shape from the xn2 / dh1 fragments
+      dfx::afused::AttnArgs aa{w.at_frags[i], w.valid, w.at_part[i], reinterpret_cast<const uint4 *>(w.dq), N, w.at_split};
+      dfx::afused::k_attn_bwd_param<<<B * w.at_split, dfx::afused::NW * 64, 0, st>>>(aa);
     }
     {
       // parameter gradients of ALL blocks from the partials the block loop left behind: one launch per kind (keys / values of all blocks: one pair
@@ -2552,7 +2493,7 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
       dfx::afused::k_attn_unfold_kv<<<dim3(dfx::afused::J, B, wt->depth), 256, 0, st>>>(ub);
       if (so.stem_end) stem_backward(sp, w.datt);
       dfx::ffused::launch_ff_wgrad_finish(sl, fb, wt->depth);
-      if (!split) k_sum_parts_jobs<<<wt->depth * 6 * (C / 32), 1024, 0, sl>>>(sj, (int)dfx::ffused::ff_groups(B, N), C, 6 * C);
+      k_sum_parts_jobs<<<wt->depth * 6 * (C / 32), 1024, 0, sl>>>(sj, (int)dfx::ffused::ff_groups(B, N), C, 6 * C);
       if (head_late) head_sums(sp);
       if ((rc = ss.fork())) return rc;   // (k_attn_unfold_w reads the per-shape sums k_attn_unfold_kv leaves in at_sum)
       dfx::afused::k_attn_unfold_w<<<dim3(C / dfx::afused::UW_D, 1, wt->depth), 1024, 0, sl>>>(ub);
@@ -2606,7 +2547,7 @@ int dfx_denoiser_train_forward(const dfx_denoiser_weights *wt, void *workspace, 
   if (rc) return rc;
   DFX_REQUIRE(precision == DFX_PREC_F32 || precision == DFX_PREC_BF16, "denoiser_train_forward: precision %d", precision);
   DFX_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "denoiser_train_forward: dropout_p %g", (double)dropout_p);
-  const dfx::TrainPlan plan = dfx::plan_train(precision, dropout_p, B, N, dfx::TrainSwitches{g_ff_fused, g_attn_in_ff, g_train_streams});
+  const dfx::TrainPlan plan = dfx::plan_train(precision, dropout_p, B, N, dfx::TrainSwitches{g_ff_fused, g_train_streams});
   {
     std::lock_guard<std::mutex> lk(g_path_mu);
     // bounded table: a record is overwritten by the next forward into the same workspace (stale addresses cost nothing); when 4096
@@ -2975,7 +2916,7 @@ int dfx_shared_mlp_train_backward(const dfx_shared_mlp_train *t, void *workspace
 
 // The dropout factors (0 or 1 / (1 - p)) of `n` consecutive elements of a site, as the training kernels apply them
 // (site 2 i: behind to_out of block i, over (B N, 128); 2 i + 1: behind the GEGLU of block i, over (B N, 512); 1000: time_embed)
-void dfx_debug_train_fused(int on) { g_ff_fused = on != 0, g_attn_in_ff = on != 2; }
+void dfx_debug_train_fused(int on) { g_ff_fused = on != 0; }
 const char *dfx_debug_last_train_path(void) { return t_last_path; }
 const char *dfx_debug_plan_train(int prec, float dropout_p, int fused_switch, int streams_switch, int B, int N, int *bits_out) {
   if ((prec != DFX_PREC_F32 && prec != DFX_PREC_BF16) || !(dropout_p >= 0.f && dropout_p < 1.f) || B < 1 || N < 32 || N % 32 != 0) return nullptr;

@@ -15,19 +15,19 @@ extern "C" {
 /* Dropout factors (0 or 1/(1-p)) of n consecutive elements of a site: 2 i = behind to_out of block i over (B N, 128),
  * 2 i + 1 = behind the GEGLU of block i over (B N, 512), 1000 = time_embed over (B, 1024).  n % 4 == 0. */
 int dfx_debug_dropout_factors(uint64_t seed, int site, float p, float *out, long long n, dfx_stream_t stream);
-/* Debug / A-B switch: 0 routes the bf16 training path through the layer-by-layer kernels instead of the fused ones (default 1;
- * the fused path applies to DFX_PREC_BF16 with dropout_p == 0); 2 = fused, but the attention forward and its input gradient run as
- * kernels of their own instead of inside the feed-forward kernels. */
+/* Debug / A-B switch: 0 routes the bf16 training path through the layer-by-layer kernels instead of the fused ones (default 1: the fused
+ * path, for DFX_PREC_BF16 from 256 rows, with or without dropout).  Any non-zero value selects the fused path (2 once kept the attention
+ * forward and its input gradient as kernels of their own; it is now the same as 1). */
 void dfx_debug_train_fused(int on);
 /* The kernel family the calling thread's most recent dfx_denoiser_train_forward took (its backward follows the same record):
- * "fused_bf16", "fused_bf16_dropout" (k_ff_fwd_chain / k_ff<true> / k_ff_wgrad), "layer_bf16(_dropout)" (layer-by-layer kernels, bf16
+ * "fused_bf16", "fused_bf16_dropout" (k_ff_fwd_chain / k_ff_bwd / k_ff_wgrad), "layer_bf16(_dropout)" (layer-by-layer kernels, bf16
  * products), "layer_f32(_dropout)" (exact fp32; also what DFX_PREC_BF16 takes below 256 rows), "none" before the first call. */
 const char *dfx_debug_last_train_path(void);
 /* Host-side run (no GPU) of the training step's planner (csrc/train_plan.h): the name dfx_debug_last_train_path() would report after a
  * dfx_denoiser_train_forward of B shapes of N points with `prec` (DFX_PREC_*) and dropout_p under dfx_debug_train_fused(fused_switch) and
  * dfx_debug_train_streams(streams_switch); NULL for arguments the entry points reject.  *bits_out (may be NULL): bits 0-1 the path (0 layer
- * by layer with fp32-stored activations, 1 layer by layer with bf16-stored product operands, 2 fused with the attention as kernels of its own,
- * 3 fused), 4 = bf16-stored product operands, 8 = dropout on; what goes to the side stream: 16 the forward's context branch, 32 the backward
+ * by layer with fp32-stored activations, 1 layer by layer with bf16-stored product operands, 3 fused; 2 was the fused path with the attention
+ * as kernels of its own: retired, never reported), 4 = bf16-stored product operands, 8 = dropout on; what goes to the side stream: 16 the forward's context branch, 32 the backward
  * uses the side stream at all, 64 the head's sums right behind k_head_bwd, 128 the stem's backward behind block 0, 256 the finishing kernels'
  * leaves, 512 the stem's backward beside the finishing kernels.  A pure function of its arguments: the process-global switches are not read. */
 const char *dfx_debug_plan_train(int prec, float dropout_p, int fused_switch, int streams_switch, int B, int N, int *bits_out);

@@ -291,47 +291,6 @@ def test_layernorm3_fold_with_awkward_affine_parameters():
     assert e_eps < 6.6e-3 and worst < 1.7e-2 and max(z) < 1.7e-2, (e_eps, worst, at, z)
 
 
-def test_attention_inside_the_feed_forward_kernels_matches_the_separate_attention_kernels():
-    """dfx_debug_train_fused(2) runs the attention forward and its input gradient as kernels of their own (k_attn_fwd_fused,
-    k_attn_bwd_dx); the default folds them into k_ff<false>'s prologue / k_ff<true>'s epilogue.  Same device functions on the same
-    values in the forward: identical eps.  Backward: since round 5 the default carries the gradient between two blocks as a bf16 pair
-    (hi + lo = the fp32 value to 2^-17, train_ff_fused.h TL_DH_HL) where the separate kernels pass fp32 — a 2^-17 difference that flips
-    the bf16 rounding of a few operand elements per block (measured: gradients 2.7e-4 of their max-abs; 1.6e-7 with fp32 on both sides,
-    r04), and computes the head in the last block's kernel, leaving post_norm's normalised row for k_head_bwd as bf16 fragments where the
-    separate path re-reads the fp32 rows (measured with both: gradients 1.5e-3, eps 4.8e-7 — the head's fp32 sums in another order) —
-    below the bf16-vs-fp32 distance the other gates measure (3e-3 .. 7.5e-3)."""
-    from difffacto_amd import _ffi, synth
-    B, N = 3, 160
-    rng = np.random.Generator(np.random.PCG64(4242))
-    W = synth.make_denoiser_weights(7)
-    pc, mean, logvar, valid = synth.make_latents(B, seed=13, all_valid=False)
-    seg = synth.make_seg_mask(valid, N)
-    var = np.exp(logvar).astype(np.float32)
-    idx = np.broadcast_to(seg.astype(np.int64)[:, None, :], (B, 3, N))
-    anc, vr = np.take_along_axis(mean, idx, axis=2), np.take_along_axis(var, idx, axis=2)
-    c = dict(W=W, x_t=(anc + np.sqrt(vr) * rng.standard_normal((B, 3, N))).astype(np.float32), t=rng.integers(0, 1000, size=(B,)).astype(np.int64),
-             ctx_code=pc, ctx_mv=np.concatenate([mean, var], axis=1).astype(np.float32),
-             anchors_pt=np.ascontiguousarray(anc.transpose(0, 2, 1)), variances_pt=np.ascontiguousarray(vr.transpose(0, 2, 1)),
-             valid=valid, assignment=seg.astype(np.int32), noise=rng.standard_normal((B, 3, N)).astype(np.float32),
-             flags=(rng.uniform(size=(B, 1, N)) > 0.3).astype(np.float32))
-    inside = _run(c, True, precision="bf16")
-    _ffi.lib().dfx_debug_train_fused(2)
-    try:
-        apart = _run(c, True, precision="bf16")
-    finally:
-        _ffi.lib().dfx_debug_train_fused(1)
-    e_eps = np.abs(inside["eps"] - apart["eps"]).max()
-    worst = 0.0
-    for k, gr in apart["grads"].items():
-        worst = max(worst, np.abs(inside["grads"][k] - gr).max() / max(np.abs(gr).max(), 1e-30))
-    print(f"attention inside vs beside the feed-forward kernels: eps max-abs {e_eps:.1e}, gradients worst max-norm {worst:.1e}")
-    # Round 6: the default forward (ff_fwd) evaluates the GEGLU with the sampling kernel's packed-fp16 polynomial and GEMM2 as an fp16 product; the
-    # separate-attention variant keeps round 5's forward body (fp32 sigmoid form, bf16 GEMM2): the two forwards now differ by the distance between
-    # the two GELU formulations — measured eps 1.7e-3, gradients 2.0e-3 of max-abs (gates at 3x / 2x; both forwards sit inside the bf16 gates against the
-    # fp32 oracle, test_bf16_matrix_products_within_stated_tolerance).  Until round 5: identical eps (< 1e-5).
-    assert e_eps < 5e-3 and worst < 4e-3
-
-
 def test_fused_training_step_is_bit_reproducible():
     """No atomics anywhere in the fused path (column sums through LDS tiles in fixed order, per-slab / per-shape partials summed in
     order): two runs of the same iteration give bit-identical eps and gradients."""

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Are two builds of the training kernels bit-identical?  (GPU box)  usage: ab_bits.sh "-DFLAGS_OF_ARM_0" ["-DFLAGS_OF_ARM_1"]   (arm 1 without flags = the shipped build)
 # eps + 79 gradients of one iteration at three shapes (16 x 2048 with Dropout 0.2, 3 x 160, 64 x 2048 with Dropout 0.2) from each build, compared bit by bit.
-# Used for: k_ff<true>'s transpose-read ring against the two-item ring it replaced, k_ff_wgrad's transpose-read consumers, its consumer-side staging.
+# Used for: k_ff_bwd's transpose-read ring against the two-item ring it replaced, k_ff_wgrad's transpose-read consumers, its consumer-side staging.
 # Those knobs are not part of the shipped kernels: git apply tools/patches/train_ff_knobs_and_ablations.patch first and pass the flag its header lists.
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 [ $# -ge 1 ] || { echo "usage: ab_bits.sh \"-DFLAGS_OF_ARM_0\" [\"-DFLAGS_OF_ARM_1\"]   (flags: the header of tools/patches/train_ff_knobs_and_ablations.patch)"; exit 2; }

@@ -1,4 +1,4 @@
-"""Phase trace of the training step's fused feed-forward kernels (k_ff<false>, k_ff<true>, k_ff_wgrad): builds libdfx with
+"""Phase trace of the training step's fused feed-forward kernels (k_ff_fwd_chain launched per block, k_ff_bwd, k_ff_wgrad): builds libdfx with
 -DDFX_TRACE_FF (stamps of wave 0 of every 29th workgroup: tag + shader clock + HW_ID), runs tools/bench_train.py once and prints the
 average duration of each phase in shader cycles.  GPU box only; rebuilds the plain library afterwards.
 
@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 from difffacto_amd import build  # noqa: E402
 
-NAMES = {0: "k_ff<false>", 1: "k_ff<true>", 2: "k_ff_wgrad (producer wave 0)", 3: "k_ff_wgrad (consumer wave 4)"}
+NAMES = {0: "k_ff_fwd_chain (n = 1)", 1: "k_ff_bwd", 2: "k_ff_wgrad (producer wave 0)", 3: "k_ff_wgrad (consumer wave 4)"}
 
 
 def analyse(path, out):

@@ -32,7 +32,7 @@ def bands(prec, fold, N, code=0):
 
 def train_table():
     """path, record and side-stream use of a denoiser training step by precision, row count, dropout and dfx_debug_train_fused."""
-    paths = ("layer by layer, fp32-stored", "layer by layer, bf16-stored operands", "fused, attention as kernels of its own", "fused")
+    paths = {0: "layer by layer, fp32-stored", 1: "layer by layer, bf16-stored operands", 3: "fused"}   # (2: retired, never reported)
     side = ((16, "forward: context branch"), (64, "head sums early"), (128, "stem early"), (256, "leaves"), (512, "stem at the end"))
 
     def cells(prec, p, sw, B, N):
