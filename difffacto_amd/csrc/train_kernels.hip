@@ -1608,17 +1608,46 @@ struct Carver {
   }
 };
 
-struct BlockAct {
-  float *hin, *st2, *xn2, *q, *k, *v, *p, *att, *h1, *st3, *xn3, *ag, *hid;
-};
-struct TrainWs {
-  // saved by the forward
-  float *xin, *h0, *st_pre, *hfin, *st_post, *hn, *ctx, *te_in, *te_ag, *te_hid, *te_out;
-  BlockAct blk[DFX_MAX_DEPTH];
-  // backward scratch
-  float *dh, *dh2, *dwide, *dhid, *dq, *datt, *dk, *dv, *dctx, *dte_out, *dte_hid, *dte_ag, *wT, *wpad, *part, *bpart, *apart;
-  float *valid;
+struct PartBufs {   // scratch of the two-pass reductions
+  float *part, *bpart;
   size_t part_floats, bpart_floats;
+};
+struct BnScratch { PartBufs pb; float *sums; };   // of bn_fwd / bn_bwd: column-sum partials and their sums
+// The entry points' workspace rules; need = the byte count of the workspace's carve at null
+int check_ws(size_t need, const void *ws, size_t ws_bytes, const char *what) {
+  DFX_REQUIRE(ws_bytes >= need, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
+  DFX_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: workspace must be 256-byte aligned", what);
+  return DFX_OK;
+}
+
+// ---- the denoiser training workspace: three groups of buffers by who uses them (the table in front of TrainStep) ----
+struct CommonWs {   // both families of paths
+  float *xin, *ctx, *te_in, *te_ag, *te_hid, *te_out, *valid;   // saved by the forward
+  float *dctx, *dte_out, *dte_hid, *dte_ag;                      // backward
+  PartBufs pb;   // pb, wT: scratch of the launches on the CALLER's stream, and of those only: the fused backward's side stream runs beside them
+  float *wT;
+};
+struct LayerAct { float *hin, *st2, *xn2, *q, *k, *v, *p, *att, *h1, *st3, *xn3, *ag, *hid; };
+struct LayeredWs {   // forward_layered / backward_layered only
+  float *h0, *st_pre, *hfin, *st_post, *hn;   // saved by the forward
+  LayerAct blk[DFX_MAX_DEPTH];
+  float *dh, *dh2, *dwide, *dhid, *dq, *datt, *dk, *dv, *wpad, *apart;   // backward scratch
+};
+// A tile-major tensor of the fused kernels (train_ff_fused.h), 16 KiB per 32 points: one address, as floats and as the 16-byte fragments
+struct Tiles { float *f32; uint4 *u4; };
+// Scratch of the fused backward's launches that MAY run on the side stream (head_sums, stem_backward, the leaves): from the kernel that fills a buffer until
+// the join, no other launch touches it
+struct SideScratch {
+  float *head_part, *stem_part;   // views: [ceil(R / HEAD_ROWS)][HEAD_PART], [ceil(R / STEM_ROWS)][STEM_PART]
+  float *ffw_lnpart[DFX_MAX_DEPTH];
+};
+struct FusedWs {   // forward_fused / backward_fused only
+  // Views: the fused step's own layouts in the memory of layered buffers, set by carve() alone (the table in front of TrainStep says what each holds)
+  float *hin[DFX_MAX_DEPTH];
+  Tiles h1_frag[DFX_MAX_DEPTH], head_frag, dh_pair[2];
+  uint4 *pk2;
+  unsigned *dmask[DFX_MAX_DEPTH];
+  SideScratch side;
   // fused feed-forward (train_ff_fused.h): the block's W1 / W2 as bf16 MFMA fragments, re-packed by every forward
   uint4 *ff_frags[DFX_MAX_DEPTH];
   float *ff_b1p[DFX_MAX_DEPTH], *ff_b2p[DFX_MAX_DEPTH];
@@ -1627,103 +1656,100 @@ struct TrainWs {
   float *at_part[DFX_MAX_DEPTH], *at_sum[DFX_MAX_DEPTH], *cpart[DFX_MAX_DEPTH];   // per block: summed / unfolded behind the block loop, one launch each
   int at_split;
   // weight-stationary feed-forward gradients (k_ff_wgrad): per-slab partial tiles
-  float *ffw_part[DFX_MAX_DEPTH], *ffw_bpart[DFX_MAX_DEPTH], *ffw_lnpart[DFX_MAX_DEPTH], *head_tab;
+  float *ffw_part[DFX_MAX_DEPTH], *ffw_bpart[DFX_MAX_DEPTH], *head_tab;
   int ffw_slabs;
   // keys / values of all blocks in one product: packed weights (and transposed), k | v of every block side by side, their gradients
   float *wkv, *wkvT, *kv, *dkv, *dwkv;
+};
+struct TrainWs {
+  CommonWs common;
+  LayeredWs layered;
+  FusedWs fused;
+  const char *miss = nullptr;   // the first view whose need exceeds the buffer under it (no legal shape has one: tests/test_train_workspace_cpu.py)
+  size_t miss_need = 0, miss_cap = 0;
 };
 
 constexpr int WG_SLAB = 2048;   // rows per k_wgrad slab (64 for the few-row products over the context tokens / the batch)
 inline int slab_rows(long long R) { return R <= 8192 ? 64 : WG_SLAB; }
 inline int nslabs(long long R) { return (int)((R + slab_rows(R) - 1) / slab_rows(R)); }
 
-size_t carve(TrainWs &w, void *base, int B, int N, int depth) {
+// Per-point views: bytes of a 32-point tile in the fused layout against the tile's rows in the layered buffer
+constexpr size_t TILE_ROWS_BYTES = 32 * C * sizeof(float);   // h1, hfin, dh, dh2, dq: (R, 128) floats
+constexpr int STEM_PART = 2048;                              // floats per workgroup of k_stem_bwd's partial sums (its red[4][2048])
+static_assert(dfx::ffused::DM_TILE * sizeof(unsigned) <= 32 * HEADS * J * sizeof(float), "dmask: 80 B per point over p's 128");
+static_assert(2 * 8 * 64 * sizeof(uint4) == TILE_ROWS_BYTES, "pk2: [2][8][64] uint4 per tile = dq's 512 B per point");
+static_assert((dfx::ffused::HL_LO_U4 + 8 * 64) * sizeof(uint4) == TILE_ROWS_BYTES, "dh_pair: hi + lo halves = dh's 512 B per point");
+static_assert(8 * 64 * sizeof(uint4) <= dfx::ffused::H1F_RSTD * sizeof(float) && (dfx::ffused::H1F_RSTD + 32) * sizeof(float) <= TILE_ROWS_BYTES,
+              "h1_frag, head_frag: 8 KiB of fragments + 32 rstd = 260 B per point over h1's / hfin's 512");
+static_assert(dfx::ffused::HEAD_TAB_FLOATS <= 512, "head_tab");
+inline size_t head_part_floats(size_t R) { return (R + HEAD_ROWS - 1) / HEAD_ROWS * HEAD_PART; }
+inline size_t stem_part_floats(size_t R) { return (R + STEM_ROWS - 1) / STEM_ROWS * STEM_PART; }
+
+size_t carve(TrainWs &ws, void *base, int B, int N, int depth) {
   Carver c{static_cast<char *>(base)};
+  CommonWs &cm = ws.common;
+  LayeredWs &l = ws.layered;
+  FusedWs &f = ws.fused;
   const size_t R = (size_t)B * N, BJ = (size_t)B * J;
-  w.xin = c.take<float>(R * XIN);
-  w.h0 = c.take<float>(R * C);
-  w.st_pre = c.take<float>(R * 2);
-  w.hfin = nullptr;   // = output buffer of the last block (blk[depth].hin slot below)
-  w.st_post = c.take<float>(R * 2);
-  w.hn = c.take<float>(R * C);
-  w.ctx = c.take<float>(BJ * CTXP);
-  w.te_in = c.take<float>((size_t)B * TE);
-  w.te_ag = c.take<float>((size_t)B * 2 * TEH);
-  w.te_hid = c.take<float>((size_t)B * TEH);
-  w.te_out = c.take<float>((size_t)B * TE);
-  w.valid = c.take<float>(BJ);
+  auto pts = [&](size_t n) { return c.take<float>(R * n); };            // n floats per point,
+  auto tok = [&](size_t n) { return c.take<float>(BJ * n); };           // per context token,
+  auto shp = [&](size_t n) { return c.take<float>((size_t)B * n); };    // per shape
+  cm.xin = pts(XIN);
+  l.h0 = pts(C), l.st_pre = pts(2), l.st_post = pts(2), l.hn = pts(C);
+  cm.ctx = tok(CTXP), cm.te_in = shp(TE), cm.te_ag = shp(2 * TEH), cm.te_hid = shp(TEH), cm.te_out = shp(TE), cm.valid = tok(1);
   for (int i = 0; i < depth; ++i) {
-    BlockAct &a = w.blk[i];
-    a.hin = c.take<float>(R * C);
-    a.st2 = c.take<float>(R * 2);
-    a.xn2 = c.take<float>(R * C);
-    a.q = c.take<float>(R * C);
-    a.k = c.take<float>(BJ * C);
-    a.v = c.take<float>(BJ * C);
-    a.p = c.take<float>(R * HEADS * J);
-    a.att = c.take<float>(R * C);
-    a.h1 = c.take<float>(R * C);
-    a.st3 = c.take<float>(R * 2);
-    a.xn3 = c.take<float>(R * C);
-    a.ag = c.take<float>(R * 2 * FH);
-    a.hid = c.take<float>(R * FH);
+    LayerAct &a = l.blk[i];
+    a.hin = pts(C), a.st2 = pts(2), a.xn2 = pts(C), a.q = pts(C), a.k = tok(C), a.v = tok(C), a.p = pts(HEADS * J);
+    a.att = pts(C), a.h1 = pts(C), a.st3 = pts(2), a.xn3 = pts(C), a.ag = pts(2 * FH), a.hid = pts(FH);
   }
-  w.hfin = c.take<float>(R * C);
-  w.dh = c.take<float>(R * C);
-  w.dh2 = c.take<float>(R * C);
-  w.dwide = c.take<float>(R * 2 * FH);
-  w.dhid = c.take<float>(R * FH);
-  w.dq = c.take<float>(R * C);
-  w.datt = c.take<float>(R * C);
-  w.dk = c.take<float>(BJ * C);
-  w.dv = c.take<float>(BJ * C);
-  w.dctx = c.take<float>(BJ * CTXP);
-  w.dte_out = c.take<float>((size_t)B * TE);
-  w.dte_hid = c.take<float>((size_t)B * TEH);
-  w.dte_ag = c.take<float>((size_t)B * 2 * TEH);
-  w.wT = c.take<float>((size_t)2 * TEH * TE + 64);      // largest transposed weight: time_embed.net.0.proj (2048 x 256)
-  w.wpad = c.take<float>((size_t)C * CTXP);
+  l.hfin = pts(C);   // the last block's output
+  l.dh = pts(C), l.dh2 = pts(C), l.dwide = pts(2 * FH), l.dhid = pts(FH), l.dq = pts(C), l.datt = pts(C), l.dk = tok(C), l.dv = tok(C);
+  cm.dctx = tok(CTXP), cm.dte_out = shp(TE), cm.dte_hid = shp(TEH), cm.dte_ag = shp(2 * TEH);
+  cm.wT = c.take<float>((size_t)2 * TEH * TE + 64);      // largest transposed weight: time_embed.net.0.proj (2048 x 256)
+  l.wpad = c.take<float>((size_t)C * CTXP);
   // partial buffers of the two-pass reductions: the largest weight-gradient partial of each row count (points, context
   // tokens, batch rows), the LayerNorm / proj_out column sums
   const size_t ns_r = nslabs((long long)R), ns_bj = nslabs((long long)BJ), ns_b = nslabs(B);
   size_t pf = ns_r * (size_t)(2 * FH) * C;                                  // W1 (1024 x 128) over the points
   const size_t cands[] = {ns_bj * (size_t)C * CTXP, ns_b * (size_t)2 * TEH * TE, ((R + LNB_ROWS - 1) / LNB_ROWS) * 2 * C,
                           ((R + EPSB_ROWS - 1) / EPSB_ROWS) * 4 * C};
-  for (size_t v : cands)
-    if (v > pf) pf = v;
-  w.part_floats = pf;
-  w.part = c.take<float>(pf);
-  size_t ns_max = ns_r > ns_bj ? ns_r : ns_bj;
-  if (ns_b > ns_max) ns_max = ns_b;
-  w.bpart_floats = (ns_max > 2048 ? ns_max : 2048) * (size_t)(2 * TEH);   // room for 2048 slabs of the widest bias
-  w.bpart = c.take<float>(w.bpart_floats);
-  w.apart = c.take<float>((size_t)B * (N / 32) * 2 * J * C);
+  for (size_t v : cands) pf = std::max(pf, v);
+  cm.pb.part_floats = pf, cm.pb.part = c.take<float>(pf);
+  const size_t ns_max = std::max({ns_r, ns_bj, ns_b});
+  cm.pb.bpart_floats = std::max<size_t>(ns_max, 2048) * (size_t)(2 * TEH), cm.pb.bpart = c.take<float>(cm.pb.bpart_floats);   // room for 2048 slabs of the widest bias
+  l.apart = c.take<float>((size_t)B * (N / 32) * 2 * J * C);
   for (int i = 0; i < depth; ++i) {
-    w.ff_frags[i] = c.take<uint4>(dfx::ffused::pack_bytes_frags() / sizeof(uint4));
-    w.ff_b1p[i] = c.take<float>(3 * dfx::ffused::B1P_FLOATS);   // the folded bias three times: in the chunk loop's order, in natural order (PackArgs::b1f), and with the forward's fp16 scales (b1ps)
-    w.ff_b2p[i] = c.take<float>(dfx::ffused::B2P_FLOATS);
+    f.ff_frags[i] = c.take<uint4>(dfx::ffused::pack_bytes_frags() / sizeof(uint4));
+    f.ff_b1p[i] = c.take<float>(3 * dfx::ffused::B1P_FLOATS);   // the folded bias three times: in the chunk loop's order, in natural order (PackArgs::b1f), and with the forward's fp16 scales (b1ps)
+    f.ff_b2p[i] = c.take<float>(dfx::ffused::B2P_FLOATS);
   }
-  for (int i = 0; i < depth; ++i) w.at_frags[i] = c.take<uint4>((size_t)B * dfx::afused::SHAPE_U4);
-  w.at_split = dfx::afused::param_split(B, N);
-  w.ffw_slabs = dfx::ffused::wgrad_slabs((long long)(R / 32));
+  for (int i = 0; i < depth; ++i) f.at_frags[i] = c.take<uint4>((size_t)B * dfx::afused::SHAPE_U4);
+  f.at_split = dfx::afused::param_split(B, N);
+  f.ffw_slabs = dfx::ffused::wgrad_slabs((long long)(R / 32));
   for (int i = 0; i < depth; ++i) {
-    w.at_part[i] = c.take<float>((size_t)B * w.at_split * 2 * dfx::afused::HJ * C);
-    w.at_sum[i] = c.take<float>((size_t)B * 2 * dfx::afused::HJ * C);
-    // (b: what the retired separate attention-gradient kernel's partials took — min(ceil(R / 128), 1024) rows of 3 C; it still bounds the size
-    // from below, so that every later buffer keeps its offset)
-    const long long dxg = (R / 32 + 3) / 4;
-    const size_t groups = (size_t)dfx::ffused::ff_groups(B, N), a = groups * 6 * C, b = (size_t)(dxg < 1024 ? dxg : 1024) * 3 * C;
-    w.cpart[i] = c.take<float>(a > b ? a : b);
-    w.ffw_part[i] = c.take<float>((size_t)w.ffw_slabs * dfx::ffused::NCHUNK * 12 * 1024);
-    w.ffw_bpart[i] = c.take<float>((size_t)w.ffw_slabs * dfx::ffused::NCHUNK * 64);
-    w.ffw_lnpart[i] = c.take<float>(dfx::ffused::LNPART_FLOATS);
-    if (i == 0) w.head_tab = c.take<float>(512);   // (>= dfx::ffused::HEAD_TAB_FLOATS)
+    f.at_part[i] = c.take<float>((size_t)B * f.at_split * 2 * dfx::afused::HJ * C);
+    f.at_sum[i] = c.take<float>((size_t)B * 2 * dfx::afused::HJ * C);
+    // (the retired separate attention-gradient kernel's min(ceil(R / 128), 1024) rows of 3 C never bound this from below: B ceil(N / 128) 6 C >= ceil(B N / 128) 3 C)
+    f.cpart[i] = c.take<float>((size_t)dfx::ffused::ff_groups(B, N) * 6 * C);
+    f.ffw_part[i] = c.take<float>((size_t)f.ffw_slabs * dfx::ffused::NCHUNK * 12 * 1024);
+    f.ffw_bpart[i] = c.take<float>((size_t)f.ffw_slabs * dfx::ffused::NCHUNK * 64);
+    f.side.ffw_lnpart[i] = c.take<float>(dfx::ffused::LNPART_FLOATS);
+    if (i == 0) f.head_tab = c.take<float>(512);
   }
-  w.wkv = c.take<float>((size_t)2 * depth * C * CTXP);
-  w.wkvT = c.take<float>((size_t)2 * depth * C * CTXP);
-  w.dwkv = c.take<float>((size_t)2 * depth * C * CTXP);
-  w.kv = c.take<float>(BJ * 2 * depth * C);
-  w.dkv = c.take<float>(BJ * 2 * depth * C);
+  const size_t wkv_floats = (size_t)2 * depth * C * CTXP;
+  f.wkv = c.take<float>(wkv_floats), f.wkvT = c.take<float>(wkv_floats), f.dwkv = c.take<float>(wkv_floats);
+  f.kv = tok(2 * depth * C), f.dkv = tok(2 * depth * C);
+  // The fused views: each set once, here, to the layered buffer it overlays.  Per-point views: the static_asserts above; the partial sums: need against capacity
+  auto tiles = [](float *p) { return Tiles{p, reinterpret_cast<uint4 *>(p)}; };
+  auto partial = [&](const char *view, float *under, size_t cap, size_t need) {
+    if (need > cap && !ws.miss) ws.miss = view, ws.miss_need = need, ws.miss_cap = cap;
+    return under;
+  };
+  for (int i = 0; i < depth; ++i) f.hin[i] = l.blk[i].hin, f.h1_frag[i] = tiles(l.blk[i].h1), f.dmask[i] = reinterpret_cast<unsigned *>(l.blk[i].p);
+  f.head_frag = tiles(l.hfin), f.dh_pair[0] = tiles(l.dh), f.dh_pair[1] = tiles(l.dh2), f.pk2 = reinterpret_cast<uint4 *>(l.dq);
+  f.side.head_part = partial("head_part", l.hn, R * C, head_part_floats(R));
+  f.side.stem_part = partial("stem_part", l.datt, R * C, stem_part_floats(R));
+  partial("stem partials in the caller's stream scratch", cm.pb.part, cm.pb.part_floats, stem_part_floats(R));   // (backward_fused without a side stream)
   return c.off;
 }
 
@@ -1791,12 +1817,6 @@ inline int pick_slab(long long R, long long tiles, long long target_blocks, size
   return (int)slab;
 }
 
-struct PartBufs {   // scratch of the two-pass reductions
-  float *part;
-  size_t part_floats;
-  float *bpart;
-  size_t bpart_floats;
-};
 int wgrad(hipStream_t st, int prec, const PartBufs &w, const float *dY, int ldy, const float *X, int ldx, float *dW, float *db, int O, int I,
           int I_valid, long long R, bool dy_bf = false, bool x_bf = false) {
   bool done = false;
@@ -1841,12 +1861,7 @@ int wgrad(hipStream_t st, int prec, const PartBufs &w, const float *dY, int ldy,
   return dfx::check_launch("train: wgrad");
 }
 
-inline int wgrad(hipStream_t st, int prec, TrainWs &w, const float *dY, int ldy, const float *X, int ldx, float *dW, float *db, int O, int I,
-                 int I_valid, long long R, bool dy_bf = false, bool x_bf = false) {
-  return wgrad(st, prec, PartBufs{w.part, w.part_floats, w.bpart, w.bpart_floats}, dY, ldy, X, ldx, dW, db, O, I, I_valid, R, dy_bf, x_bf);
-}
-
-int ln_bwd(hipStream_t st, TrainWs &w, const float *dy, const float *x, const float *stats, const float *g, const float *resid,
+int ln_bwd(hipStream_t st, const PartBufs &w, const float *dy, const float *x, const float *stats, const float *g, const float *resid,
            float *out, float *dg, float *db, long long R) {
   const int nb = (int)((R + LNB_ROWS - 1) / LNB_ROWS);
   k_ln_bwd<<<nb, 256, 0, st>>>(dy, x, stats, g, resid, out, w.part, R);
@@ -1864,9 +1879,8 @@ int check_args(const dfx_denoiser_weights *wt, const void *ws, size_t ws_bytes, 
   DFX_REQUIRE((long long)B * N < (1ll << 31), "%s: B*N too large", what);
   TrainWs t;
   const size_t need = carve(t, nullptr, B, N, wt->depth);
-  DFX_REQUIRE(ws_bytes >= need, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
-  DFX_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: workspace must be 256-byte aligned", what);
-  return DFX_OK;
+  DFX_REQUIRE(!t.miss, "%s: workspace view %s needs %zu floats, the buffer under it holds %zu", what, t.miss, t.miss_need, t.miss_cap);
+  return check_ws(need, ws, ws_bytes, what);
 }
 
 // ---- PointNetV2 train mode: workspace and BatchNorm helpers ----
@@ -1876,8 +1890,8 @@ struct PnWs {
   int32_t *arg;
   float *hz[2][2], *hy[2][2], *hmean[2][2], *hrstd[2][2];
   // backward scratch
-  float *dA, *dB, *dpooled, *dh[2], *wpad, *wT, *sums;
-  PartBufs pb;
+  float *dA, *dB, *dpooled, *dh[2], *wpad, *wT;
+  BnScratch bn;   // (+ the weight gradients' partials: bn.pb)
 };
 constexpr int PN_C[5] = {8, 128, 128, 256, 512};   // trunk widths (input padded 3 -> 8)
 size_t carve_pn(PnWs &w, void *base, int B, int N, int A, int /*zdim: the heads write straight into the caller's outputs*/) {
@@ -1885,37 +1899,29 @@ size_t carve_pn(PnWs &w, void *base, int B, int N, int A, int /*zdim: the heads 
   const size_t R = (size_t)B * N;
   w.X8 = c.take<float>(R * 8);
   for (int l = 0; l < 4; ++l) {
-    w.z[l] = c.take<float>(R * PN_C[l + 1]);
-    w.y[l] = c.take<float>(R * PN_C[l + 1]);
-    w.mean[l] = c.take<float>(PN_C[l + 1]);
-    w.rstd[l] = c.take<float>(PN_C[l + 1]);
+    w.z[l] = c.take<float>(R * PN_C[l + 1]), w.y[l] = c.take<float>(R * PN_C[l + 1]);
+    w.mean[l] = c.take<float>(PN_C[l + 1]), w.rstd[l] = c.take<float>(PN_C[l + 1]);
   }
   w.pooled = c.take<float>((size_t)B * A * 512);
   w.arg = c.take<int32_t>((size_t)B * A * 512);
   const int hc[2] = {256, 128};
   for (int k = 0; k < 2; ++k)
     for (int l = 0; l < 2; ++l) {
-      w.hz[k][l] = c.take<float>((size_t)B * A * hc[l]);
-      w.hy[k][l] = c.take<float>((size_t)B * A * hc[l]);
-      w.hmean[k][l] = c.take<float>((size_t)A * hc[l]);
-      w.hrstd[k][l] = c.take<float>((size_t)A * hc[l]);
+      w.hz[k][l] = c.take<float>((size_t)B * A * hc[l]), w.hy[k][l] = c.take<float>((size_t)B * A * hc[l]);
+      w.hmean[k][l] = c.take<float>((size_t)A * hc[l]), w.hrstd[k][l] = c.take<float>((size_t)A * hc[l]);
     }
-  w.dA = c.take<float>(R * 512);
-  w.dB = c.take<float>(R * 512);
+  w.dA = c.take<float>(R * 512), w.dB = c.take<float>(R * 512);
   w.dpooled = c.take<float>((size_t)B * A * 512);
-  w.dh[0] = c.take<float>((size_t)B * A * 256);
-  w.dh[1] = c.take<float>((size_t)B * A * 256);
+  w.dh[0] = c.take<float>((size_t)B * A * 256), w.dh[1] = c.take<float>((size_t)B * A * 256);
   w.wpad = c.take<float>(128 * 8);
   w.wT = c.take<float>((size_t)4 * 512 * 256);   // a transposed trunk weight (<= 512 x 256), or the four parts' transposed head weights side by side
-  w.sums = c.take<float>(4 * 1024);
+  w.bn.sums = c.take<float>(4 * 1024);
   const size_t nslab = (R + BN_SLAB - 1) / BN_SLAB;
   size_t pf = nslab * 2 * 1024;                            // BatchNorm column-sum partials (up to A * 256 channels)
   const size_t wg = (size_t)nslabs((long long)R) * 512 * 256;   // weight-gradient partials (conv4: 512 x 256)
   if (wg > pf) pf = wg;
-  w.pb.part_floats = pf;
-  w.pb.part = c.take<float>(pf);
-  w.pb.bpart_floats = (size_t)2048 * 1024;
-  w.pb.bpart = c.take<float>(w.pb.bpart_floats);
+  w.bn.pb.part_floats = pf, w.bn.pb.part = c.take<float>(pf);
+  w.bn.pb.bpart_floats = (size_t)2048 * 1024, w.bn.pb.bpart = c.take<float>(w.bn.pb.bpart_floats);
   return c.off;
 }
 
@@ -1924,7 +1930,7 @@ size_t carve_pn(PnWs &w, void *base, int B, int N, int A, int /*zdim: the heads 
 bool g_bn_fused_stats = true;
 // y = [relu] BN_train(z) over R rows; leaves mean / rstd behind and updates the running statistics when momentum >= 0
 // stat_parts > 0: the product that wrote z left that many rows of per-workgroup (count, mean, M2) partials in w.pb.part (lin_stats below): no pass over z
-int bn_fwd(hipStream_t st, const PnWs &w, const float *z, long long R, int Cc, const float *g, const float *b, float *run_mean,
+int bn_fwd(hipStream_t st, const BnScratch &w, const float *z, long long R, int Cc, const float *g, const float *b, float *run_mean,
            float *run_var, float momentum, float eps, float *mean, float *rstd, float *y, bool relu, bool apply = true, int stat_parts = 0) {
   const int ns = (int)((R + BN_SLAB - 1) / BN_SLAB);
   const dim3 grid((Cc + 63) / 64, ns);
@@ -1954,7 +1960,7 @@ int bn_fwd(hipStream_t st, const PnWs &w, const float *z, long long R, int Cc, c
 // dz from dy (gradient at the output of [relu] BN); d gamma, d beta written
 // batch_stats = false: BatchNorm in eval() mode under autograd (mean / rstd are the running statistics, constants): dz = g rstd gm — the two
 // correction terms of the batch-statistics form carry the factor 1 / R, which is passed as 0
-int bn_bwd(hipStream_t st, const PnWs &w, const float *dy, const float *be, const float *z, long long R, int Cc, const float *g,
+int bn_bwd(hipStream_t st, const BnScratch &w, const float *dy, const float *be, const float *z, long long R, int Cc, const float *g,
            const float *mean, const float *rstd, float *dz, float *dgamma, float *dbeta, bool relu, bool batch_stats = true) {
   const float invR = batch_stats ? 1.0f / (float)R : 0.0f;
   const int ns = (int)((R + BN_SLAB - 1) / BN_SLAB);
@@ -1979,10 +1985,7 @@ int check_pn(const dfx_pointnet_v2_weights *wt, const void *ws, size_t ws_bytes,
   DFX_REQUIRE(B >= 2 && N >= 1, "%s: B >= 2 (BatchNorm over the batch in the heads) and N >= 1 required", what);
   DFX_REQUIRE((long long)B * N < (1ll << 31), "%s: B*N too large", what);
   PnWs t;
-  const size_t need = carve_pn(t, nullptr, B, N, wt->num_anchors, wt->zdim);
-  DFX_REQUIRE(ws_bytes >= need, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
-  DFX_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: workspace must be 256-byte aligned", what);
-  return DFX_OK;
+  return check_ws(carve_pn(t, nullptr, B, N, wt->num_anchors, wt->zdim), ws, ws_bytes, what);
 }
 // grouped 1x1 convolution over B rows: group a reads columns a*cin.., writes a*cout..  (one launch, blockIdx.z = group)
 int glin(hipStream_t st, const float *X, const float *W, const float *b, float *Y, int B, int A, int cin, int cout) {
@@ -2008,35 +2011,23 @@ size_t carve_flow(FlowWs &w, void *base, int B, int depth, int H) {
   const size_t Rf = (size_t)NPART * B;
   for (int l = 0; l <= depth; ++l) w.xs[l] = c.take<float>(Rf * ZD);
   for (int l = 0; l < depth; ++l) {
-    w.h1[l] = c.take<float>(Rf * H);
-    w.h2[l] = c.take<float>(Rf * H);
-    w.st[l] = c.take<float>(Rf * ZD);
+    w.h1[l] = c.take<float>(Rf * H), w.h2[l] = c.take<float>(Rf * H), w.st[l] = c.take<float>(Rf * ZD);
   }
-  w.logdet = c.take<float>(Rf);
-  w.acoef = c.take<float>(Rf);
-  w.logp = c.take<float>(Rf);
-  w.ent = c.take<float>(Rf);
-  w.dlogdet = c.take<float>(Rf);
-  w.dy = c.take<float>(Rf * ZD);
-  w.dy2 = c.take<float>(Rf * ZD);
-  w.dst = c.take<float>(Rf * ZD);
-  w.dh1 = c.take<float>(Rf * H);
-  w.dh2 = c.take<float>(Rf * H);
+  w.logdet = c.take<float>(Rf), w.acoef = c.take<float>(Rf), w.logp = c.take<float>(Rf), w.ent = c.take<float>(Rf), w.dlogdet = c.take<float>(Rf);
+  w.dy = c.take<float>(Rf * ZD), w.dy2 = c.take<float>(Rf * ZD), w.dst = c.take<float>(Rf * ZD);
+  w.dh1 = c.take<float>(Rf * H), w.dh2 = c.take<float>(Rf * H);
   const size_t hm = (size_t)(H > ZD ? H : ZD);
   w.wT = c.take<float>(NPART * hm * hm);
   const size_t ns = (size_t)(B + 63) / 64 + 1;
-  w.pb.part_floats = ns * hm * hm;
-  w.pb.part = c.take<float>(w.pb.part_floats);
-  w.pb.bpart_floats = ns * hm;
-  w.pb.bpart = c.take<float>(w.pb.bpart_floats);
+  w.pb.part_floats = ns * hm * hm, w.pb.part = c.take<float>(w.pb.part_floats);
+  w.pb.bpart_floats = ns * hm, w.pb.bpart = c.take<float>(w.pb.bpart_floats);
   return c.off;
 }
 int check_flow(const float *const *flow, int depth, int H, const void *ws, size_t ws_bytes, int B, const char *what) {
   DFX_REQUIRE(flow && ws, "%s: null argument", what);
   DFX_REQUIRE(depth >= 1 && depth <= DFX_MAX_FLOW_DEPTH && H >= 8 && H % 8 == 0 && B >= 1, "%s: depth %d hidden %d B %d", what, depth, H, B);
   FlowWs t;
-  DFX_REQUIRE(ws_bytes >= carve_flow(t, nullptr, B, depth, H), "%s: workspace too small", what);
-  DFX_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: workspace must be 256-byte aligned", what);
+  if (int rc = check_ws(carve_flow(t, nullptr, B, depth, H), ws, ws_bytes, what)) return rc;
   for (int k = 0; k < NPART * depth * 6; ++k) DFX_REQUIRE(flow[k], "%s: null flow parameter %d", what, k);
   return DFX_OK;
 }
@@ -2131,7 +2122,7 @@ struct SmtWs {
   float *rows0, *z[DFX_MLP_MAX_LAYERS], *y[DFX_MLP_MAX_LAYERS], *mean[DFX_MLP_MAX_LAYERS], *rstd[DFX_MLP_MAX_LAYERS];
   int32_t *arg;
   float *dA, *dB, *wpad, *wT, *dwpad;
-  PnWs pn;   // (bn_fwd / bn_bwd take their scratch — pb, sums — from a PnWs)
+  BnScratch bn;   // (+ the weight gradients' partials: bn.pb)
   int cp0;   // ch[0] rounded up to a multiple of 8 (K of the products is consumed 8 at a time)
 };
 size_t carve_smt(SmtWs &w, void *base, const dfx_shared_mlp_train *t, long long R, long long G) {
@@ -2142,27 +2133,20 @@ size_t carve_smt(SmtWs &w, void *base, const dfx_shared_mlp_train *t, long long 
   size_t wmax = 0;
   for (int l = 0; l < t->layers; ++l) {
     const int co = t->ch[l + 1], ci = l == 0 ? w.cp0 : t->ch[l];
-    w.z[l] = c.take<float>((size_t)R * co);
-    w.y[l] = c.take<float>((size_t)R * co);
-    w.mean[l] = c.take<float>(co);
-    w.rstd[l] = c.take<float>(co);
+    w.z[l] = c.take<float>((size_t)R * co), w.y[l] = c.take<float>((size_t)R * co);
+    w.mean[l] = c.take<float>(co), w.rstd[l] = c.take<float>(co);
     cmax = std::max(cmax, co);
     wmax = std::max(wmax, (size_t)co * ci);
   }
   w.arg = c.take<int32_t>((size_t)G * t->ch[t->layers]);
-  w.dA = c.take<float>((size_t)R * cmax);
-  w.dB = c.take<float>((size_t)R * cmax);
-  w.wpad = c.take<float>(wmax);
-  w.wT = c.take<float>(wmax);
-  w.dwpad = c.take<float>(wmax);
-  w.pn.sums = c.take<float>(4 * 1024);
+  w.dA = c.take<float>((size_t)R * cmax), w.dB = c.take<float>((size_t)R * cmax);
+  w.wpad = c.take<float>(wmax), w.wT = c.take<float>(wmax), w.dwpad = c.take<float>(wmax);
+  w.bn.sums = c.take<float>(4 * 1024);
   const size_t nslab = (size_t)((R + BN_SLAB - 1) / BN_SLAB);
   size_t pf = nslab * 2 * (size_t)cmax;                                 // BatchNorm column-sum partials
   pf = std::max(pf, (size_t)nslabs(R) * wmax);                         // weight-gradient partials
-  w.pn.pb.part_floats = pf;
-  w.pn.pb.part = c.take<float>(pf);
-  w.pn.pb.bpart_floats = (size_t)2048 * 1024;
-  w.pn.pb.bpart = c.take<float>(w.pn.pb.bpart_floats);
+  w.bn.pb.part_floats = pf, w.bn.pb.part = c.take<float>(pf);
+  w.bn.pb.bpart_floats = (size_t)2048 * 1024, w.bn.pb.bpart = c.take<float>(w.bn.pb.bpart_floats);
   return c.off;
 }
 int check_smt(const dfx_shared_mlp_train *t, const void *ws, size_t ws_bytes, int B, int M, int ns, const char *what) {
@@ -2176,13 +2160,24 @@ int check_smt(const dfx_shared_mlp_train *t, const void *ws, size_t ws_bytes, in
     DFX_REQUIRE(t->bn_w[l] ? (t->bn_b[l] != nullptr) : true, "%s: layer %d: BatchNorm weight without bias", what, l);
   }
   SmtWs w;
-  const size_t need = carve_smt(w, nullptr, t, (long long)B * M * ns, (long long)B * M);
-  DFX_REQUIRE(ws_bytes >= need, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
-  DFX_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: workspace must be 256-byte aligned", what);
-  return DFX_OK;
+  return check_ws(carve_smt(w, nullptr, t, (long long)B * M * ns, (long long)B * M), ws, ws_bytes, what);
 }
 
 // ---- the denoiser training step: one forward and one backward function per family of paths (train_plan.h) ----
+// The workspace (carve()) is three groups.  CommonWs: what both families use — input rows, context and time-embedding rows, their gradients, the caller's stream's
+// scratch (pb, wT).  LayeredWs: only forward_layered / backward_layered.  FusedWs: only forward_fused / backward_fused; head_sums, stem_backward and the leaves take
+// scratch only from its SideScratch (the one stem_backward on the caller's stream names c.pb.part at its call).  The size has to cover the layered path (no precision
+// argument), so the fused step's own layouts live in layered buffers, as views that carve() alone sets:
+//   fused view (R = B N points)               layered buffer under it   need                                        capacity
+//   hin[i]        input rows, tile-major      blk[i].hin                512 B per point                             512 B per point
+//   h1_frag[i]    xhat3 fragments + 1 / std   blk[i].h1                 260 B per point (8320 B per 32-point tile)  512 B per point
+//   head_frag     the same, post_norm's       hfin                      260 B per point                             512 B per point
+//   dmask[i]      dropout bits                blk[i].p                  80 B per point (DM_TILE words per tile)     128 B per point
+//   dh_pair[0/1]  bf16-pair tiles / fp32 rows dh, dh2                   512 B per point                             512 B per point
+//   pk2           xn2 / dh1 fragments         dq                        512 B per point ([R / 32][2][8][64] uint4)  512 B per point
+//   head_part     k_head_bwd's partial sums   hn                        ceil(R / 128) 672 floats                    128 R floats
+//   stem_part     k_stem_bwd's partial sums   datt                      ceil(R / 512) 2048 floats                   128 R floats
+// The per-point rows are static_asserts in front of carve(); the last two are compared in carve() and a miss fails check_args by name, before any launch.
 struct TrainFwdIo {
   const float *x;
   const int32_t *t;
@@ -2197,7 +2192,8 @@ struct TrainBwdIo {
 };
 struct TrainStep {   // one call: weights, carved workspace, shape, plan, the caller's stream
   const dfx_denoiser_weights *wt;
-  TrainWs w;
+  TrainWs ws;
+  const CommonWs &c = ws.common;   // (each family's functions bind their own group beside it, as w)
   int B, N, BJ;
   long long R;
   dfx::TrainPlan plan;
@@ -2209,23 +2205,23 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
   TrainStep(const dfx_denoiser_weights *wt_, void *workspace, int B_, int N_, const dfx::TrainPlan &plan_, float p, uint64_t seed, dfx_stream_t stream)
       : wt(wt_), B(B_), N(N_), BJ(B_ * J), R((long long)B_ * N_), plan(plan_), side(dfx::plan_train_streams(plan_.path, g_train_streams)),   // (the side-stream decisions: from the live switch, by each call)
         dropout_p(p), dropout_seed(seed), st(dfx::as_stream(stream)) {
-    carve(w, workspace, B, N, wt->depth);
+    carve(ws, workspace, B, N, wt->depth);
   }
 
   // ---- forward ----
   // time embedding -> context rows, on sc
   int context_rows(const TrainFwdIo &io, hipStream_t sc) {
     int rc;
-    k_timestep_embedding<<<(B * TE + 255) / 256, 256, 0, sc>>>(io.t, w.te_in, B);
-    if ((rc = lin(sc, plan.prec, w.te_in, TE, wt->te0_w, wt->te0_b, w.te_ag, 2 * TEH, B, 2 * TEH, TE))) return rc;
-    k_geglu_fwd<false><<<(int)(((long long)B * TEH / 4 + 255) / 256), 256, 0, sc>>>(w.te_ag, w.te_hid, TEH, (long long)B * TEH, Drop{dropout_p, dropout_seed, SITE_TE});
-    if ((rc = lin(sc, plan.prec, w.te_hid, TEH, wt->te2_w, wt->te2_b, w.te_out, TE, B, TE, TEH))) return rc;
-    k_build_ctx<<<(BJ * CTXP + 255) / 256, 256, 0, sc>>>(io.ctx_code, io.ctx_mv, w.te_out, w.ctx, B);
+    k_timestep_embedding<<<(B * TE + 255) / 256, 256, 0, sc>>>(io.t, c.te_in, B);
+    if ((rc = lin(sc, plan.prec, c.te_in, TE, wt->te0_w, wt->te0_b, c.te_ag, 2 * TEH, B, 2 * TEH, TE))) return rc;
+    k_geglu_fwd<false><<<(int)(((long long)B * TEH / 4 + 255) / 256), 256, 0, sc>>>(c.te_ag, c.te_hid, TEH, (long long)B * TEH, Drop{dropout_p, dropout_seed, SITE_TE});
+    if ((rc = lin(sc, plan.prec, c.te_hid, TEH, wt->te2_w, wt->te2_b, c.te_out, TE, B, TE, TEH))) return rc;
+    k_build_ctx<<<(BJ * CTXP + 255) / 256, 256, 0, sc>>>(io.ctx_code, io.ctx_mv, c.te_out, c.ctx, B);
     return DFX_OK;
   }
   int keep_flags(const float *valid) {
-    if (valid) DFX_HIP_TRY(hipMemcpyAsync(w.valid, valid, sizeof(float) * BJ, hipMemcpyDeviceToDevice, st));
-    else DFX_HIP_TRY(hipMemsetAsync(w.valid, 0x3f, sizeof(float) * BJ, st));   // any non-zero value = keep
+    if (valid) DFX_HIP_TRY(hipMemcpyAsync(c.valid, valid, sizeof(float) * BJ, hipMemcpyDeviceToDevice, st));
+    else DFX_HIP_TRY(hipMemsetAsync(c.valid, 0x3f, sizeof(float) * BJ, st));   // any non-zero value = keep
     return DFX_OK;
   }
 
@@ -2233,25 +2229,26 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
     int rc;
     const int prec = plan.prec;
     const bool bf = plan.bf_store;
+    const LayeredWs &w = ws.layered;
     if ((rc = context_rows(io, st)) || (rc = keep_flags(io.valid))) return rc;
     // proj_in + pre_norm
-    k_build_xin<<<(int)((R + 255) / 256), 256, 0, st>>>(io.x, io.anchors, io.variances, io.assignment, w.xin, N, R);
+    k_build_xin<<<(int)((R + 255) / 256), 256, 0, st>>>(io.x, io.anchors, io.variances, io.assignment, c.xin, N, R);
     k_pad_cols<<<(C * XIN + 255) / 256, 256, 0, st>>>(wt->proj_in_w, w.wpad, C, 13, XIN);
-    if ((rc = lin(st, prec, w.xin, XIN, w.wpad, wt->proj_in_b, w.h0, C, R, C, XIN))) return rc;
+    if ((rc = lin(st, prec, c.xin, XIN, w.wpad, wt->proj_in_b, w.h0, C, R, C, XIN))) return rc;
     k_ln_fwd<false><<<(int)((R + 7) / 8), 256, 0, st>>>(w.h0, wt->pre_norm_w, wt->pre_norm_b, w.blk[0].hin, w.st_pre, R);
     for (int i = 0; i < wt->depth; ++i) {
       const dfx_block_weights &bw = wt->blk[i];
-      BlockAct &a = w.blk[i];
+      const LayerAct &a = w.blk[i];
       float *hout = i + 1 < wt->depth ? w.blk[i + 1].hin : w.hfin;
       if (bf) k_ln_fwd<true><<<(int)((R + 7) / 8), 256, 0, st>>>(a.hin, bw.norm2_w, bw.norm2_b, a.xn2, a.st2, R);
       else k_ln_fwd<false><<<(int)((R + 7) / 8), 256, 0, st>>>(a.hin, bw.norm2_w, bw.norm2_b, a.xn2, a.st2, R);
       if ((rc = lin(st, prec, a.xn2, C, bw.to_q, nullptr, a.q, C, R, C, C, nullptr, 0, bf))) return rc;
       k_pad_cols<<<(C * CTXP + 255) / 256, 256, 0, st>>>(bw.to_k, w.wpad, C, CTX, CTXP);
-      if ((rc = lin(st, prec, w.ctx, CTXP, w.wpad, nullptr, a.k, C, BJ, C, CTXP))) return rc;
+      if ((rc = lin(st, prec, c.ctx, CTXP, w.wpad, nullptr, a.k, C, BJ, C, CTXP))) return rc;
       k_pad_cols<<<(C * CTXP + 255) / 256, 256, 0, st>>>(bw.to_v, w.wpad, C, CTX, CTXP);
-      if ((rc = lin(st, prec, w.ctx, CTXP, w.wpad, nullptr, a.v, C, BJ, C, CTXP))) return rc;
-      if (bf) k_attn_fwd<true><<<dim3(N / 32, B), 256, 0, st>>>(a.q, a.k, a.v, w.valid, a.p, a.att, N);
-      else k_attn_fwd<false><<<dim3(N / 32, B), 256, 0, st>>>(a.q, a.k, a.v, w.valid, a.p, a.att, N);
+      if ((rc = lin(st, prec, c.ctx, CTXP, w.wpad, nullptr, a.v, C, BJ, C, CTXP))) return rc;
+      if (bf) k_attn_fwd<true><<<dim3(N / 32, B), 256, 0, st>>>(a.q, a.k, a.v, c.valid, a.p, a.att, N);
+      else k_attn_fwd<false><<<dim3(N / 32, B), 256, 0, st>>>(a.q, a.k, a.v, c.valid, a.p, a.att, N);
       if (dropout_p > 0.f) {   // h1 = dropout(att Wo^T + bo) + hin   (attention.py:177: to_out = Sequential(Linear, Dropout))
         if ((rc = lin(st, prec, a.att, C, bw.to_out_w, bw.to_out_b, a.h1, C, R, C, C, nullptr, 0, bf))) return rc;
         k_dropout<<<(int)((R * C / 4 + 255) / 256), 256, 0, st>>>(a.h1, a.hin, a.h1, R * C, Drop{dropout_p, dropout_seed, (unsigned)(2 * i)});
@@ -2271,6 +2268,7 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
 
   int forward_fused(const TrainFwdIo &io) {   // Fused
     int rc;
+    const FusedWs &w = ws.fused;
     // Two branches meet in front of the first block: the points (input rows, proj_in + pre_norm, the blocks' weight fragments) on the caller's
     // stream, the context (time embedding -> context rows -> keys / values of every block -> folded attention operands) on the side stream
     dfx::SideStream ss;
@@ -2287,8 +2285,8 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
     if ((rc = keep_flags(io.valid))) return rc;
     if ((rc = ss.fork())) return rc;
     // proj_in + pre_norm
-    k_build_xin<<<(int)((R + 255) / 256), 256, 0, st>>>(io.x, io.anchors, io.variances, io.assignment, w.xin, N, R);
-    k_stem_fwd<<<2048, 256, 0, st>>>(w.xin, wt->proj_in_w, wt->proj_in_b, wt->pre_norm_w, wt->pre_norm_b, w.blk[0].hin, R);
+    k_build_xin<<<(int)((R + 255) / 256), 256, 0, st>>>(io.x, io.anchors, io.variances, io.assignment, c.xin, N, R);
+    k_stem_fwd<<<2048, 256, 0, st>>>(c.xin, wt->proj_in_w, wt->proj_in_b, wt->pre_norm_w, wt->pre_norm_b, w.hin[0], R);
     // W1 / W2 of every block as bf16 MFMA fragments (train_ff_fused.h), one launch
     dfx::ffused::PackBatch pb{};
     for (int i = 0; i < wt->depth; ++i)
@@ -2299,7 +2297,7 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
     pb.head_w = wt->proj_out_w, pb.head_b = wt->proj_out_b, pb.head_g = wt->post_norm_w, pb.head_be = wt->post_norm_b, pb.head_tab = w.head_tab;
     dfx::ffused::launch_pack(st, pb, wt->depth);
     // keys and values of every block: one product over the B x 4 context tokens
-    if ((rc = lin(sc, plan.prec, w.ctx, CTXP, w.wkv, nullptr, w.kv, LDKV, BJ, LDKV, CTXP))) return rc;
+    if ((rc = lin(sc, plan.prec, c.ctx, CTXP, w.wkv, nullptr, w.kv, LDKV, BJ, LDKV, CTXP))) return rc;
     dfx::afused::FoldArgs fo{};
     fo.kv = w.kv, fo.ldkv = LDKV;
     for (int i = 0; i < wt->depth; ++i) fo.wq[i] = wt->blk[i].to_q, fo.wo[i] = wt->blk[i].to_out_w, fo.frags[i] = w.at_frags[i];
@@ -2311,20 +2309,19 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
     chain.n = wt->depth;
     for (int i = 0; i < wt->depth; ++i) {
       const dfx_block_weights &bw = wt->blk[i];
-      BlockAct &a = w.blk[i];
       dfx::ffused::FfArgs &fa = chain.blk[i];
       fa.frags = w.ff_frags[i], fa.b2p = w.ff_b2p[i], fa.g3 = bw.norm3_w, fa.b3 = bw.norm3_b;
       fa.b1p = w.ff_b1p[i] + 2 * dfx::ffused::B1P_FLOATS;   // ff_fwd's table: scaled like its W1 tiles (PackArgs::b1ps)
-      fa.h2 = i + 1 < wt->depth ? w.blk[i + 1].hin : w.hfin, fa.R = R, fa.B = B, fa.N = N;
+      fa.h2 = i + 1 < wt->depth ? w.hin[i + 1] : w.head_frag.f32, fa.R = R, fa.B = B, fa.N = N;
       // tile-major rows between the fused kernels (train_ff_fused.h): everything but the stem's output and the head's input
       // (+ h1 itself only as what the backward kernels want of it: the xhat3 fragments and 1 / std, TL_H1_FRAG)
       fa.tiled = dfx::ffused::TL_H1 | (i > 0 ? dfx::ffused::TL_HIN : 0) | (i + 1 < wt->depth ? dfx::ffused::TL_H2 : 0) | dfx::ffused::TL_H1_FRAG;
-      fa.at_frags = w.at_frags[i], fa.valid = w.valid, fa.g2 = bw.norm2_w, fa.b2n = bw.norm2_b, fa.bo = bw.to_out_b;
-      fa.hin = a.hin, fa.h1_out = a.h1;
+      fa.at_frags = w.at_frags[i], fa.valid = c.valid, fa.g2 = bw.norm2_w, fa.b2n = bw.norm2_b, fa.bo = bw.to_out_b;
+      fa.hin = w.hin[i], fa.h1_out = w.h1_frag[i].f32;
       if (i + 1 == wt->depth) fa.tiled |= dfx::ffused::TL_HEAD, fa.head_tab = w.head_tab, fa.eps = io.eps;   // post_norm + proj_out in this kernel's epilogue
-      if (dropout_p > 0.f) {   // the two sites of block i (the layer-by-layer path's numbering); bits -> a.p (R x 32 floats, unused by the fused path; 80 B per point needed)
+      if (dropout_p > 0.f) {   // the two sites of block i (the layer-by-layer path's numbering); the bits stay in dmask[i] for the backward
         fa.dk = dfx::drop_key(dropout_seed, dropout_p), fa.site_att = (unsigned)(2 * i), fa.site_ff = (unsigned)(2 * i + 1);
-        fa.dmask = reinterpret_cast<unsigned *>(a.p);
+        fa.dmask = w.dmask[i];
       }
     }
 #if !defined(DFX_TRACE_FF) || defined(DFX_TRACE_FF_CHAIN)
@@ -2345,56 +2342,57 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
     const int prec = plan.prec;
     const bool bf = plan.bf_store;
     const dfx_denoiser_weights *grads = io.grads;
+    const LayeredWs &w = ws.layered;
     // proj_out, post_norm
     const int nb = (int)((R + EPSB_ROWS - 1) / EPSB_ROWS);
-    k_eps_bwd<<<nb, 128, 0, st>>>(io.d_eps, w.hn, wt->proj_out_w, w.dh2, w.part, N, R);
-    k_sum_parts<<<3 * C / 32, 1024, 0, st>>>(w.part, mut(grads->proj_out_w), nb, 3 * C, 4 * C);
-    k_sum_parts<<<1, 1024, 0, st>>>(w.part + 3 * C, mut(grads->proj_out_b), nb, 3, 4 * C);
-    if ((rc = ln_bwd(st, w, w.dh2, w.hfin, w.st_post, wt->post_norm_w, nullptr, w.dh, mut(grads->post_norm_w), mut(grads->post_norm_b), R))) return rc;
-    DFX_HIP_TRY(hipMemsetAsync(w.dctx, 0, sizeof(float) * (size_t)BJ * CTXP, st));
+    k_eps_bwd<<<nb, 128, 0, st>>>(io.d_eps, w.hn, wt->proj_out_w, w.dh2, c.pb.part, N, R);
+    k_sum_parts<<<3 * C / 32, 1024, 0, st>>>(c.pb.part, mut(grads->proj_out_w), nb, 3 * C, 4 * C);
+    k_sum_parts<<<1, 1024, 0, st>>>(c.pb.part + 3 * C, mut(grads->proj_out_b), nb, 3, 4 * C);
+    if ((rc = ln_bwd(st, c.pb, w.dh2, w.hfin, w.st_post, wt->post_norm_w, nullptr, w.dh, mut(grads->post_norm_w), mut(grads->post_norm_b), R))) return rc;
+    DFX_HIP_TRY(hipMemsetAsync(c.dctx, 0, sizeof(float) * (size_t)BJ * CTXP, st));
     for (int i = wt->depth - 1; i >= 0; --i) {
       const dfx_block_weights &bw = wt->blk[i], &gw = grads->blk[i];
-      BlockAct &a = w.blk[i];
+      const LayerAct &a = w.blk[i];
       // feed-forward: h2 = h1 + W2 hid + b2, hid = a gelu(g), [a | g] = W1 xn3 + b1
-      if ((rc = wgrad(st, prec, w, w.dh, C, a.hid, FH, mut(gw.ff2_w), mut(gw.ff2_b), C, FH, FH, R, false, bf))) return rc;
-      transpose(st, bw.ff2_w, w.wT, C, FH);                                    // (512, 128)
-      if ((rc = lin(st, prec, w.dh, C, w.wT, nullptr, w.dhid, FH, R, FH, C))) return rc;
+      if ((rc = wgrad(st, prec, c.pb, w.dh, C, a.hid, FH, mut(gw.ff2_w), mut(gw.ff2_b), C, FH, FH, R, false, bf))) return rc;
+      transpose(st, bw.ff2_w, c.wT, C, FH);                                    // (512, 128)
+      if ((rc = lin(st, prec, w.dh, C, c.wT, nullptr, w.dhid, FH, R, FH, C))) return rc;
       const Drop dff{dropout_p, dropout_seed, (unsigned)(2 * i + 1)};
       if (bf) k_geglu_bwd<true><<<(int)((R * FH / 4 + 255) / 256), 256, 0, st>>>(a.ag, w.dhid, w.dwide, FH, R * FH, dff);
       else k_geglu_bwd<false><<<(int)((R * FH / 4 + 255) / 256), 256, 0, st>>>(a.ag, w.dhid, w.dwide, FH, R * FH, dff);
-      if ((rc = wgrad(st, prec, w, w.dwide, 2 * FH, a.xn3, C, mut(gw.ff0_w), mut(gw.ff0_b), 2 * FH, C, C, R, bf, bf))) return rc;
-      transpose(st, bw.ff0_w, w.wT, 2 * FH, C);                                // (128, 1024)
-      if ((rc = lin(st, prec, w.dwide, 2 * FH, w.wT, nullptr, w.dh2, C, R, C, 2 * FH, nullptr, 0, bf))) return rc;
-      if ((rc = ln_bwd(st, w, w.dh2, a.h1, a.st3, bw.norm3_w, w.dh, w.dh, mut(gw.norm3_w), mut(gw.norm3_b), R))) return rc;
+      if ((rc = wgrad(st, prec, c.pb, w.dwide, 2 * FH, a.xn3, C, mut(gw.ff0_w), mut(gw.ff0_b), 2 * FH, C, C, R, bf, bf))) return rc;
+      transpose(st, bw.ff0_w, c.wT, 2 * FH, C);                                // (128, 1024)
+      if ((rc = lin(st, prec, w.dwide, 2 * FH, c.wT, nullptr, w.dh2, C, R, C, 2 * FH, nullptr, 0, bf))) return rc;
+      if ((rc = ln_bwd(st, c.pb, w.dh2, a.h1, a.st3, bw.norm3_w, w.dh, w.dh, mut(gw.norm3_w), mut(gw.norm3_b), R))) return rc;
       // attention: h1 = hin + Wo att + bo
       const float *dho = w.dh;   // gradient at the output of to_out: dh behind the dropout
       if (dropout_p > 0.f) {
         k_dropout<<<(int)((R * C / 4 + 255) / 256), 256, 0, st>>>(w.dh, nullptr, w.dh2, R * C, Drop{dropout_p, dropout_seed, (unsigned)(2 * i)});
         dho = w.dh2;
       }
-      if ((rc = wgrad(st, prec, w, dho, C, a.att, C, mut(gw.to_out_w), mut(gw.to_out_b), C, C, C, R, false, bf))) return rc;
-      transpose(st, bw.to_out_w, w.wT, C, C);
-      if ((rc = lin(st, prec, dho, C, w.wT, nullptr, w.datt, C, R, C, C))) return rc;
+      if ((rc = wgrad(st, prec, c.pb, dho, C, a.att, C, mut(gw.to_out_w), mut(gw.to_out_b), C, C, C, R, false, bf))) return rc;
+      transpose(st, bw.to_out_w, c.wT, C, C);
+      if ((rc = lin(st, prec, dho, C, c.wT, nullptr, w.datt, C, R, C, C))) return rc;
       const int nab = (N + ATT_BP - 1) / ATT_BP;
       if (bf) k_attn_bwd<true><<<dim3(nab, B), 256, 0, st>>>(w.datt, a.q, a.k, a.v, a.p, w.dq, w.apart, N);
       else k_attn_bwd<false><<<dim3(nab, B), 256, 0, st>>>(w.datt, a.q, a.k, a.v, a.p, w.dq, w.apart, N);
       k_attn_bwd_finish<<<B, J * C, 0, st>>>(w.apart, w.dk, w.dv, nab);
-      if ((rc = wgrad(st, prec, w, w.dq, C, a.xn2, C, mut(gw.to_q), nullptr, C, C, C, R, bf, bf))) return rc;
-      transpose(st, bw.to_q, w.wT, C, C);
-      if ((rc = lin(st, prec, w.dq, C, w.wT, nullptr, w.dh2, C, R, C, C, nullptr, 0, bf))) return rc;
-      if ((rc = ln_bwd(st, w, w.dh2, a.hin, a.st2, bw.norm2_w, w.dh, w.dh, mut(gw.norm2_w), mut(gw.norm2_b), R))) return rc;
+      if ((rc = wgrad(st, prec, c.pb, w.dq, C, a.xn2, C, mut(gw.to_q), nullptr, C, C, C, R, bf, bf))) return rc;
+      transpose(st, bw.to_q, c.wT, C, C);
+      if ((rc = lin(st, prec, w.dq, C, c.wT, nullptr, w.dh2, C, R, C, C, nullptr, 0, bf))) return rc;
+      if ((rc = ln_bwd(st, c.pb, w.dh2, a.hin, a.st2, bw.norm2_w, w.dh, w.dh, mut(gw.norm2_w), mut(gw.norm2_b), R))) return rc;
       // keys / values of the 4 context tokens
-      if ((rc = wgrad(st, prec, w, w.dk, C, w.ctx, CTXP, mut(gw.to_k), nullptr, C, CTXP, CTX, BJ))) return rc;
-      if ((rc = wgrad(st, prec, w, w.dv, C, w.ctx, CTXP, mut(gw.to_v), nullptr, C, CTXP, CTX, BJ))) return rc;
-      DFX_HIP_TRY(hipMemsetAsync(w.wT, 0, sizeof(float) * (size_t)CTXP * C, st));
-      transpose(st, bw.to_k, w.wT, C, CTX);                                    // (522 -> 528 rows of 128)
-      if ((rc = lin(st, prec, w.dk, C, w.wT, nullptr, w.dctx, CTXP, BJ, CTXP, C, w.dctx, CTXP))) return rc;
-      transpose(st, bw.to_v, w.wT, C, CTX);
-      if ((rc = lin(st, prec, w.dv, C, w.wT, nullptr, w.dctx, CTXP, BJ, CTXP, C, w.dctx, CTXP))) return rc;
+      if ((rc = wgrad(st, prec, c.pb, w.dk, C, c.ctx, CTXP, mut(gw.to_k), nullptr, C, CTXP, CTX, BJ))) return rc;
+      if ((rc = wgrad(st, prec, c.pb, w.dv, C, c.ctx, CTXP, mut(gw.to_v), nullptr, C, CTXP, CTX, BJ))) return rc;
+      DFX_HIP_TRY(hipMemsetAsync(c.wT, 0, sizeof(float) * (size_t)CTXP * C, st));
+      transpose(st, bw.to_k, c.wT, C, CTX);                                    // (522 -> 528 rows of 128)
+      if ((rc = lin(st, prec, w.dk, C, c.wT, nullptr, c.dctx, CTXP, BJ, CTXP, C, c.dctx, CTXP))) return rc;
+      transpose(st, bw.to_v, c.wT, C, CTX);
+      if ((rc = lin(st, prec, w.dv, C, c.wT, nullptr, c.dctx, CTXP, BJ, CTXP, C, c.dctx, CTXP))) return rc;
     }
     // pre_norm, proj_in
-    if ((rc = ln_bwd(st, w, w.dh, w.h0, w.st_pre, wt->pre_norm_w, nullptr, w.dh2, mut(grads->pre_norm_w), mut(grads->pre_norm_b), R))) return rc;
-    if ((rc = wgrad(st, prec, w, w.dh2, C, w.xin, XIN, mut(grads->proj_in_w), mut(grads->proj_in_b), C, XIN, 13, R))) return rc;
+    if ((rc = ln_bwd(st, c.pb, w.dh, w.h0, w.st_pre, wt->pre_norm_w, nullptr, w.dh2, mut(grads->pre_norm_w), mut(grads->pre_norm_b), R))) return rc;
+    if ((rc = wgrad(st, prec, c.pb, w.dh2, C, c.xin, XIN, mut(grads->proj_in_w), mut(grads->proj_in_b), C, XIN, 13, R))) return rc;
     if ((rc = backward_tail(io, w.dh))) return rc;
     return dfx::check_launch("denoiser_train_backward");
   }
@@ -2403,18 +2401,18 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
     int rc;
     const int prec = plan.prec;
     const dfx_denoiser_weights *grads = io.grads;
+    const FusedWs &w = ws.fused;
     // Parameter-gradient reductions that nothing on the way back to the input waits for run on the side stream (joined before the return):
-    // the head's and the stem's partial sums — in buffers of their own (w.hn, w.datt: free on the fused path), because the products behind
-    // the block loop use w.part on the caller's stream meanwhile — and the leaves of the finishing kernels behind the block loop.
+    // the head's and the stem's partial sums — in scratch of their own (w.side), because the products behind the block loop use c.pb on
+    // the caller's stream meanwhile — and the leaves of the finishing kernels behind the block loop.
     dfx::SideStream ss;
     if ((rc = ss.open(st, side.bwd_open))) return rc;
     const dfx::TrainStreams so = ss.on ? side : dfx::TrainStreams{};   // (a caller beyond the side streams' cap gets none: everything on its own stream)
     hipStream_t sp = ss.side;
     // proj_out, post_norm
     const int nbh = (int)((R + HEAD_ROWS - 1) / HEAD_ROWS);
-    float *hp = w.hn;
-    k_head_bwd<<<nbh, 256, 0, st>>>(io.d_eps, w.hfin, wt->post_norm_w, wt->post_norm_b, wt->proj_out_w, w.dh, hp, N, R);
-    auto head_sums = [&](hipStream_t s) {
+    k_head_bwd<<<nbh, 256, 0, st>>>(io.d_eps, w.head_frag.f32, wt->post_norm_w, wt->post_norm_b, wt->proj_out_w, w.dh_pair[0].f32, w.side.head_part, N, R);
+    auto head_sums = [&, hp = w.side.head_part](hipStream_t s) {
       k_sum_parts<<<3 * C / 32, 1024, 0, s>>>(hp, mut(grads->proj_out_w), nbh, 3 * C, HEAD_PART);
       k_sum_parts_multi<<<2 * C / 32, 1024, 0, s>>>(hp + 3 * C, SumOuts{{mut(grads->post_norm_w), mut(grads->post_norm_b), nullptr, nullptr}}, nbh, C, HEAD_PART);
       k_sum_parts<<<1, 1024, 0, s>>>(hp + 5 * C, mut(grads->proj_out_b), nbh, 3, HEAD_PART);
@@ -2424,48 +2422,47 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
       if ((rc = ss.fork())) return rc;
       head_sums(sp);
     }
-    DFX_HIP_TRY(hipMemsetAsync(w.dctx, 0, sizeof(float) * (size_t)BJ * CTXP, st));
-    float *dh_cur = w.dh;   // the gradient of the residual stream: where the next kernel on the way back finds it
-    auto stem_backward = [&](hipStream_t s, float *part) {   // pre_norm, proj_in: reads dh_cur, the input rows and the weights
+    DFX_HIP_TRY(hipMemsetAsync(c.dctx, 0, sizeof(float) * (size_t)BJ * CTXP, st));
+    int cur = 0;   // the gradient of the residual stream: which of dh_pair the next kernel on the way back finds it in
+    auto stem_backward = [&](hipStream_t s, float *part) {   // pre_norm, proj_in: reads dh_pair[cur] (fp32 rows by then), the input rows and the weights
       const int nb = (int)((R + STEM_ROWS - 1) / STEM_ROWS);
-      k_stem_bwd<<<nb, 256, 0, s>>>(dh_cur, w.xin, wt->proj_in_w, wt->proj_in_b, wt->pre_norm_w, part, R);
-      k_sum_parts<<<C * 13 / 32, 1024, 0, s>>>(part, mut(grads->proj_in_w), nb, C * 13, 2048);
-      k_sum_parts_multi<<<3 * C / 32, 1024, 0, s>>>(part + C * 13, SumOuts{{mut(grads->proj_in_b), mut(grads->pre_norm_w), mut(grads->pre_norm_b), nullptr}}, nb, C, 2048);
+      k_stem_bwd<<<nb, 256, 0, s>>>(w.dh_pair[cur].f32, c.xin, wt->proj_in_w, wt->proj_in_b, wt->pre_norm_w, part, R);
+      k_sum_parts<<<C * 13 / 32, 1024, 0, s>>>(part, mut(grads->proj_in_w), nb, C * 13, STEM_PART);
+      k_sum_parts_multi<<<3 * C / 32, 1024, 0, s>>>(part + C * 13, SumOuts{{mut(grads->proj_in_b), mut(grads->pre_norm_w), mut(grads->pre_norm_b), nullptr}}, nb, C, STEM_PART);
     };
     for (int i = wt->depth - 1; i >= 0; --i) {
       const dfx_block_weights &bw = wt->blk[i];
-      BlockAct &a = w.blk[i];
       // feed-forward and attention sub-block, one pass over the points (k_ff_bwd): [a | g] recomputed from the xhat3 fragments the forward left,
       // d hid = W2^T dh, GEGLU backward, dxn3 = W1^T d[a | g], LayerNorm3 backward -> dh1, the attention's input gradient -> dh_in.
       // The gradient travels from the head through the blocks as bf16-pair tiles (train_ff_fused.h, TL_DH_HL; k_head_bwd writes the pair format
-      // too), alternating between w.dh and w.dh2 (k_ff_wgrad reads block i's INCOMING gradient after k_ff_bwd has written the outgoing one);
-      // block 0 writes the fp32 rows the stem reads (dh_cur behind the loop).  + the layouts the forward left behind
-      const float *dh_in_blk = dh_cur;
+      // too), alternating between the two dh_pair (k_ff_wgrad reads block i's INCOMING gradient after k_ff_bwd has written the outgoing one);
+      // block 0 writes the fp32 rows the stem reads (dh_pair[cur] behind the loop).  + the layouts the forward left behind
+      const Tiles &dh_blk = w.dh_pair[cur];
+      cur ^= 1;
       dfx::ffused::FfArgs fa{};
       fa.frags = w.ff_frags[i], fa.b1p = w.ff_b1p[i], fa.b2p = w.ff_b2p[i], fa.g3 = bw.norm3_w, fa.b3 = bw.norm3_b;
-      fa.h1 = a.h1, fa.dh = dh_in_blk, fa.cpart = w.cpart[i], fa.R = R, fa.B = B, fa.N = N;
+      fa.h1 = w.h1_frag[i].f32, fa.dh = dh_blk.f32, fa.cpart = w.cpart[i], fa.R = R, fa.B = B, fa.N = N;
       fa.tiled = dfx::ffused::TL_H1 | (i > 0 ? dfx::ffused::TL_HIN | dfx::ffused::TL_DHIN | dfx::ffused::TL_DHIN_HL : 0) |
                  (i + 1 < wt->depth ? dfx::ffused::TL_DH : 0) | dfx::ffused::TL_DH_HL | dfx::ffused::TL_H1_FRAG;
-      fa.at_frags = w.at_frags[i], fa.valid = w.valid, fa.g2 = bw.norm2_w, fa.b2n = bw.norm2_b, fa.bo = bw.to_out_b;
-      fa.hin = a.hin, fa.dh_in = dh_cur = (dh_cur == w.dh ? w.dh2 : w.dh);
-      fa.pk2 = reinterpret_cast<uint4 *>(w.dq);   // xn2 / dh1 as fragments for the parameter kernel (w.dq: free in this path)
-      if (dropout_p > 0.f) {   // the bits the forward left in a.p
+      fa.at_frags = w.at_frags[i], fa.valid = c.valid, fa.g2 = bw.norm2_w, fa.b2n = bw.norm2_b, fa.bo = bw.to_out_b;
+      fa.hin = w.hin[i], fa.dh_in = w.dh_pair[cur].f32;
+      fa.pk2 = w.pk2;   // xn2 / dh1 as fragments for the parameter kernel
+      if (dropout_p > 0.f) {   // the bits the forward left
         fa.dk = dfx::drop_key(dropout_seed, dropout_p), fa.site_att = (unsigned)(2 * i), fa.site_ff = (unsigned)(2 * i + 1);
-        fa.dmask = reinterpret_cast<unsigned *>(a.p);
+        fa.dmask = w.dmask[i];
       }
       if (dfx::ffused::launch_ff_bwd(st, fa)) return dfx::set_error(DFX_ERR_HIP, "train: fused feed-forward backward launch");
-      if (i == 0 && so.stem_early) {   // w.dh is final: pre_norm / proj_in backward beside the rest of the block's parameter kernels
+      if (i == 0 && so.stem_early) {   // dh_pair[cur] is final: pre_norm / proj_in backward beside the rest of the block's parameter kernels
         if ((rc = ss.fork())) return rc;
-        stem_backward(sp, w.datt);
+        stem_backward(sp, w.side.stem_part);
       }
-      // dW1, db1, dW2: weight-stationary, hid and d[a | g] recomputed from the forward's xhat3 fragments (a.h1) and the hi halves of the block's incoming
+      // dW1, db1, dW2: weight-stationary, hid and d[a | g] recomputed from the forward's xhat3 fragments (h1_frag) and the hi halves of the block's incoming
       // gradient; the slab partials of every block are summed in one launch behind the loop (as are the six column sums k_ff_bwd left in cpart)
-      dfx::ffused::FwArgs wa{w.ff_frags[i], w.ff_b1p[i] + dfx::ffused::B1P_FLOATS, reinterpret_cast<const uint4 *>(a.h1), w.ffw_part[i], w.ffw_bpart[i],
-                             R / 32, w.ffw_slabs, dropout_p > 0.f ? reinterpret_cast<const unsigned *>(a.p) : nullptr,
-                             reinterpret_cast<const uint4 *>(dh_in_blk)};
+      dfx::ffused::FwArgs wa{w.ff_frags[i], w.ff_b1p[i] + dfx::ffused::B1P_FLOATS, w.h1_frag[i].u4, w.ffw_part[i], w.ffw_bpart[i],
+                             R / 32, w.ffw_slabs, dropout_p > 0.f ? w.dmask[i] : nullptr, dh_blk.u4};
       if (dfx::ffused::launch_ff_wgrad(st, wa)) return dfx::set_error(DFX_ERR_HIP, "train: feed-forward weight-gradient launch");
       // attention, parameter side (train_attn_fused.h): dA_s, dM_s per shape from the xn2 / dh1 fragments
-      dfx::afused::AttnArgs aa{w.at_frags[i], w.valid, w.at_part[i], reinterpret_cast<const uint4 *>(w.dq), N, w.at_split};
+      dfx::afused::AttnArgs aa{w.at_frags[i], c.valid, w.at_part[i], w.pk2, N, w.at_split};
       dfx::afused::k_attn_bwd_param<<<B * w.at_split, dfx::afused::NW * 64, 0, st>>>(aa);
     }
     {
@@ -2479,7 +2476,7 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
         const dfx_block_weights &bw = wt->blk[i], &gw = grads->blk[i];
         fb.blk[i] = dfx::ffused::FwFinishArgs{w.ffw_part[i], w.ffw_bpart[i], mut(gw.ff0_w), mut(gw.ff0_b), mut(gw.ff2_w), w.ffw_slabs,
                                               dropout_p > 0.f ? 1.0f / (1.0f - dropout_p) : 1.0f, bw.norm3_w, bw.norm3_b, bw.ff0_w,
-                                              w.ffw_lnpart[i], mut(gw.norm3_w), mut(gw.norm3_b)};   // (d gamma3 / d beta3: k_ln3_param behind the slab sums)
+                                              w.side.ffw_lnpart[i], mut(gw.norm3_w), mut(gw.norm3_b)};   // (d gamma3 / d beta3: k_ln3_param behind the slab sums)
         ub.blk[i] = dfx::afused::UnfoldArgs{w.at_part[i], w.kv + 2 * i * C, w.kv + (2 * i + 1) * C, bw.to_q, bw.to_out_w, w.dkv + 2 * i * C, w.dkv + (2 * i + 1) * C,
                                             mut(gw.to_q), mut(gw.to_out_w), w.at_sum[i], B, w.at_split, LDKV0};
         sj.part[i] = w.cpart[i];
@@ -2491,7 +2488,7 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
       if ((rc = ss.fork())) return rc;
       hipStream_t sl = so.leaves ? sp : st;
       dfx::afused::k_attn_unfold_kv<<<dim3(dfx::afused::J, B, wt->depth), 256, 0, st>>>(ub);
-      if (so.stem_end) stem_backward(sp, w.datt);
+      if (so.stem_end) stem_backward(sp, w.side.stem_part);
       dfx::ffused::launch_ff_wgrad_finish(sl, fb, wt->depth);
       k_sum_parts_jobs<<<wt->depth * 6 * (C / 32), 1024, 0, sl>>>(sj, (int)dfx::ffused::ff_groups(B, N), C, 6 * C);
       if (head_late) head_sums(sp);
@@ -2499,16 +2496,16 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
       dfx::afused::k_attn_unfold_w<<<dim3(C / dfx::afused::UW_D, 1, wt->depth), 1024, 0, sl>>>(ub);
       // d Wk, d Wv of every block and d ctx from the side-by-side key / value gradients
       const int n2 = 2 * wt->depth, LDKV = n2 * C;
-      if ((rc = wgrad(st, prec, w, w.dkv, LDKV, w.ctx, CTXP, w.dwkv, nullptr, LDKV, CTXP, CTXP, BJ))) return rc;
+      if ((rc = wgrad(st, prec, c.pb, w.dkv, LDKV, c.ctx, CTXP, w.dwkv, nullptr, LDKV, CTXP, CTXP, BJ))) return rc;
       KvMutPtrs gp{};
       for (int i = 0; i < wt->depth; ++i) gp.p[2 * i] = mut(grads->blk[i].to_k), gp.p[2 * i + 1] = mut(grads->blk[i].to_v);
       k_unpack_kv<<<(n2 * C * CTX + 255) / 256, 256, 0, st>>>(w.dwkv, gp, n2);
       transpose(st, w.wkv, w.wkvT, LDKV, CTXP);                                  // (528 rows of 2 depth x 128)
-      if ((rc = lin(st, prec, w.dkv, LDKV, w.wkvT, nullptr, w.dctx, CTXP, BJ, CTXP, LDKV))) return rc;
+      if ((rc = lin(st, prec, w.dkv, LDKV, w.wkvT, nullptr, c.dctx, CTXP, BJ, CTXP, LDKV))) return rc;
     }
     // pre_norm, proj_in
-    if (!so.stem_early && !so.stem_end) stem_backward(st, w.part);
-    if ((rc = backward_tail(io, dh_cur))) return rc;
+    if (!so.stem_early && !so.stem_end) stem_backward(st, c.pb.part);   // not beside anything: on the caller's stream, with the caller's stream's scratch
+    if ((rc = backward_tail(io, w.dh_pair[cur].f32))) return rc;
     if ((rc = ss.join())) return rc;
     return dfx::check_launch("denoiser_train_backward");
   }
@@ -2519,14 +2516,14 @@ struct TrainStep {   // one call: weights, carved workspace, shape, plan, the ca
     const int prec = plan.prec;
     const dfx_denoiser_weights *grads = io.grads;
     // gradient at the input rows (optional)
-    if (io.d_x || io.d_variances) k_stem_dx<<<2048, 256, 0, st>>>(dh, w.xin, wt->proj_in_w, wt->proj_in_b, wt->pre_norm_w, io.d_x, io.d_variances, N, R);
+    if (io.d_x || io.d_variances) k_stem_dx<<<2048, 256, 0, st>>>(dh, c.xin, wt->proj_in_w, wt->proj_in_b, wt->pre_norm_w, io.d_x, io.d_variances, N, R);
     // context -> part codes, (mean, var), time embedding MLP
-    k_ctx_bwd<<<(B * CTX + 255) / 256, 256, 0, st>>>(w.dctx, io.d_ctx_code, io.d_ctx_mv, w.dte_out, B);
-    if ((rc = wgrad(st, prec, w, w.dte_out, TE, w.te_hid, TEH, mut(grads->te2_w), mut(grads->te2_b), TE, TEH, TEH, B))) return rc;
-    transpose(st, wt->te2_w, w.wT, TE, TEH);                                   // (1024, 256)
-    if ((rc = lin(st, prec, w.dte_out, TE, w.wT, nullptr, w.dte_hid, TEH, B, TEH, TE))) return rc;
-    k_geglu_bwd<false><<<(int)(((long long)B * TEH / 4 + 255) / 256), 256, 0, st>>>(w.te_ag, w.dte_hid, w.dte_ag, TEH, (long long)B * TEH, Drop{dropout_p, dropout_seed, SITE_TE});
-    return wgrad(st, prec, w, w.dte_ag, 2 * TEH, w.te_in, TE, mut(grads->te0_w), mut(grads->te0_b), 2 * TEH, TE, TE, B);
+    k_ctx_bwd<<<(B * CTX + 255) / 256, 256, 0, st>>>(c.dctx, io.d_ctx_code, io.d_ctx_mv, c.dte_out, B);
+    if ((rc = wgrad(st, prec, c.pb, c.dte_out, TE, c.te_hid, TEH, mut(grads->te2_w), mut(grads->te2_b), TE, TEH, TEH, B))) return rc;
+    transpose(st, wt->te2_w, c.wT, TE, TEH);                                   // (1024, 256)
+    if ((rc = lin(st, prec, c.dte_out, TE, c.wT, nullptr, c.dte_hid, TEH, B, TEH, TE))) return rc;
+    k_geglu_bwd<false><<<(int)(((long long)B * TEH / 4 + 255) / 256), 256, 0, st>>>(c.te_ag, c.dte_hid, c.dte_ag, TEH, (long long)B * TEH, Drop{dropout_p, dropout_seed, SITE_TE});
+    return wgrad(st, prec, c.pb, c.dte_ag, 2 * TEH, c.te_in, TE, mut(grads->te0_w), mut(grads->te0_b), 2 * TEH, TE, TE, B);
   }
 };
 }  // namespace
@@ -2536,7 +2533,8 @@ extern "C" {
 size_t dfx_denoiser_train_workspace_bytes(int B, int N, int depth) {
   if (B < 1 || N < 32 || depth < 1 || depth > DFX_MAX_DEPTH) return 0;
   TrainWs t;
-  return carve(t, nullptr, B, N, depth);
+  const size_t n = carve(t, nullptr, B, N, depth);
+  return t.miss ? 0 : n;   // (check_args names the view)
 }
 
 int dfx_denoiser_train_forward(const dfx_denoiser_weights *wt, void *workspace, size_t workspace_bytes, const float *x,
@@ -2633,11 +2631,11 @@ int dfx_pointnet_v2_train_forward(const dfx_pointnet_v2_weights *wt, void *works
     if (precision == DFX_PREC_F32 && g_bn_fused_stats) {
       LinArgs la{};
       la.X = in, la.ldx = K, la.W = l == 0 ? w.wpad : wt->conv_w[l], la.b = wt->conv_b[l], la.Y = w.z[l], la.ldy = Co, la.M = (int)R, la.N = Co, la.K = K;
-      la.stats = w.pb.part;
-      if ((size_t)std::min<long long>((R + 255) / 256, 512) * Co * 3 <= w.pb.part_floats) parts = dfx::lin::launch_wide_lds_stats(st, la);
+      la.stats = w.bn.pb.part;
+      if ((size_t)std::min<long long>((R + 255) / 256, 512) * Co * 3 <= w.bn.pb.part_floats) parts = dfx::lin::launch_wide_lds_stats(st, la);
     }
     if (!parts && (rc = lin(st, precision, in, K, l == 0 ? w.wpad : wt->conv_w[l], wt->conv_b[l], w.z[l], Co, R, Co, K))) return rc;
-    if ((rc = bn_fwd(st, w, w.z[l], R, Co, wt->bn_w[l], wt->bn_b[l], mut(wt->bn_mean[l]), mut(wt->bn_var[l]), momentum, wt->bn_eps,
+    if ((rc = bn_fwd(st, w.bn, w.z[l], R, Co, wt->bn_w[l], wt->bn_b[l], mut(wt->bn_mean[l]), mut(wt->bn_var[l]), momentum, wt->bn_eps,
                      w.mean[l], w.rstd[l], w.y[l], l < 3, l < 3, parts))) return rc;
   }
   const float scale = wt->reweight_by_anchor ? (float)A : 1.0f;
@@ -2647,7 +2645,7 @@ int dfx_pointnet_v2_train_forward(const dfx_pointnet_v2_weights *wt, void *works
     const float *in = w.pooled;
     for (int l = 0; l < 2; ++l) {
       if ((rc = glin(st, in, wt->head_w[k][l], wt->head_b[k][l], w.hz[k][l], B, A, hc[l], hc[l + 1]))) return rc;
-      if ((rc = bn_fwd(st, w, w.hz[k][l], B, A * hc[l + 1], wt->head_bn_w[k][l], wt->head_bn_b[k][l], mut(wt->head_bn_mean[k][l]),
+      if ((rc = bn_fwd(st, w.bn, w.hz[k][l], B, A * hc[l + 1], wt->head_bn_w[k][l], wt->head_bn_b[k][l], mut(wt->head_bn_mean[k][l]),
                        mut(wt->head_bn_var[k][l]), momentum, wt->bn_eps, w.hmean[k][l], w.hrstd[k][l], w.hy[k][l], true))) return rc;
       in = w.hy[k][l];
     }
@@ -2677,7 +2675,7 @@ int dfx_pointnet_v2_train_backward(const dfx_pointnet_v2_weights *wt, void *work
       const float *in = l == 0 ? w.pooled : w.hy[k][l - 1];
       const float *dz = dcur;
       if (l < 2) {   // through relu + BatchNorm over the B rows
-        if ((rc = bn_bwd(st, w, dcur, wt->head_bn_b[k][l], w.hz[k][l], B, A * cout, wt->head_bn_w[k][l], w.hmean[k][l], w.hrstd[k][l], w.dh[1],
+        if ((rc = bn_bwd(st, w.bn, dcur, wt->head_bn_b[k][l], w.hz[k][l], B, A * cout, wt->head_bn_w[k][l], w.hmean[k][l], w.hrstd[k][l], w.dh[1],
                          mut(grads->head_bn_w[k][l]), mut(grads->head_bn_b[k][l]), true))) return rc;
         dz = w.dh[1];
       }
@@ -2695,7 +2693,7 @@ int dfx_pointnet_v2_train_backward(const dfx_pointnet_v2_weights *wt, void *work
         } else if ((rc = lin_g4<dfx::lin::EPI_NONE>(st, dz, A * cout, cout, nullptr, nullptr, w.wT, wt_gs, w.dh[0], A * cin, cin, B, cin, cout))) return rc;
       } else
       for (int a = 0; a < A; ++a) {   // per-part weights: group a of the grouped 1x1 convolution
-        if ((rc = wgrad(st, precision, w.pb, dz + a * cout, A * cout, in + a * cin, A * cin, mut(grads->head_w[k][l]) + (size_t)a * cout * cin,
+        if ((rc = wgrad(st, precision, w.bn.pb, dz + a * cout, A * cout, in + a * cin, A * cin, mut(grads->head_w[k][l]) + (size_t)a * cout * cin,
                         mut(grads->head_b[k][l]) + a * cout, cout, cin, cin, B))) return rc;
         transpose(st, wt->head_w[k][l] + (size_t)a * cout * cin, w.wT, cout, cin);   // (cin, cout)
         if (l == 0) {   // d pooled accumulates over the two heads
@@ -2719,8 +2717,8 @@ int dfx_pointnet_v2_train_backward(const dfx_pointnet_v2_weights *wt, void *work
   }
   for (int l = 3; l >= 0; --l) {
     const int K = PN_C[l], Co = PN_C[l + 1];
-    if (l < 3 && (rc = bn_bwd(st, w, dy, wt->bn_b[l], w.z[l], R, Co, wt->bn_w[l], w.mean[l], w.rstd[l], dz, mut(grads->bn_w[l]), mut(grads->bn_b[l]), true))) return rc;
-    if ((rc = wgrad(st, precision, w.pb, dz, Co, l == 0 ? w.X8 : w.y[l - 1], K, mut(grads->conv_w[l]), mut(grads->conv_b[l]), Co, K, l == 0 ? 3 : K, R))) return rc;
+    if (l < 3 && (rc = bn_bwd(st, w.bn, dy, wt->bn_b[l], w.z[l], R, Co, wt->bn_w[l], w.mean[l], w.rstd[l], dz, mut(grads->bn_w[l]), mut(grads->bn_b[l]), true))) return rc;
+    if ((rc = wgrad(st, precision, w.bn.pb, dz, Co, l == 0 ? w.X8 : w.y[l - 1], K, mut(grads->conv_w[l]), mut(grads->conv_b[l]), Co, K, l == 0 ? 3 : K, R))) return rc;
     if (l > 0) {
       transpose(st, wt->conv_w[l], w.wT, Co, K);   // (K, Co)
       if ((rc = lin(st, precision, dz, Co, w.wT, nullptr, dy, K, R, K, Co))) return rc;
@@ -2848,7 +2846,7 @@ int dfx_shared_mlp_train_forward(const dfx_shared_mlp_train *t, void *workspace,
     const bool relu = (t->relu_mask >> l) & 1u;
     const float *act = w.y[l];
     if (t->bn_w[l] && batch_stats) {
-      if ((rc = bn_fwd(st, w.pn, w.z[l], R, co, t->bn_w[l], t->bn_b[l], t->bn_mean[l], t->bn_var[l], momentum, t->bn_eps, w.mean[l], w.rstd[l], w.y[l], relu))) return rc;
+      if ((rc = bn_fwd(st, w.bn, w.z[l], R, co, t->bn_w[l], t->bn_b[l], t->bn_mean[l], t->bn_var[l], momentum, t->bn_eps, w.mean[l], w.rstd[l], w.y[l], relu))) return rc;
     } else if (t->bn_w[l]) {   // eval(): running statistics, nothing updated
       if (!t->bn_mean[l] || !t->bn_var[l]) return dfx::set_error(DFX_ERR_INVALID_ARG, "shared_mlp_train_forward: layer %d: running statistics required", l);
       k_smt_running_stats<<<(co + 255) / 256, 256, 0, st>>>(t->bn_mean[l], t->bn_var[l], w.mean[l], w.rstd[l], t->bn_eps, co);
@@ -2890,13 +2888,13 @@ int dfx_shared_mlp_train_backward(const dfx_shared_mlp_train *t, void *workspace
     const float *xin = l == 0 ? w.rows0 : plain_below ? w.z[l - 1] : w.y[l - 1];
     float *dz = other;
     if (t->bn_w[l]) {
-      if ((rc = bn_bwd(st, w.pn, dy, t->bn_b[l], w.z[l], R, co, t->bn_w[l], w.mean[l], w.rstd[l], dz, mut(grads->bn_w[l]), mut(grads->bn_b[l]), relu, batch_stats != 0))) return rc;
+      if ((rc = bn_bwd(st, w.bn, dy, t->bn_b[l], w.z[l], R, co, t->bn_w[l], w.mean[l], w.rstd[l], dz, mut(grads->bn_w[l]), mut(grads->bn_b[l]), relu, batch_stats != 0))) return rc;
     } else if (relu) {
       k_smt_relu_bwd<<<(int)((R * co + 255) / 256), 256, 0, st>>>(dy, w.z[l], dz, R * co);
     } else {
       dz = dy;   // plain linear layer
     }
-    if ((rc = wgrad(st, DFX_PREC_F32, w.pn.pb, dz, co, xin, ci, mut(grads->conv_w[l]), t->conv_b[l] ? mut(grads->conv_b[l]) : nullptr, co, ci, ci_valid, R))) return rc;
+    if ((rc = wgrad(st, DFX_PREC_F32, w.bn.pb, dz, co, xin, ci, mut(grads->conv_w[l]), t->conv_b[l] ? mut(grads->conv_b[l]) : nullptr, co, ci, ci_valid, R))) return rc;
     if (l > 0 || d_x) {   // d (input rows) = dz W
       const float *W = t->conv_w[l];
       if (ci != ci_valid) {
@@ -2964,8 +2962,7 @@ int dfx_debug_prior_loss_branch(const void *workspace, size_t workspace_bytes, i
   DFX_REQUIRE(flow_depth >= 1 && flow_depth <= DFX_MAX_FLOW_DEPTH && flow_hidden >= 8 && flow_hidden % 8 == 0 && B >= 1,
               "debug_prior_loss_branch: depth %d hidden %d B %d", flow_depth, flow_hidden, B);
   FlowWs w;
-  DFX_REQUIRE(workspace_bytes >= carve_flow(w, nullptr, B, flow_depth, flow_hidden), "debug_prior_loss_branch: workspace too small");
-  DFX_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "debug_prior_loss_branch: workspace must be 256-byte aligned");
+  if (int rc = check_ws(carve_flow(w, nullptr, B, flow_depth, flow_hidden), workspace, workspace_bytes, "debug_prior_loss_branch")) return rc;
   hipStream_t st = dfx::as_stream(stream);
   carve_flow(w, const_cast<void *>(workspace), B, flow_depth, flow_hidden);
   const long long n = (long long)NPART * B * flow_hidden;
