@@ -355,8 +355,44 @@ __device__ __forceinline__ void load16(v16f &v, const float *src) {
 }
 
 // Masked softmax over the 4 keys of each head, in place (registers 4g..4g+3 = keys 0..3 of head 2g+hf; attention.py:195-198).
-template <bool FAST_RCP = false>   // bf16 kernels: the hardware reciprocal (1 ulp) instead of the correctly rounded division (~10 VALU instructions, four per block)
+// bf16 kernels (softmax4<true>, every one of them through this function): on register pairs, as ln_stats_fast.  The max-subtract and the exp's scale
+// (__expf = v_exp_f32 of x * log2(e)) take the pairs (0, 1) and (2, 3) of a head; the sum and the multiply by the reciprocal take the SAME key of two
+// neighbouring heads side by side, so that every half is the operation it always was, in the order it always was (0 + e0 + e1 + e2 + e3), and the bits
+// hold for every key mask (tests/test_gpu_softmax_masks_bits.py).  The mask select, the max, v_exp_f32 and v_rcp_f32 have no packed form.  The
+// hardware reciprocal (1 ulp) stands for the correctly rounded division (~10 VALU instructions, four per block).
+__device__ __forceinline__ void softmax4_pk(v16f &sim, unsigned vmask) {
+  const v2f l2e = splat2(1.44269504088896340736f);
+#pragma unroll
+  for (int gp = 0; gp < 2; ++gp) {   // heads 2gp and 2gp + 1 of this half-wave
+    float e[2][4];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int g = 2 * gp + u;
+      float sj[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) sj[j] = (vmask >> j) & 1u ? sim[4 * g + j] : -3.402823466e38f;  // :195-197
+      const v2f m2 = splat2(fmaxf(fmaxf(sj[0], sj[1]), fmaxf(sj[2], sj[3])));
+      const v2f t01 = (v2f{sj[0], sj[1]} - m2) * l2e, t23 = (v2f{sj[2], sj[3]} - m2) * l2e;
+      e[u][0] = __builtin_amdgcn_exp2f(t01[0]), e[u][1] = __builtin_amdgcn_exp2f(t01[1]);
+      e[u][2] = __builtin_amdgcn_exp2f(t23[0]), e[u][3] = __builtin_amdgcn_exp2f(t23[1]);
+    }
+    v2f sum = {0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sum += v2f{e[0][j], e[1][j]};
+    const v2f inv = {__builtin_amdgcn_rcpf(sum[0]), __builtin_amdgcn_rcpf(sum[1])};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const v2f pr = v2f{e[0][j], e[1][j]} * inv;
+      sim[8 * gp + j] = pr[0], sim[8 * gp + 4 + j] = pr[1];
+    }
+  }
+}
+template <bool FAST_RCP = false>   // true: the bf16 kernels (softmax4_pk)
 __device__ __forceinline__ void softmax4(v16f &sim, unsigned vmask) {
+  if constexpr (FAST_RCP) {
+    softmax4_pk(sim, vmask);
+    return;
+  }
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
     float sj[4];
@@ -369,7 +405,7 @@ __device__ __forceinline__ void softmax4(v16f &sim, unsigned vmask) {
       e[j] = __expf(sj[j] - m);
       sum += e[j];
     }
-    const float inv = FAST_RCP ? __builtin_amdgcn_rcpf(sum) : 1.0f / sum;
+    const float inv = 1.0f / sum;
 #pragma unroll
     for (int j = 0; j < 4; ++j) sim[4 * g + j] = e[j] * inv;
   }
@@ -583,7 +619,7 @@ __device__ __forceinline__ void ff_chunk(v16f (&h)[4], const Act<DFX_PREC_F32> (
 //   * a VALU instruction next to MFMAs costs ~3.1 cycles of SIMD issue (transcendentals ~10), every MFMA takes
 //     ~18 cycles of VALU issue away: T(SIMD) ~ max(32.6 nMFMA, 3.1 nVALU + 10 nTRANS + 18 nMFMA);
 //   * packed fp32 VALU (v_pk_mul/fma/add_f32) serialises against the matrix pipe: never in an M or V slot of the feed-forward
-//     (the library is built with -fno-slp-vectorize, +10 %); the V0 / V2 slots and the step boundary do use it (ln_stats_fast);
+//     (the library is built with -fno-slp-vectorize, +10 %); the V0 / V1 / V2 slots and the step boundary do use it (ln_stats_fast, softmax4_pk);
 //   * LDS delivers ~240 B/clk/CU with eight wavefronts reading; one wavefront sustains ~32 B/clk (latency bound).
 __device__ __forceinline__ v8bf as_bf(const uint4 &u) { return __builtin_bit_cast(v8bf, u); }
 
@@ -756,24 +792,9 @@ __device__ __forceinline__ void attn_m1(v16f (&h)[4], const Act<DFX_PREC_BF16> &
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// attention V slot: masked softmax over the 4 keys of each head (registers 4g..4g+3 = keys of head 2g+hf)
+// attention V slot: masked softmax over the 4 keys of each head (registers 4g..4g+3 = keys of head 2g+hf), on register pairs
 __device__ __forceinline__ void attn_softmax(v16f &sim, Act<DFX_PREC_BF16> &pa, unsigned vmask) {
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    float sj[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sj[j] = (vmask >> j) & 1u ? sim[4 * g + j] : -3.402823466e38f;  // attention.py:195-197
-    const float m = fmaxf(fmaxf(sj[0], sj[1]), fmaxf(sj[2], sj[3]));
-    float e[4], sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      e[j] = __expf(sj[j] - m);
-      sum += e[j];
-    }
-    const float inv = __builtin_amdgcn_rcpf(sum);   // (as softmax4<true>: every bf16 kernel takes the same reciprocal; +0.25 % in a same-box A/B)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sim[4 * g + j] = e[j] * inv;
-  }
+  softmax4_pk(sim, vmask);   // (every bf16 kernel takes the same reciprocal; +0.25 % in a same-box A/B)
   pa.set(sim);
 }
 
@@ -1148,6 +1169,32 @@ struct DmaState {
   const char *ff_src;         // this wave's window of the next FF record
 };
 
+// The attention record of block st.b for shape s: 17 KiB shape record | 5 KiB block constants | 1 KiB c_t row | 1 padding piece.  Everything here is
+// wave-uniform, and it is spelled so that it STAYS on the scalar unit (the record is prepared right in front of a V slot, whose issue slots are the
+// wavefront's critical path): the shape record's offset is one 32 x 32 -> 64-bit product of scalar registers (written as (size_t)s * depth it shared the
+// 64-bit copy of `s` that the per-lane addresses keep in a VGPR pair, and the product, the pointer and the selects behind it all ran on the VALU), and the
+// timestep is looked up once, by the one wavefront whose pieces include the c_t row, not once per piece.
+struct AttnRecord {
+  const char *as, *bconst, *ct_row;
+  unsigned ring, bc, dummy;   // LDS: the ring slot, this block's block-constant buffer, the padding sink
+  __device__ __forceinline__ void piece(int q, const char *&src, unsigned &dst) const {
+    src = bconst, dst = dummy;
+    if (q < 17) src = as + q * 1024, dst = ring + q * 1024;
+    else if (q < 22) src = bconst + (q - 17) * 1024, dst = bc + (q - 17) * 1024;
+    else if (q == 22) src = ct_row, dst = ring + 17 * 1024;
+  }
+};
+__device__ __forceinline__ AttnRecord attn_record(const KParams &p, const DmaState &st, const BlockPack &bp, int q0, int nc, unsigned ring, unsigned lds0, int s) {
+  AttnRecord r;
+  const unsigned rec = (unsigned)__builtin_amdgcn_readfirstlane(s * p.d.depth + st.b);
+  r.as = reinterpret_cast<const char *>(p.as_ms) + (unsigned long long)rec * (unsigned)asms_bytes(DFX_PREC_BF16);
+  r.bconst = reinterpret_cast<const char *>(bp.bconst);
+  r.ct_row = r.bconst;
+  if (q0 <= 22 && 22 < q0 + nc) r.ct_row = reinterpret_cast<const char *>(bp.ct + (size_t)step_t(p, st.step, s) * CT_ROW);
+  r.ring = ring, r.bc = lds0 + L_BCONST + (st.seq & 1) * BCONST_BYTES, r.dummy = lds0 + L_DUMMY;
+  return r;
+}
+
 // Issue this wave's pieces (CALLS_A / CALLS_B of them, starting at piece q0) of the next record and advance the state.
 template <int NC>
 __device__ __forceinline__ void issue_pieces(const KParams &p, DmaState &st, int q0, unsigned voff, unsigned lds0, int s) {
@@ -1160,21 +1207,12 @@ __device__ __forceinline__ void issue_pieces(const KParams &p, DmaState &st, int
     st.ff_src += SLOT_BYTES;
   } else {  // attention record: 17 KiB shape record | 5 KiB block constants | 1 KiB c_t row | 1 padding piece
     const BlockPack bp = block_pack(p, st.b);
+    const AttnRecord ar = attn_record(p, st, bp, q0, NC, ring, lds0, s);
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
-      const int q = q0 + j;
-      const char *src = reinterpret_cast<const char *>(bp.bconst);
-      unsigned dst = lds0 + L_DUMMY;
-      if (q < 17) {
-        src = reinterpret_cast<const char *>(p.as_ms) + ((size_t)s * p.d.depth + st.b) * asms_bytes(DFX_PREC_BF16) + q * 1024;
-        dst = ring + q * 1024;
-      } else if (q < 22) {
-        src = reinterpret_cast<const char *>(bp.bconst) + (q - 17) * 1024;
-        dst = lds0 + L_BCONST + (st.seq & 1) * BCONST_BYTES + (q - 17) * 1024;
-      } else if (q == 22) {
-        src = reinterpret_cast<const char *>(bp.ct + (size_t)step_t(p, st.step, s) * CT_ROW);
-        dst = ring + 17 * 1024;
-      }
+      const char *src;
+      unsigned dst;
+      ar.piece(q0 + j, src, dst);
       dma1k_pinned(src, voff, dst);
     }
     st.ff_src = reinterpret_cast<const char *>(bp.chunks) + q0 * 1024;
@@ -1200,23 +1238,13 @@ __device__ __forceinline__ void prepare_pieces(const KParams &p, DmaState &st, i
     st.ff_src += SLOT_BYTES;
   } else {
     const BlockPack bp = block_pack(p, st.b);
+    const AttnRecord ar = attn_record(p, st, bp, q0, NC, ring, lds0, s);
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
-      const int q = q0 + j;
-      const char *src = reinterpret_cast<const char *>(bp.bconst);
-      unsigned dst = lds0 + L_DUMMY;
-      if (q < 17) {
-        src = reinterpret_cast<const char *>(p.as_ms) + ((size_t)s * p.d.depth + st.b) * asms_bytes(DFX_PREC_BF16) + q * 1024;
-        dst = ring + q * 1024;
-      } else if (q < 22) {
-        src = reinterpret_cast<const char *>(bp.bconst) + (q - 17) * 1024;
-        dst = lds0 + L_BCONST + (st.seq & 1) * BCONST_BYTES + (q - 17) * 1024;
-      } else if (q == 22) {
-        src = reinterpret_cast<const char *>(bp.ct + (size_t)step_t(p, st.step, s) * CT_ROW);
-        dst = ring + 17 * 1024;
-      }
-      // (the 64-bit address arithmetic above may run on the VALU: back to scalar registers for the "s" operands of the DMA)
-      pc.src[j] = pin_ptr(src), pc.dst[j] = (unsigned)__builtin_amdgcn_readfirstlane(dst);
+      const char *src;
+      unsigned dst;
+      ar.piece(q0 + j, src, dst);
+      pc.src[j] = pin_ptr(src), pc.dst[j] = (unsigned)__builtin_amdgcn_readfirstlane(dst);   // (the "s" operands of the DMA: no-ops on scalar registers)
     }
     st.ff_src = reinterpret_cast<const char *>(bp.chunks) + q0 * 1024;
   }

@@ -6,7 +6,13 @@
 // per MFMA) issued as 4 v_fma_f32 or as 2 v_pk_fma_f32 — what a packed fp32 instruction costs the full chip against the two scalar ones
 // it replaces.  M16 rows: every v_mfma_f32_32x32x16 replaced by the two v_mfma_f32_16x16x32 (one per 16-point N-tile, same A fragment)
 // of the chain kernels' feed-forward; "per MFMA" then means per such pair.
-// Usage: pair_issue [iters = 2000]
+// ORDER rows (pair_issue <iters> order): the 16x16x32 stream with the feed-forward's mix (one refill and 5 v_pk per fragment, two MFMAs per fragment: one per
+// N-tile b0 / b1), the SAME MFMAs and accumulators in three issue orders — what the order of operand changes costs the full chip:
+//   (a) today's:        (A1,N0) (A1,N1) (A2,N0) (A2,N1)             A held for two MFMAs, B changes at every one: 1.5 operand changes per MFMA
+//   (b) boustrophedon:  (A1,N0) (A2,N0) (A2,N1) (A1,N1) (A3,N1) ... exactly one operand changes per MFMA
+//   (c) upper bracket:  (A1,N0) (A2,N1) (A3,N0) (A4,N1) (A1,N1) ... both operands change at every MFMA
+// Every row three times in one process, the rows interleaved, with each run's time and the row's spread.
+// Usage: pair_issue [iters = 2000] [order]
 // Build: hipcc --offload-arch=gfx950 -O3 pair_issue.hip -o _build/pair_issue
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -21,7 +27,7 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 // NV: 0, 3 or 5 fillers behind every MFMA.  PAIR: 1 = the two MFMAs of a pair share A; 0 = every MFMA its own A (+ its own refill)
 // F32: 0 = none, 1 = 4 v_fma_f32, 2 = 2 v_pk_fma_f32 behind every MFMA.  M16: 1 = pairs of 16x16x32 (C/D in the accumulator file)
 typedef float v2f __attribute__((ext_vector_type(2)));
-template <int ACC, int BA, int LDS, int NV, int PAIR, int F32 = 0, int M16 = 0>
+template <int ACC, int BA, int LDS, int NV, int PAIR, int F32 = 0, int M16 = 0, int ORD = 0>
 __global__ void __launch_bounds__(256, 1) k(unsigned long long *out, int iters) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
   for (int i = threadIdx.x; i < 32 * 1024 / 4; i += blockDim.x) {
@@ -78,8 +84,35 @@ __global__ void __launch_bounds__(256, 1) k(unsigned long long *out, int iters) 
     if (LDS) EMIT16("ds_read_b128 %[" fr "], %[la] offset:" #off "\n");                                                                  \
     if (LDS && !PAIR) EMIT16("ds_read_b128 %[" fr2 "], %[la] offset:" #off "+16384\n");                                                  \
     if (NV == 5) EMIT16(FILL); FILL32(ub, wb);
+  // ORDER rows: one MFMA / one refill / one counted wait per statement (the LDS returns in order: eight refills are in flight at a group's start)
+#define MF(d, f, b) EMIT16("v_mfma_f32_16x16x32_bf16 %[" d "], %[" f "], %[" b "], %[" d "]\n");
+#define RD(f, off) EMIT16("ds_read_b128 %[" f "], %[la] offset:" #off "\n");
+#define WT(n) EMIT16("s_waitcnt lgkmcnt(" #n ")\n");
+#define FL EMIT16(FILL);
+  // (a): accumulators (fr, b0) (fr, b1) (fr2, b0) (fr2, b1) = da db dc dd; every fragment refilled in place behind its second MFMA
+#define GA(da, db, dc, dd, fr, fr2, off) WT(7) MF(da, fr, "b0") MF(db, fr, "b1") RD(fr, off) FL WT(7) MF(dc, fr2, "b0") MF(dd, fr2, "b1") RD(fr2, off + 16384) FL
+  // (b): X / Y = the N-tile the group starts / ends with; ax = accumulator of (fr, X), ay of (fr, Y), cx of (fr2, X), cy of (fr2, Y); fr2 is refilled first
+#define GB(ax, ay, cx, cy, fr, fr2, X, Y, off) WT(6) MF(ax, fr, X) MF(cx, fr2, X) FL MF(cy, fr2, Y) RD(fr2, off + 16384) MF(ay, fr, Y) RD(fr, off) FL
+  // (c): four fragments, pX / pY = accumulator of (fragment p, X / Y)
+#define GC(fa, fb, fc, fd, aX, aY, bX, bY, cX, cY, dX, dY, X, Y, o1, o2)                                              \
+    WT(7) MF(aX, fa, X) WT(6) MF(bY, fb, Y) FL WT(5) MF(cX, fc, X) WT(4) MF(dY, fd, Y) FL                             \
+    MF(aY, fa, Y) RD(fa, o1) MF(bX, fb, X) RD(fb, o1 + 16384) FL MF(cY, fc, Y) RD(fc, o2) MF(dX, fd, X) RD(fd, o2 + 16384) FL
   for (int it = 0; it < iters; ++it) {
-    if (M16) {
+    if (ORD == 1) {
+      GA("d0", "d1", "d2", "d3", "f0", "f1", 1024) GA("d4", "d5", "d6", "d7", "f2", "f3", 2048) GA("d0", "d1", "d2", "d3", "f4", "f5", 3072)
+      GA("d4", "d5", "d6", "d7", "f6", "f7", 4096) GA("d0", "d1", "d2", "d3", "f0", "f1", 5120) GA("d4", "d5", "d6", "d7", "f2", "f3", 6144)
+      GA("d0", "d1", "d2", "d3", "f4", "f5", 7168) GA("d4", "d5", "d6", "d7", "f6", "f7", 8192)
+    } else if (ORD == 2) {
+      GB("d0", "d1", "d2", "d3", "f0", "f1", "b0", "b1", 1024) GB("d5", "d4", "d7", "d6", "f2", "f3", "b1", "b0", 2048)
+      GB("d0", "d1", "d2", "d3", "f4", "f5", "b0", "b1", 3072) GB("d5", "d4", "d7", "d6", "f6", "f7", "b1", "b0", 4096)
+      GB("d0", "d1", "d2", "d3", "f0", "f1", "b0", "b1", 5120) GB("d5", "d4", "d7", "d6", "f2", "f3", "b1", "b0", 6144)
+      GB("d0", "d1", "d2", "d3", "f4", "f5", "b0", "b1", 7168) GB("d5", "d4", "d7", "d6", "f6", "f7", "b1", "b0", 8192)
+    } else if (ORD == 3) {
+      GC("f0", "f1", "f2", "f3", "d0", "d1", "d2", "d3", "d4", "d5", "d6", "d7", "b0", "b1", 1024, 2048)
+      GC("f4", "f5", "f6", "f7", "d1", "d0", "d3", "d2", "d5", "d4", "d7", "d6", "b1", "b0", 3072, 4096)
+      GC("f0", "f1", "f2", "f3", "d0", "d1", "d2", "d3", "d4", "d5", "d6", "d7", "b0", "b1", 5120, 6144)
+      GC("f4", "f5", "f6", "f7", "d1", "d0", "d3", "d2", "d5", "d4", "d7", "d6", "b1", "b0", 7168, 8192)
+    } else if (M16) {
       GRP16("d0", "d1", "d2", "d3", "f0", "f1", 1024) GRP16("d4", "d5", "d6", "d7", "f2", "f3", 2048) GRP16("d0", "d1", "d2", "d3", "f4", "f5", 3072)
       GRP16("d4", "d5", "d6", "d7", "f6", "f7", 4096) GRP16("d0", "d1", "d2", "d3", "f0", "f1", 5120) GRP16("d4", "d5", "d6", "d7", "f2", "f3", 6144)
       GRP16("d0", "d1", "d2", "d3", "f4", "f5", 7168) GRP16("d4", "d5", "d6", "d7", "f6", "f7", 8192)
@@ -123,8 +156,54 @@ void run(const char *name, int blocks) {
   hipFree(d);
 }
 
+// ORDER rows: one timed launch -> milliseconds and block 0's shader cycles per fragment (pair of MFMAs)
+template <int ORD>
+void run_order(int blocks, float &ms, double &cyc) {
+  unsigned long long *d;
+  hipMalloc(&d, 16);
+  auto kern = k<1, 0, 1, 5, 0, 0, 1, ORD>;
+  hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+  kern<<<blocks, 256, 64 * 1024>>>(d, 10);
+  hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
+  hipEventRecord(a);
+  kern<<<blocks, 256, 64 * 1024>>>(d, g_iters);
+  hipEventRecord(b);
+  hipDeviceSynchronize();
+  hipEventElapsedTime(&ms, a, b);
+  unsigned long long h[2];
+  hipMemcpy(h, d, 16, hipMemcpyDeviceToHost);
+  cyc = (double)h[0] / (g_iters * 16.0);
+  hipEventDestroy(a); hipEventDestroy(b);
+  hipFree(d);
+}
+
+int order_rows() {
+  const char *names[3] = {"(a) A held for two, B alternating (today)", "(b) boustrophedon: one operand change per MFMA", "(c) both operands change at every MFMA"};
+  float ms[3][3];
+  double cyc[3];
+  for (int r = 0; r < 3; ++r) {   // rows interleaved: a drift of the box falls on all three alike
+    run_order<1>(256, ms[0][r], cyc[0]);
+    run_order<2>(256, ms[1][r], cyc[1]);
+    run_order<3>(256, ms[2][r], cyc[2]);
+  }
+  printf("# 16x16x32 pairs, refill per pair, 5 v_pk per pair; %d iterations x 16 fragments, 256 blocks; cycles per fragment of block 0 (last run)\n", g_iters);
+  printf("# %-50s cycles  ms (3 runs)                 TFLOP/s (3 runs)      spread   GHz (last run)\n", "row");
+  for (int o = 0; o < 3; ++o) {
+    float lo = ms[o][0], hi = ms[o][0];
+    double tf[3];
+    for (int r = 0; r < 3; ++r) {
+      lo = ms[o][r] < lo ? ms[o][r] : lo, hi = ms[o][r] > hi ? ms[o][r] : hi;
+      tf[r] = 256 * 4.0 * g_iters * 16 * 32768.0 / (ms[o][r] * 1e-3) / 1e12;
+    }
+    printf("%-52s %6.1f  %9.3f %9.3f %9.3f   %6.0f %6.0f %6.0f  %6.2f %%   %.3f\n", names[o], cyc[o], ms[o][0], ms[o][1], ms[o][2], tf[0], tf[1], tf[2],
+           100.0 * (hi - lo) / lo, cyc[o] * 16.0 * g_iters / (ms[o][2] * 1e-3) / 1e9);
+  }
+  return 0;
+}
+
 int main(int argc, char **argv) {
   if (argc > 1) g_iters = atoi(argv[1]);
+  if (argc > 2 && argv[2][0] == 'o') return order_rows();
   for (int blocks : {1, 256}) {
     run<0, 0, 0, 0, 1>("C/D VGPR, B VGPR, no refill, no filler", blocks);
     run<1, 0, 0, 0, 1>("C/D AGPR, B VGPR, no refill, no filler", blocks);
