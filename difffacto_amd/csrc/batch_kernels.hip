@@ -367,7 +367,9 @@ __global__ void __launch_bounds__(NT) k_batch_build(BuildArgs a) {
   build_item(cx, it);
 }
 
-// ---- draws: Philox4x32-7 (dfx_dropout.h), key = seed, counter = (group of four values, purpose, sample_id) ----
+// ---- draws: Philox4x32-7 (dfx_dropout.h), key = seed, counter = (group of four values, purpose, sample_id lo, sample_id hi) ----
+// choice = (word * M) >> 32, unit floats = (word >> 8) 2^-24; value i of an item is word i & 3 of group i >> 2.  DESIGN.md "Random streams" lists the
+// layout; tests/test_gpu_random_streams.py holds the draws to oracle/philox.py bit for bit.
 constexpr unsigned DRAW_CHOICE = 0xBA7C0u, DRAW_DROP = 0xBA7C1u, DRAW_AUG = 0xBA7C2u;
 __device__ __forceinline__ float unit_float(unsigned w) { return (float)(w >> 8) * (1.0f / 16777216.0f); }   // 24 bits: [0,1)
 

@@ -235,7 +235,11 @@ __device__ __forceinline__ void add_cvec(v16f (&h)[4], const float *__restrict__
 }
 
 // ----------------------------------------------------------------------------------------------
-// Philox4x32-10 counter RNG + Box-Muller (perf runs; parity runs feed explicit noise).
+// Philox4x32-10 counter RNG + Box-Muller (perf runs; parity runs feed explicit noise).  Counter = (gid lo, gid hi, t, stream), key = (seed lo,
+// seed hi); gid = (shape_offset + b) N + n with the N of the launch (the engine's padded one); stream 0 = the noise of timestep t, stream 1 = a
+// start draw (x_T keyed by T, the refine start keyed by n_steps).  Three normals from four 24-bit uniforms ((w >> 8) + 0.5) 2^-24: (r(u0) cos, r(u0) sin)
+// of 2 pi u1 and r(u2) cos 2 pi u3.  DESIGN.md "Random streams" lists the layout; tests/test_gpu_random_streams.py judges every entry point and
+// kernel variant against oracle/philox.py in units of z.
 __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
 #pragma unroll
   for (int i = 0; i < 10; ++i) {

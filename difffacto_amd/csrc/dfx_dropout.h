@@ -3,6 +3,8 @@
 //   factor(seed, site, element i) = draw(seed, site, i) < thr ? 0 : 1 / (1 - p),      thr = round(p 2^16), capped at 2^16 - 1
 //   draw = 16 bits of Philox4x32-7 keyed by the step's 64-bit seed, counter = (i >> 3 = group of EIGHT consecutive elements of the site's
 //          row-major tensor, site, 0xD20F0): word e >> 1 of the output, half e & 1 (low half first) for element e = i & 7 of the group
+//   The four counter words are (group lo, group hi, site, 0xD20F0) and the key is (seed lo, seed hi).  DESIGN.md "Random streams" lists this layout
+//   beside the library's other streams; oracle/philox.py restates it and tests/test_gpu_random_streams.py holds the factors to that, bit for bit.
 //
 // Round 5: eight elements per call (16-bit draws; the probability resolution 2^-16 biases E[factor] by < 8e-6) and seven rounds (Philox4x32-7 is
 // the smallest variant Salmon et al. report as passing BigCrush; -10 is their safety-margin default) instead of four 32-bit draws of Philox4x32-10:

@@ -333,8 +333,12 @@ __device__ __forceinline__ uint4 philox4x32_10(unsigned c0, unsigned c1, unsigne
 // unit draw in [0,1) with 24 random bits, as torch.rand's float32
 __device__ __forceinline__ float unit24(unsigned w) { return (float)(w >> 8) * 0x1p-24f; }
 
+// Counter = (point, DRAW_BOX | class * 2 + side, pair lo, pair hi), key = seed; words 0..2 are used, word 3 is discarded (DESIGN.md "Random
+// streams").  The tag keeps this layout apart from the chain noise's (gid lo, gid hi, t, stream), the other Philox4x32-10 stream: without it
+// (p, 0, pair, 0) was the chain's counter of point p at t = pair under the same seed.
+constexpr unsigned DRAW_BOX = 0xB0C50000u;
 __device__ __forceinline__ float3 box_unit(unsigned long long seed, unsigned long long gpair, int c, int side, int p) {
-  const uint4 r = philox4x32_10((unsigned)p, (unsigned)(c * 2 + side), (unsigned)gpair, (unsigned)(gpair >> 32), (unsigned)seed,
+  const uint4 r = philox4x32_10((unsigned)p, DRAW_BOX | (unsigned)(c * 2 + side), (unsigned)gpair, (unsigned)(gpair >> 32), (unsigned)seed,
                                 (unsigned)(seed >> 32));
   return make_float3(unit24(r.x), unit24(r.y), unit24(r.z));
 }

@@ -302,14 +302,17 @@ __host__ __device__ void fit_group(Ctx &cx, const float *mean, const float *logv
   }
 }
 
-// ---- draws: Philox4x32-7 (dfx_dropout.h), key = seed, counter = (group of four draws, purpose | axis * 8 + part, global row) ----
+// ---- draws: Philox4x32-7 (dfx_dropout.h), key = seed, counter = (group of four draws, purpose | axis * 8 + part, global row lo, hi) ----
+// DESIGN.md "Random streams" lists the layout; tests/test_gpu_random_streams.py judges the normals against oracle/philox.py in units of z.
 constexpr unsigned DRAW_PART = 0x9A570000u;
 
-// two standard normals from two words (Box-Muller on 24-bit uniforms; u1 in (0,1])
+// two standard normals from two words (Box-Muller on 24-bit uniforms; u1 in (0,1), u2 in [0,1)).  The angle 2 pi u2 goes through cospif / sinpif
+// on the exact 2 u2: the float32 2 pi is 2.8e-8 too large, which as `cosf(6.2831855f * u2)` shifted the mean of the even draws by +3.5e-8
+// (E[r] E[t sin t] / 2 pi times that) — 24 standard errors in tests/test_gpu_random_streams.py's comparison with the float64 statement.
 __device__ __forceinline__ void box_muller(unsigned a, unsigned b, float *n0, float *n1) {
   const float u1 = ((float)(a >> 8) + 0.5f) * 0x1p-24f, u2 = (float)(b >> 8) * 0x1p-24f;
-  const float r = sqrtf(-2.0f * logf(u1)), t = 6.283185307179586f * u2;
-  *n0 = r * cosf(t), *n1 = r * sinf(t);
+  const float r = sqrtf(-2.0f * logf(u1)), t = 2.0f * u2;
+  *n0 = r * cospif(t), *n1 = r * sinpif(t);
 }
 // draws 4 g .. 4 g + 3 of (row, axis c, part j)
 __device__ __forceinline__ void normals4(unsigned long long seed, unsigned long long row, int c, int j, int g, float *n) {

@@ -309,8 +309,8 @@ int dfx_part_clouds_f32(const float *xyz, const int32_t *labels, int B, int N, i
  * else a term; D = fp32 mean of the terms (NaN without any).  metric 0 = l2 (mean squared difference of [(hi-lo)/2, (hi+lo)/2]),
  * 1 = iou (1 - mean IoU in double, boxes read as the reference's get_3d_box at heading 0 reads (l,w,h): x-extent dx, y-extent dz,
  * z-extent dy), 2 = chamfer (512 points uniform in each box, u (hi-lo) + lo, then Chamfer-L2).  Chamfer draws: units (P,C,2,512,3)
- * device, P = Ma*Mb local pairs i*Mb + j, side 0 = A; or units NULL = Philox4x32-10 keyed by seed, counter (point, class*2 + side,
- * global pair (row0 + i)*Mb + j): any split of the rows into launches gives the same matrix. */
+ * device, P = Ma*Mb local pairs i*Mb + j, side 0 = A; or units NULL = Philox4x32-10 keyed by seed, counter (point, 0xB0C50000 | class*2 + side,
+ * global pair (row0 + i)*Mb + j, low word first; DESIGN.md "Random streams"): any split of the rows into launches gives the same matrix. */
 int dfx_part_box_pairwise_f32(const float *boxes_a, const int32_t *present_a, int Ma, const float *boxes_b,
                               const int32_t *present_b, int Mb, int C, int metric, uint64_t seed, long long row0,
                               const float *units, float *D, dfx_stream_t stream);
