@@ -11,7 +11,8 @@
 //   Larger n (<= 8192): only the targets in LDS, the state in the caller's workspace (every phase then pays an L2 round trip).
 //   Bid: a wavefront per unassigned point, lanes strided over the targets, branch-free running (best, second best, first index),
 //   merged over the wavefront by three single-word DPP reductions (the merge keeps the reference's result: first maximum in index
-//   order, :152-178).  The scan is VALU-bound (correctly rounded sqrtf + the reference's double-precision `3.0 - d - price`).
+//   order, :152-178, for n <= 2048; for larger n first in the order in which the reference's threads walk its 2048-target
+//   batches — the KEYED kernels, see `key` below).  The scan is VALU-bound (correctly rounded sqrtf + the reference's double-precision `3.0 - d - price`).
 //   Tail (<= 8 unassigned, 85 % of the iterations): 8 wavefronts share the bidders' scans, wavefront 0 merges their partials and
 //   does GetMax and Assign in registers, one lane per bidder — two workgroup barriers per iteration.
 //   GetMax's data race (several bidders within 1e-6 of the maximum all write max_idx, :195-199) is resolved deterministically:
@@ -105,7 +106,7 @@ __device__ __forceinline__ Best wave_merge(const Best &m) {
   return r;
 }
 
-template <bool STATE_LDS>
+template <bool STATE_LDS, bool KEYED>
 __global__ __launch_bounds__(EMD_THREADS) void k_emd(const float *__restrict__ xyz1, const float *__restrict__ xyz2, float eps,
                                                     int iters, float *__restrict__ dist, int32_t *__restrict__ assignment,
                                                     int32_t *__restrict__ wsi, float *__restrict__ wsf, int n) {
@@ -155,7 +156,19 @@ __global__ __launch_bounds__(EMD_THREADS) void k_emd(const float *__restrict__ x
                                // tid 0 is lane 0 of wavefront 0, which also stores the count of the <= 8 bidder path: same lane, program order)
     constexpr int NWAVES = EMD_THREADS / 64;
     // ---- Bid (:102-186): a wavefront walks the targets for one unassigned point, lanes strided, keeping (best, second best, first index
-    // of the best); the lanes' triples are merged with the reference's result (first maximum in index order, :152-178) ----
+    // of the best); the lanes' triples are merged with the reference's result (first maximum in ITS scan order, :152-178) ----
+    // The reference gives a bidder tpu = 1024 / ceil(U / (n / 1024)) threads (:108-109); thread t walks the chunk [t delta, (t + 1) delta),
+    // delta = ceil(end_k / tpu), of every 2048-target batch in turn (:125-158), and the chunks are merged in thread order with strict
+    // compares (:165-173).  Among equal maxima the first in the order (t, batch, k) wins: plain k order for one batch (n <= 2048), and
+    // the order of key(k) = t(k) << 13 | k for more (k < 8192, t < 1024; within a thread batch-then-k is ascending k).  KEYED kernels
+    // break ties by that key (a tie is rare on real clouds: one branch in the scan); the second best is a value and needs no order.
+    int key_dfull = 2048, key_dlast = 2048, key_k2last = 0;
+    if (KEYED) {
+      const int blocks = (n + 1023) >> 10, tpu = 1024 / ((U + blocks - 1) / blocks);   // (n / 1024 rounded up: the reference takes multiples only)
+      key_k2last = ((n - 1) >> 11) << 11;
+      key_dfull = (2048 + tpu - 1) / tpu, key_dlast = (n - key_k2last + tpu - 1) / tpu;
+    }
+    auto key = [&](int k) { return k < 0 ? k : ((((k & 2047) / (k >= key_k2last ? key_dlast : key_dfull)) << 13) | k); };
     auto bid_scan = [&](int j, int first, int stride_log2) {
       Best m{-1e9f, -1e9f, -1};
       const float x1 = STATE_LDS ? XA[j] : A[j * 3], y1 = STATE_LDS ? XA[n + j] : A[j * 3 + 1], z1 = STATE_LDS ? XA[2 * n + j] : A[j * 3 + 2];
@@ -171,6 +184,9 @@ __global__ __launch_bounds__(EMD_THREADS) void k_emd(const float *__restrict__ x
           const float r = decltype(lib)::value ? sqrtf(s) : sqrt_rn_normal(s, tiny);
           const float d = (float)(3.0 - (double)r - (double)t.w);   // `3.0` is a double literal in the reference (:151)
           m.better = __builtin_amdgcn_fmed3f(m.best, m.better, d);   // best >= better: the median = (d > best ? best : d > better ? d : better)
+          if (KEYED) {
+            if (d == m.best && (unsigned)key(k) < (unsigned)key(m.idx)) m.idx = k;   // a later k of an earlier reference thread
+          }
           m.idx = d > m.best ? k : m.idx;
           m.best = fmaxf(m.best, d);
         };
@@ -186,6 +202,7 @@ __global__ __launch_bounds__(EMD_THREADS) void k_emd(const float *__restrict__ x
         scan(std::true_type{});
       }
       EMD_T(1);
+      if (KEYED) m.idx = key(m.idx);   // from here to the end of the merges the index travels as its key: smaller key = earlier in the reference's order
       m = wave_merge(m);
       EMD_T(2);
       return m;
@@ -216,7 +233,7 @@ __global__ __launch_bounds__(EMD_THREADS) void k_emd(const float *__restrict__ x
         float inc = 0.f;
         if (lane < U) {
 #pragma clang fp contract(off)
-          j = list[lane], k = m.idx, inc = m.best - m.better + eps;
+          j = list[lane], k = KEYED ? (m.idx & 8191) : m.idx, inc = m.best - m.better + eps;
         }
         EMD_T(4);
         // GetMax among at most 8 lanes, in registers (max_inc / max_idx are scratch of one iteration — every target that receives bids has
@@ -265,9 +282,10 @@ __global__ __launch_bounds__(EMD_THREADS) void k_emd(const float *__restrict__ x
         if (lane == 0) {
 #pragma clang fp contract(off)
           const float inc = m.best - m.better + eps;
-          bid[j] = m.idx;
+          const int k = KEYED ? (m.idx & 8191) : m.idx;
+          bid[j] = k;
           bid_inc[j] = inc;
-          atomicMax(reinterpret_cast<int *>(max_inc) + m.idx, __float_as_int(inc));   // inc > 0 vs stored 0 / -1e9: int order = float order
+          atomicMax(reinterpret_cast<int *>(max_inc) + k, __float_as_int(inc));   // inc > 0 vs stored 0 / -1e9: int order = float order
         }
       }
     }
@@ -334,16 +352,23 @@ int dfx_emd_forward_f32(const float *xyz1, const float *xyz2, float *dist, int32
   DFX_REQUIRE(xyz1 && xyz2 && dist && assignment && workspace, "emd_forward: null pointer");
   static dfx::PerDeviceOnce attrs;
   DFX_HIP_TRY(attrs.run([] {
-    hipError_t e = dfx::set_max_lds(reinterpret_cast<const void *>(k_emd<false>), 8192 * 16);
-    if (e == hipSuccess) e = dfx::set_max_lds(reinterpret_cast<const void *>(k_emd<true>), EMD_STATE_LDS_MAX_N * 60);
+    hipError_t e = dfx::set_max_lds(reinterpret_cast<const void *>(k_emd<false, false>), 8192 * 16);
+    if (e == hipSuccess) e = dfx::set_max_lds(reinterpret_cast<const void *>(k_emd<false, true>), 8192 * 16);
+    if (e == hipSuccess) e = dfx::set_max_lds(reinterpret_cast<const void *>(k_emd<true, false>), EMD_STATE_LDS_MAX_N * 60);
+    if (e == hipSuccess) e = dfx::set_max_lds(reinterpret_cast<const void *>(k_emd<true, true>), EMD_STATE_LDS_MAX_N * 60);
     return e;
   }));
   int32_t *wsi = static_cast<int32_t *>(workspace);
   float *wsf = reinterpret_cast<float *>(wsi + (size_t)B * 5 * n);
-  if (n <= EMD_STATE_LDS_MAX_N && !g_emd_state_global)   // targets + prices (16 B), the auction state (32 B) and the bidders (12 B) per point in LDS
-    k_emd<true><<<B, EMD_THREADS, n * 60, dfx::as_stream(stream)>>>(xyz1, xyz2, eps, iters, dist, assignment, wsi, wsf, n);
-  else
-    k_emd<false><<<B, EMD_THREADS, n * 16, dfx::as_stream(stream)>>>(xyz1, xyz2, eps, iters, dist, assignment, wsi, wsf, n);
+  const bool state_lds = n <= EMD_STATE_LDS_MAX_N && !g_emd_state_global;   // targets + prices (16 B), the auction state (32 B) and the bidders (12 B) per point in LDS
+  const bool keyed = n > 2048;   // more than one batch of the reference's Bid: ties follow its thread-major order, not k order
+  auto launch = [&](auto kernel, size_t lds_bytes) {
+    kernel<<<B, EMD_THREADS, lds_bytes, dfx::as_stream(stream)>>>(xyz1, xyz2, eps, iters, dist, assignment, wsi, wsf, n);
+  };
+  if (state_lds && !keyed) launch(k_emd<true, false>, (size_t)n * 60);
+  else if (state_lds) launch(k_emd<true, true>, (size_t)n * 60);
+  else if (!keyed) launch(k_emd<false, false>, (size_t)n * 16);
+  else launch(k_emd<false, true>, (size_t)n * 16);
   return dfx::check_launch("emd_forward");
 }
 

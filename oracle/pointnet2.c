@@ -4,8 +4,9 @@
  *   pointnet2_ops_lib/pointnet2_ops/_ext-src/src/{sampling_gpu,ball_query_gpu,group_points_gpu,interpolate_gpu}.cu
  * as a serial loop nest with the same index order, the same comparisons and the same tie rules.
  *
- * PARITY UNPINNED for these kernels: the reference holds no tests/golden vectors for them and
- * its CUDA sources cannot be built here.  Two stated assumptions replace what cannot be observed:
+ * The reference holds no tests/golden vectors for these kernels.  FPS and the auction EMD are pinned to the reference's own kernel
+ * text run on the CPU (oracle/refkernels.py, tests/test_refkernels_cpu.py); the others to its pure-torch helpers.  Two stated
+ * assumptions replace what cannot be observed without nvcc:
  *   (1) float expressions of the form a*a + b*b + c*c are evaluated the way nvcc's default
  *       -fmad=true contracts them: t = a*a; t = fma(b,b,t); t = fma(c,c,t)  (helper sq3()),
  *       and p1*w1 + p2*w2 + p3*w3 likewise (mul, fma, fma).
@@ -262,8 +263,13 @@ void oracle_chamfer_grad(int b, int n, int m, const float *xyz1, const float *xy
  * after `iters` iterations CalcDist :225-234.  Sequential restatement with the kernels' scan order:
  *   - value of target k for bidder j: d = 3.0 - sqrtf(|x2_k - x1_j|^2) - price[k], evaluated in DOUBLE and rounded to
  *     float (`3.0` is a double literal, :151); the squared norm with nvcc's contraction (mul, fma, fma);
- *   - best = FIRST maximum in k order (strict '>' in the per-thread scans :152-160 and in the ordered merge :171-178),
- *     better = the second largest value; increment = best - better + eps (float);
+ *   - best = FIRST maximum in Bid's scan order (strict '>' in the per-thread scans :152-160 and in the ordered merge :171-178),
+ *     better = the second largest value; increment = best - better + eps (float).  The scan order: a bidder has
+ *     tpu = 1024 / ceil(unassigned / (n / 1024)) threads (:108-109); thread t walks its chunk [t delta, (t + 1) delta),
+ *     delta = ceil(end_k / tpu), of EVERY 2048-target batch in turn (:125-158), and the merge runs over the threads in order.
+ *     So the order is (t, batch, k): plain k order for n <= 2048 (one batch), not for larger n.  One running scan in that
+ *     order gives what the per-thread scans and their merge give: the same first maximum, and `better` is the second largest
+ *     value (with multiplicity) whatever the order.  (n / 1024 is rounded up here: the reference takes multiples of 1024 only);
  *   - GetMax lets every bidder whose increment is within 1e-6 (double compare, :195) of the target's maximum write
  *     max_idx: a data race in the reference; here the LARGEST bidder index wins (stated deviation, ties are rare);
  *   - the last iteration assigns every still-unassigned bidder to its bid without evicting (:209-211).
@@ -280,20 +286,30 @@ static void emd_forward_impl(int b, int n, const float *xyz1, const float *xyz2,
     for (int j = 0; j < n; ++j) as[j] = -1, ass_inv[j] = -1, price[j] = 0.f, max_inc[j] = 0.f, max_idx[j] = 0, bid[j] = 0, bid_inc[j] = 0.f;
     for (int it = 0; it < iters; ++it) {
       const int last = it == iters - 1;
-      int any = 0;
+      int any = 0, nun = 0, tpu = 1;
+      for (int j = 0; j < n; ++j) nun += as[j] == -1;
+      if (nun) {   /* :108-109 */
+        const int blocks = (n + 1023) / 1024, per_block = (nun + blocks - 1) / blocks;
+        tpu = 1024 / per_block;
+      }
       for (int j = 0; j < n; ++j) {
         if (as[j] != -1) continue;
         any = 1;
         float best = -1e9f, better = -1e9f;
         int best_i = -1;
         const float x1 = A[j * 3], y1 = A[j * 3 + 1], z1 = A[j * 3 + 2];
-        for (int k = 0; k < n; ++k) {
-          const float x2 = Bp[k * 3] - x1, y2 = Bp[k * 3 + 1] - y1, z2 = Bp[k * 3 + 2] - z1;
-          const float s = fmaf(z2, z2, fmaf(y2, y2, x2 * x2));
-          const float d = (float)(3.0 - (double)sqrtf(s) - (double)price[k]);
-          if (d > best) better = best, best = d, best_i = k;
-          else if (d > better) better = d;
-        }
+        for (int t = 0; t < tpu; ++t)
+          for (int k2 = 0; k2 < n; k2 += 2048) {
+            const int end_k = (n - k2 < 2048 ? n - k2 : 2048), delta = (end_k + tpu - 1) / tpu;
+            const int r = (t + 1) * delta < end_k ? (t + 1) * delta : end_k;
+            for (int k = k2 + t * delta; k < k2 + r; ++k) {
+              const float x2 = Bp[k * 3] - x1, y2 = Bp[k * 3 + 1] - y1, z2 = Bp[k * 3 + 2] - z1;
+              const float s = fmaf(z2, z2, fmaf(y2, y2, x2 * x2));
+              const float d = (float)(3.0 - (double)sqrtf(s) - (double)price[k]);
+              if (d > best) better = best, best = d, best_i = k;
+              else if (d > better) better = d;
+            }
+          }
         bid[j] = best_i;
         bid_inc[j] = best - better + eps;
         if (bid_inc[j] > max_inc[best_i]) max_inc[best_i] = bid_inc[j];

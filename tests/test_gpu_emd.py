@@ -1,7 +1,8 @@
 """GPU parity of the auction EMD through the C-ABI vs the C oracle (oracle/pointnet2.c: a sequential
 restatement of emd_cuda.cu): assignment and squared distances bit-exact — integer work and correctly-rounded fp32 /
-fp64 scalar arithmetic in the same order.  The oracle itself is unpinned against the reference (its CUDA source cannot be
-built here); its tie rule for GetMax's data race (largest bidder index) is shared by both sides."""
+fp64 scalar arithmetic in the same order.  The oracle itself is pinned to the reference's own kernels run on the CPU
+(tests/test_refkernels_cpu.py; the HIP kernel directly in tests/test_gpu_refkernels.py); its rule for GetMax's data race, which the
+reference leaves undefined (largest bidder index = last writer in ascending thread order), is shared by both sides."""
 import numpy as np
 import pytest
 import torch
@@ -53,6 +54,45 @@ def test_emd_backward_vs_oracle():
     ref = o.emd_backward(a, b, w.cpu().numpy(), asg.cpu().numpy())
     assert np.abs(x1.grad.cpu().numpy() - ref).max() < 1e-6
     assert float(x2.grad.abs().max()) == 0.0
+
+
+_BATCHED = {}
+
+
+def _batched_cases():
+    """Lattice clouds (k/16: constant exact ties) of more than 2048 points, eps 0.1 so that the tail is reached: (a, b, iters, oracle
+    distance, oracle assignment, bidders of the last iteration), computed once."""
+    if not _BATCHED:
+        from oracle import pointnet2 as o
+        for n, its in ((2500, (3, 20, 75, 120, 300)), (3000, (3, 40, 160, 300))):
+            rng = np.random.Generator(np.random.PCG64(n))
+            lat = (rng.integers(0, 17, (2, n, 3)) / 16).astype(np.float32)
+            a, b = lat[:1], lat[1:]
+            hist = o.emd_unassigned_per_iteration(a, b, 0.1, max(its))
+            _BATCHED[n] = [(a, b, it) + tuple(o.emd_forward(a, b, 0.1, it)) + (int(hist[it - 1]),) for it in its]
+    return _BATCHED
+
+
+@pytest.mark.parametrize("state_global", [0, 1])
+@pytest.mark.parametrize("n", [2500, 3000])
+def test_emd_more_than_one_target_batch_ties_bit_exact(n, state_global):
+    """n > 2048: the reference's Bid walks the targets in batches of 2048, every thread of a bidder its chunk of each batch, so among
+    equal values the first in (thread, batch, k) order wins, not the first k (the oracle is pinned to that by the n = 3072 and 4096
+    fixtures of tests/test_gpu_refkernels.py; the reference itself takes multiples of 1024 only).  Ragged sizes, whose last batch has
+    a chunk length of its own: 2500 keeps the auction's state in LDS, 3000 in the workspace; stopped among many bidders and inside
+    the tail path (the keys then travel through the partial merges of wavefront 0)."""
+    from difffacto_amd import _ffi
+    from difffacto_amd.metrics import emdFunction
+    cases = _batched_cases()[n]
+    assert sum(1 <= c[5] <= 8 for c in cases) >= 2 and sum(c[5] > 16 for c in cases) >= 2
+    _ffi.lib().dfx_debug_emd_state_global(state_global)
+    try:
+        for a, b, it, d_ref, as_ref, _ in cases:
+            d, asg = emdFunction.apply(torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda(), 0.1, it)
+            assert np.array_equal(asg.cpu().numpy(), as_ref), (n, it, int((asg.cpu().numpy() != as_ref).sum()))
+            assert np.array_equal(d.cpu().numpy(), d_ref), (n, it)
+    finally:
+        _ffi.lib().dfx_debug_emd_state_global(0)
 
 
 @pytest.mark.parametrize("state_global", [0, 1])

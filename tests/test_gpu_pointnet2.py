@@ -36,7 +36,11 @@ def cloud(rng, B, N, dup=0.0, origin=0):
 
 
 @pytest.mark.parametrize("B,N,M", [(2, 2048, 512), (3, 512, 128), (1, 8192, 2048), (2, 700, 64), (2, 5000, 300),
-                                   (1, 12000, 128), (1, 20000, 64), (4, 33, 33), (2, 1, 1), (1, 3, 3)])
+                                   (1, 12000, 128), (1, 20000, 64), (4, 33, 33), (2, 1, 1), (1, 3, 3),
+                                   # every launch shape of the table and both sides of each of its boundaries (512x8 = 2048 < N <= 4096
+                                   # had no case), of the LDS-coordinates flip (8192) and of the resident / streaming flip (16384)
+                                   (1, 3000, 128), (2, 513, 64), (2, 1024, 64), (2, 1025, 64), (1, 2049, 64), (1, 4096, 64),
+                                   (1, 4097, 64), (1, 8193, 64), (1, 16384, 64), (1, 16385, 64)])
 def test_fps_matches_oracle(pu, B, N, M):
     rng = np.random.default_rng(N + M)
     xyz = cloud(rng, B, N, dup=0.2 if N > 100 else 0.0, origin=3 if N > 100 else 0)

@@ -1,8 +1,9 @@
 """GPU parity against REFERENCE output directly (not through the C oracle): the HIP FPS / ball-query / Chamfer kernels
 vs goldens produced by the reference's own pure-torch helpers (tests/golden/make_golden_pins.py):
 farthest_point_sample (models/encoders/pointnet2_utils.py:60-81, start index patched to 0), query_ball_point (:84-104),
-distChamfer (datasets/evaluation_utils.py:93-103), the feature-propagation path's 3-NN + interpolation (:289-299).  Only the
-auction EMD has no pure-torch counterpart in the reference and stays "parity unpinned" (bit-exact vs oracle/pointnet2.c only)."""
+distChamfer (datasets/evaluation_utils.py:93-103), the feature-propagation path's 3-NN + interpolation (:289-299).  The
+auction EMD and the FPS tie rule / origin skip have no pure-torch counterpart in the reference; they are pinned to its CUDA kernels
+run on the CPU in tests/test_gpu_refkernels.py."""
 import os
 
 import numpy as np
