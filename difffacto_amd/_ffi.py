@@ -207,6 +207,8 @@ SIGNATURES = {
     "dfx_debug_force_direct": (None, [_I]),
     "dfx_debug_bare_mfma": (_I, [_I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double), _P]),
     "dfx_debug_pipe_waves": (None, [_I]),
+    "dfx_debug_chain_general": (None, [_I]),
+    "dfx_debug_last_chain_kind": (ctypes.c_char_p, []),
     "dfx_debug_plan_variant": (ctypes.c_char_p, [_I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]),
     "dfx_debug_ff16_pack_w1": (None, [_P, _P, _P, _P, _I, _I, _P]),   # host pointers
     "dfx_debug_ff16_pack_w2": (None, [_P, _I, _P]),

@@ -61,6 +61,12 @@ __host__ __device__ inline int cvec_index(int ch) {  // channel -> position in c
 //   c_t rows (per block): [T] x 1 KiB, first 512 B = cvec of to_out(W_v[:,266:] t_embed(t)) + to_out.bias
 //   attention record (per shape, per block): 4 A_s tiles (k-tile c) | 4 M_s tiles (row-tile ct) |
 //        1 KiB: sbias [hf][16] fp32 (beta2 . A_s rows) + pad
+//        Key mask (bf16 records only): the sbias entries of an ABSENT part (valid[j] == 0; entry 16 hf + r is row rho(r, hf) = 4 head + j of A_s)
+//        hold -FLT_MAX.  sbias is the C operand of the A_s MFMAs and the products stay far below half an ulp of FLT_MAX (1e31), so `sim` leaves
+//        them as exactly the -FLT_MAX that the masked softmax selects (attention.py:195-197), and the bf16 kernels' softmax has no select
+//        (softmax4_pk).  Readers of a bf16 record — every bf16 kernel of denoiser_kernel.hip, whatever the entry point: dfx_denoise_eps(_t),
+//        dfx_p_sample(_ddim), the chains, the partial chains — rely on it.  fp32 records hold the plain bias: the exact kernels select
+//        (softmax4<false>).  Nothing else reads the records: training has its own attention path, the editing paths prepare a new context.
 constexpr int CHUNK_TILES = 12;
 constexpr int FF_SKEW = 1;
 constexpr int FF_STAGES = FF_CHUNKS + FF_SKEW;

@@ -40,6 +40,12 @@ enum { MODE_EPS = 0, MODE_PSAMPLE = 1, MODE_CHAIN = 2 };
 // or q_sample of the caller's clean x_in at the first executed timestep, computed in the prologue
 enum { START_NOISE = 0, START_GIVEN = 1, START_QSAMPLE = 2 };   // (START_NOISE: the generation kernels; the others: their FROM instantiations)
 constexpr int DDIM_MAX_STEPS = 128;
+// Instantiations of the bf16 chain kernels.  GENERAL: every entry point, every mode select of KParams tested at run time.  FROM: partial chains.
+// PLAIN: plain generation — MODE_CHAIN, DDPM over the whole chain (t = t0 - step), in-kernel Philox for x_T and for the step noise, no t_shape, no
+// xstart, no snapshots, no x_in, no hold mask — with all of that fixed at compile time: the launcher (launch(), plain_launch()) takes it exactly
+// when the launch is of that kind.  What is left of every function is what GENERAL runs for such a launch, expression for expression, in the same
+// order: the two are bit-identical (tests/test_gpu_chain_plain_bits.py).  The exact-fp32 and the direct kernels have GENERAL and FROM only.
+enum ChainKind { CHAIN_GENERAL = 0, CHAIN_FROM = 1, CHAIN_PLAIN = 2 };
 
 struct KParams {
   DenoiserDev d;
@@ -362,9 +368,13 @@ __device__ __forceinline__ void load16(v16f &v, const float *src) {
 // bf16 kernels (softmax4<true>, every one of them through this function): on register pairs, as ln_stats_fast.  The max-subtract and the exp's scale
 // (__expf = v_exp_f32 of x * log2(e)) take the pairs (0, 1) and (2, 3) of a head; the sum and the multiply by the reciprocal take the SAME key of two
 // neighbouring heads side by side, so that every half is the operation it always was, in the order it always was (0 + e0 + e1 + e2 + e3), and the bits
-// hold for every key mask (tests/test_gpu_softmax_masks_bits.py).  The mask select, the max, v_exp_f32 and v_rcp_f32 have no packed form.  The
+// hold for every key mask (tests/test_gpu_softmax_masks_bits.py).  The max, v_exp_f32 and v_rcp_f32 have no packed form.  The
 // hardware reciprocal (1 ulp) stands for the correctly rounded division (~10 VALU instructions, four per block).
-__device__ __forceinline__ void softmax4_pk(v16f &sim, unsigned vmask) {
+// There is no mask select here: a bf16 attention record carries the key mask in sbias (dfx_shape_ctx_prepare writes -FLT_MAX into the rows of absent
+// parts), sbias is the C operand of the A_s MFMAs, and -FLT_MAX plus products below half its ulp (1e31) is -FLT_MAX: `sim` arrives with the value the
+// select used to put there (:195-197).  Every bf16 kernel relies on it, through this function: the chain kernels, dfx_denoise_eps(_t), dfx_p_sample(_ddim)
+// and the partial chains, on every context of a bf16 engine — the editing paths prepare a new context whenever they change `valid`.
+__device__ __forceinline__ void softmax4_pk(v16f &sim) {
   const v2f l2e = splat2(1.44269504088896340736f);
 #pragma unroll
   for (int gp = 0; gp < 2; ++gp) {   // heads 2gp and 2gp + 1 of this half-wave
@@ -374,7 +384,7 @@ __device__ __forceinline__ void softmax4_pk(v16f &sim, unsigned vmask) {
       const int g = 2 * gp + u;
       float sj[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) sj[j] = (vmask >> j) & 1u ? sim[4 * g + j] : -3.402823466e38f;  // :195-197
+      for (int j = 0; j < 4; ++j) sj[j] = sim[4 * g + j];
       const v2f m2 = splat2(fmaxf(fmaxf(sj[0], sj[1]), fmaxf(sj[2], sj[3])));
       const v2f t01 = (v2f{sj[0], sj[1]} - m2) * l2e, t23 = (v2f{sj[2], sj[3]} - m2) * l2e;
       e[u][0] = __builtin_amdgcn_exp2f(t01[0]), e[u][1] = __builtin_amdgcn_exp2f(t01[1]);
@@ -394,7 +404,7 @@ __device__ __forceinline__ void softmax4_pk(v16f &sim, unsigned vmask) {
 template <bool FAST_RCP = false>   // true: the bf16 kernels (softmax4_pk)
 __device__ __forceinline__ void softmax4(v16f &sim, unsigned vmask) {
   if constexpr (FAST_RCP) {
-    softmax4_pk(sim, vmask);
+    softmax4_pk(sim);   // (the mask is in sim already: sbias)
     return;
   }
 #pragma unroll
@@ -796,9 +806,9 @@ __device__ __forceinline__ void attn_m1(v16f (&h)[4], const Act<DFX_PREC_BF16> &
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// attention V slot: masked softmax over the 4 keys of each head (registers 4g..4g+3 = keys of head 2g+hf), on register pairs
-__device__ __forceinline__ void attn_softmax(v16f &sim, Act<DFX_PREC_BF16> &pa, unsigned vmask) {
-  softmax4_pk(sim, vmask);   // (every bf16 kernel takes the same reciprocal; +0.25 % in a same-box A/B)
+// attention V slot: softmax over the 4 keys of each head (registers 4g..4g+3 = keys of head 2g+hf; masked through sbias), on register pairs
+__device__ __forceinline__ void attn_softmax(v16f &sim, Act<DFX_PREC_BF16> &pa) {
+  softmax4_pk(sim);   // (every bf16 kernel takes the same reciprocal; +0.25 % in a same-box A/B)
   pa.set(sim);
 }
 
@@ -853,7 +863,9 @@ __device__ __forceinline__ void post_eps_pk(const v16f (&h)[4], const float *wou
 }
 
 // Timestep of the step-th executed step (wave-uniform): T-1, T-2, ... for DDPM, the list for DDIM.
+template <int KIND = CHAIN_GENERAL>
 __device__ __forceinline__ int step_t(const KParams &p, int step, int s) {
+  if constexpr (KIND == CHAIN_PLAIN) return p.t0 - step;
   if (p.t_shape) return __builtin_amdgcn_readfirstlane(p.t_shape[s]);   // wave-uniform (one shape per wave)
   if (p.ddim_n > 0) return p.ddim_t[step < p.ddim_n ? step : p.ddim_n - 1];
   return p.t0 - step;
@@ -893,9 +905,9 @@ __device__ __forceinline__ void chain_start_from(const KParams &p, PointState &p
 
 // One point of `pred` or of a snapshot.  In a partial chain a point of a held part (hold bit of its part id) is written as the caller's x_in:
 // decided here, from the part id and the shape's mask, and re-read from global memory — nothing of it travels through the step loop.
-template <bool FROM>
+template <int KIND>
 __device__ __forceinline__ void chain_store(const KParams &p, const PointState &ps, float *o) {
-  if constexpr (FROM) {
+  if constexpr (KIND == CHAIN_FROM) {
     if (p.hold && ((p.hold[ps.s] >> ps.sg) & 1)) {
 #pragma unroll
       for (int i = 0; i < 3; ++i) o[i] = p.x_in[((size_t)ps.s * 3 + i) * p.N + ps.n];
@@ -907,7 +919,7 @@ __device__ __forceinline__ void chain_store(const KParams &p, const PointState &
 
 // FROM: the instantiation for partial chains (dfx_sample_chain_from / dfx_refine_chain / dfx_sample_chain_ddim_from).  Every kernel exists twice,
 // and the generation kernels (FROM = false) compile to what they were before partial chains existed.
-template <bool FROM = false>
+template <int KIND = CHAIN_GENERAL>
 __device__ __forceinline__ void point_init(const KParams &p, PointState &ps, int s, int n, unsigned long long gid,
                                            unsigned &vmask) {
   ps.s = s; ps.n = n; ps.gid = gid;
@@ -924,7 +936,12 @@ __device__ __forceinline__ void point_init(const KParams &p, PointState &ps, int
   for (int j = 0; j < 4; ++j) vmask |= (part[24 + j] != 0.f ? 1u : 0u) << j;  // mask.to(bool), attention.py:196
   vmask = __builtin_amdgcn_readfirstlane(vmask);
   const int hf = (threadIdx.x >> 5) & 1;
-  if constexpr (FROM) {
+  if constexpr (KIND == CHAIN_PLAIN) {   // x_T = a + L z, z from the Philox stream of the x_T draw
+    float z[3];
+    philox_normal3(p.seed, gid, (unsigned)p.d.T, 1u, z);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ps.x[i] = ps.L[i] * z[i] + ps.anc[i];  // anchored_diffusion.py:563-564
+  } else if constexpr (KIND == CHAIN_FROM) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) ps.x[i] = p.x_in[((size_t)s * 3 + i) * p.N + n];
     chain_start_from(p, ps, hf);
@@ -951,11 +968,38 @@ __device__ __forceinline__ void point_init(const KParams &p, PointState &ps, int
 // What happens to eps after the network: store it (MODE_EPS), or the anchored posterior update
 // (anchored_diffusion.py:306-319,365-367,378-380,401-409,175-213,476-483; reference op order, no contraction)
 // plus the bookkeeping of AnchorDiffAE.decode (anchor_gen.py:160-167).  Returns true when the kernel is done.
-template <bool FROM = false>
+// PLAIN: the DDPM posterior of a MODE_CHAIN launch and nothing else; `tab_row` is the table row of t, fetched by the caller (one scalar load at the top
+// of the step boundary in the pipelined kernels, the idle wavefront's copy in LDS in the co-operative ones).  The store of `pred` at t = 0 is the one
+// place that writes global memory.
+template <int KIND = CHAIN_GENERAL>
 __device__ __forceinline__ bool step_epilogue(const KParams &p, PointState &ps, const float (&eps)[3], int step, int t,
                                               const float *z_ready = nullptr, const float *tab_row = nullptr) {
   const int hf = ps.live ? (threadIdx.x >> 5) & 1 : 1;   // stores are done by half-wave 0 of live wavefronts
   const int s = ps.s, n = ps.n;
+  if constexpr (KIND == CHAIN_PLAIN) {
+    float z[3];
+    if (z_ready) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) z[i] = z_ready[i];
+    } else {
+      philox_normal3(p.seed, ps.gid, (unsigned)t, 0u, z);
+    }
+    {
+#pragma clang fp contract(off)
+      const float *tb = tab_row;
+      const float sra = tb[0], srm1 = tb[1], c1 = tb[2], c2 = tb[3], c3 = tb[4], pv = tb[5];
+      const float nz = t != 0 ? 1.0f : 0.0f;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const float x0 = sra * (ps.x[i] - ps.anc[i]) + ps.anc[i] - srm1 * ps.L[i] * eps[i];
+        const float mv = pv * ps.var[i];
+        const float mu = c1 * x0 + c2 * ps.x[i] + c3 * ps.anc[i];
+        ps.x[i] = mu + nz * sqrtf(mv) * z[i];
+      }
+    }
+    if (hf == 0 && t == 0) chain_store<KIND>(p, ps, p.out + ((size_t)s * p.N + n) * 3);
+    return false;
+  }
   if (p.mode == MODE_EPS) {
     if (hf == 0) {
 #pragma unroll
@@ -1004,10 +1048,10 @@ __device__ __forceinline__ bool step_epilogue(const KParams &p, PointState &ps, 
   }
   if (hf == 0) {
     if (t == 0) {
-      chain_store<FROM>(p, ps, p.out + ((size_t)s * p.N + n) * 3);
+      chain_store<KIND>(p, ps, p.out + ((size_t)s * p.N + n) * 3);
     } else if (p.traj && t % p.ret_interval == 0) {
       const int k = p.d.T / p.ret_interval - t / p.ret_interval;
-      chain_store<FROM>(p, ps, p.traj + (((size_t)k * p.B + s) * p.N + n) * 3);
+      chain_store<KIND>(p, ps, p.traj + (((size_t)k * p.B + s) * p.N + n) * 3);
     }
   }
   return false;
@@ -1188,19 +1232,20 @@ struct AttnRecord {
     else if (q == 22) src = ct_row, dst = ring + 17 * 1024;
   }
 };
+template <int KIND>
 __device__ __forceinline__ AttnRecord attn_record(const KParams &p, const DmaState &st, const BlockPack &bp, int q0, int nc, unsigned ring, unsigned lds0, int s) {
   AttnRecord r;
   const unsigned rec = (unsigned)__builtin_amdgcn_readfirstlane(s * p.d.depth + st.b);
   r.as = reinterpret_cast<const char *>(p.as_ms) + (unsigned long long)rec * (unsigned)asms_bytes(DFX_PREC_BF16);
   r.bconst = reinterpret_cast<const char *>(bp.bconst);
   r.ct_row = r.bconst;
-  if (q0 <= 22 && 22 < q0 + nc) r.ct_row = reinterpret_cast<const char *>(bp.ct + (size_t)step_t(p, st.step, s) * CT_ROW);
+  if (q0 <= 22 && 22 < q0 + nc) r.ct_row = reinterpret_cast<const char *>(bp.ct + (size_t)step_t<KIND>(p, st.step, s) * CT_ROW);
   r.ring = ring, r.bc = lds0 + L_BCONST + (st.seq & 1) * BCONST_BYTES, r.dummy = lds0 + L_DUMMY;
   return r;
 }
 
 // Issue this wave's pieces (CALLS_A / CALLS_B of them, starting at piece q0) of the next record and advance the state.
-template <int NC>
+template <int NC, int KIND>
 __device__ __forceinline__ void issue_pieces(const KParams &p, DmaState &st, int q0, unsigned voff, unsigned lds0, int s) {
   const unsigned ring = lds0 + L_RING + st.slot * SLOT_BYTES;
   if (NC == 0) {
@@ -1211,7 +1256,7 @@ __device__ __forceinline__ void issue_pieces(const KParams &p, DmaState &st, int
     st.ff_src += SLOT_BYTES;
   } else {  // attention record: 17 KiB shape record | 5 KiB block constants | 1 KiB c_t row | 1 padding piece
     const BlockPack bp = block_pack(p, st.b);
-    const AttnRecord ar = attn_record(p, st, bp, q0, NC, ring, lds0, s);
+    const AttnRecord ar = attn_record<KIND>(p, st, bp, q0, NC, ring, lds0, s);
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
       const char *src;
@@ -1230,7 +1275,7 @@ struct Pieces {
   const char *src[NC];
   unsigned dst[NC];
 };
-template <int NC>
+template <int NC, int KIND>
 __device__ __forceinline__ void prepare_pieces(const KParams &p, DmaState &st, int q0, unsigned lds0, int s, Pieces<NC> &pc) {
   const unsigned ring = lds0 + L_RING + st.slot * SLOT_BYTES;
   if (st.step >= p.nsteps) {
@@ -1242,7 +1287,7 @@ __device__ __forceinline__ void prepare_pieces(const KParams &p, DmaState &st, i
     st.ff_src += SLOT_BYTES;
   } else {
     const BlockPack bp = block_pack(p, st.b);
-    const AttnRecord ar = attn_record(p, st, bp, q0, NC, ring, lds0, s);
+    const AttnRecord ar = attn_record<KIND>(p, st, bp, q0, NC, ring, lds0, s);
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
       const char *src;
@@ -1266,9 +1311,9 @@ __device__ __forceinline__ void advance_record(const KParams &p, DmaState &st) {
   }
 }
 
-template <int NW>
+template <int NW, int KIND>
 __device__ __forceinline__ void issue_record(const KParams &p, DmaState &st, int wave, unsigned voff, unsigned lds0, int s) {
-  issue_pieces<PipeCfg<NW>::CALLS>(p, st, wave * PipeCfg<NW>::CALLS, voff, lds0, s);
+  issue_pieces<PipeCfg<NW>::CALLS, KIND>(p, st, wave * PipeCfg<NW>::CALLS, voff, lds0, s);
   advance_record(p, st);
 }
 
@@ -1276,7 +1321,7 @@ __device__ __forceinline__ void issue_record(const KParams &p, DmaState &st, int
 // groups' M slots are in anti-phase, so at most four waves issue at a time, one KiB per ~250 cycles).  Issued all at once
 // behind the record's management barrier, the eight waves' 24 KiB hit the texture-address path (64 B/clk) together and
 // every wave sits ~400 cycles in the issue stall on the critical path of the record (slot trace, tools/experiments/run_trace.sh).
-template <int NW>
+template <int NW, int KIND>
 struct Issuer {
   static constexpr int CALLS = PipeCfg<NW>::CALLS;
   // 8-wave workgroups fill the chip: their pieces are spread over the M slot (comment above).  The 4- and 2-wave workgroups of
@@ -1292,13 +1337,13 @@ struct Issuer {
   // (scalar) source / destination bookkeeping of the pieces of the next M slot; runs in the V slot before it
   __device__ __forceinline__ void m_begin() {
     if constexpr (SPREAD) {
-      prepare_pieces<CALLS>(p, st, wave * CALLS, lds0, s, pc);
+      prepare_pieces<CALLS, KIND>(p, st, wave * CALLS, lds0, s, pc);
       advance_record(p, st);
     }
   }
   // right behind a record's management barrier
   __device__ __forceinline__ void after_barrier() {
-    if constexpr (!SPREAD) issue_record<NW>(p, st, wave, voff, lds0, s);
+    if constexpr (!SPREAD) issue_record<NW, KIND>(p, st, wave, voff, lds0, s);
   }
   // after MFMA i of the n of an M slot
   __device__ __forceinline__ void at(int i, int n) {
@@ -1307,6 +1352,19 @@ struct Issuer {
       for (int k = 0; k < CALLS; ++k)
         if (i == (k * n) / CALLS) dma1k(pc.src[k], voff, pc.dst[k]);
     }
+  }
+};
+
+// One row of the posterior table ([T][8] floats, 32-byte rows of a 256-byte-aligned array that no kernel writes) through the scalar unit: the address is
+// wave-uniform, and read through the constant address space the row is ONE s_load_dwordx8 — as a plain global pointer hipcc cannot prove that the
+// kernel's own stores leave it alone and fetches it per lane.
+struct TabRow {
+  float v[8];
+  __device__ __forceinline__ void fetch(const float *tab, int t) {
+    typedef __attribute__((address_space(4))) const v8f *cv8;
+    const v8f r = *(cv8)(uintptr_t)(tab + (size_t)t * 8);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = r[i];
   }
 };
 
@@ -1340,7 +1398,7 @@ __device__ __forceinline__ void pstate_load(const float *ps_lds, int pt, int PTS
   ps.sg = __float_as_int(ps_lds[12 * PTS + pt]);
 }
 
-template <int NW, bool FROM = false>
+template <int NW, int KIND = CHAIN_GENERAL>
 __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe(const KParams p) {
   constexpr int PREC = DFX_PREC_BF16;
   constexpr int PIPE_NW = NW, PTS = PipeCfg<NW>::PTS;
@@ -1377,9 +1435,9 @@ __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe(const KParams p) {
 
   // ---- prologue DMA: records 0, 1, 2 in flight while the per-point state is set up ----
   DmaState dma{0, 0, 0, 0, 0, nullptr};
-  issue_record<NW>(p, dma, wave, voff, lds0, s);
-  issue_record<NW>(p, dma, wave, voff, lds0, s);
-  issue_record<NW>(p, dma, wave, voff, lds0, s);
+  issue_record<NW, KIND>(p, dma, wave, voff, lds0, s);
+  issue_record<NW, KIND>(p, dma, wave, voff, lds0, s);
+  issue_record<NW, KIND>(p, dma, wave, voff, lds0, s);
 
   // ---- chain-invariant small operands -> LDS (plain loads; not part of the ring) ----
   {   // (W_in, pre_norm, W_out: the pair tables of proj_in_prenorm_pk / post_eps_pk, inside the regions of the one-float4-per-channel form)
@@ -1395,7 +1453,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe(const KParams p) {
   {
     PointState ps0;
     ps0.live = live;
-    point_init<FROM>(p, ps0, s, n, gid, vmask);
+    point_init<KIND>(p, ps0, s, n, gid, vmask);
     pstate_store(ps_lds, pt, PTS, ps0, true);   // both half-waves hold the same point: identical values
   }
   __syncthreads();
@@ -1404,7 +1462,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe(const KParams p) {
   const float *pregb = reinterpret_cast<const float *>(pipe_smem + L_PREGB) + hf * 32 * PAIR_PREGB;
   const float *wout = reinterpret_cast<const float *>(pipe_smem + L_WOUT) + hf * 32 * PAIR_WOUT;
 
-  Issuer<NW> issue_in_m{p, dma, wave, voff, lds0, s, {}};
+  Issuer<NW, KIND> issue_in_m{p, dma, wave, voff, lds0, s, {}};
   // slot boundary; `mgmt` = this barrier is a record's management barrier for this wave's group
 #define DFX_SLOT(mgmt)                   \
   do {                                   \
@@ -1456,11 +1514,19 @@ __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe(const KParams p) {
       if (b == 0) {
         PointState ps;
         ps.s = s, ps.n = n, ps.gid = gid, ps.live = live;
+        TabRow row;
+        if constexpr (KIND == CHAIN_PLAIN) {   // the posterior's table row: one scalar load, under the state's LDS reads and post_eps
+          if (step > 0) row.fetch(p.d.tab, step_t<KIND>(p, step - 1, s));
+        }
         pstate_load(ps_lds, pt, PTS, ps, step > 0);
         if (step > 0) {
           float eps[3];
           post_eps_pk(h, wout, p.d.bout, eps);
-          done = step_epilogue<FROM>(p, ps, eps, step - 1, step_t(p, step - 1, s));
+          if constexpr (KIND == CHAIN_PLAIN) {
+            step_epilogue<KIND>(p, ps, eps, step - 1, step_t<KIND>(p, step - 1, s), nullptr, row.v);
+          } else {
+            done = step_epilogue<KIND>(p, ps, eps, step - 1, step_t(p, step - 1, s));
+          }
           if (!done) pstate_store(ps_lds, pt, PTS, ps, false);   // both half-waves hold the same point and write the same x
         }
         if (step == p.nsteps) done = true;
@@ -1480,7 +1546,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_denoise_pipe(const KParams p) {
       // ---- V1: softmax ----
       DFX_SLOT(false);
       Act<PREC> pa;
-      attn_softmax(sim, pa, vmask);
+      attn_softmax(sim, pa);
       // ---- M1: h += M_s P ----
       DFX_SLOT(false);
       attn_m1(h, pa, rec, P, DFX_PEEK_RECORD());
@@ -1884,10 +1950,10 @@ __device__ __forceinline__ void coop_stage_consts(unsigned char *cc, const KPara
 
 // The 32 points of tile (s, n - pj): initial chain state -> its LDS home between step boundaries
 // (the state would otherwise sit in scratch memory for the whole chain: a global-memory round trip per field at every step boundary)
-template <bool FROM>
+template <int KIND>
 __device__ __forceinline__ void coop_point_init(const KParams &p, float *ps_lds, int s, int n, int pj, unsigned &vmask) {
   PointState ps0;
-  point_init<FROM>(p, ps0, s, n, ((unsigned long long)p.shape0 + (unsigned)s) * (unsigned)p.N + (unsigned)n, vmask);
+  point_init<KIND>(p, ps0, s, n, ((unsigned long long)p.shape0 + (unsigned)s) * (unsigned)p.N + (unsigned)n, vmask);
   pstate_store(ps_lds, pj, 32, ps0, true);
 }
 
@@ -1975,10 +2041,11 @@ __device__ __forceinline__ void coop_phase_a(v4f *home, const uint4 *s_at, uint4
 }
 
 // The step's noise for the tile's 32 points (n = this lane's) and the posterior table row -> s_z, ready for the step boundary: z[3][32] | row at float 128
+template <int KIND>
 __device__ __forceinline__ void coop_draw_noise(const KParams &p, float *s_z, int step, int t, int s, int n, int lane) {
   const int hf = lane >> 5, pj = lane & 31;
   float z[3];
-  if (p.noise) {
+  if (KIND != CHAIN_PLAIN && p.noise) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) z[i] = p.noise[(((size_t)step * p.B + s) * 3 + i) * p.N + n];
   } else {
@@ -2017,14 +2084,14 @@ __device__ __forceinline__ void coop_eps(float (&eps)[3], const v4f *home, const
   post_eps_tiles(h, reinterpret_cast<const float *>(cc + CC_WOUT) + (lane >> 5) * 32 * PAIR_WOUT, p.d.bout, eps);
 }
 // ... the posterior update of the chain state parked at ps_lds, with the noise coop_draw_noise left in s_z (true: the kernel is done) ...
-template <bool FROM>
+template <int KIND>
 __device__ __forceinline__ bool coop_posterior(const KParams &p, PointState &ps, const float (&eps)[3], const float *ps_lds, const float *s_z, int s, int n,
                                                int step, int t, int pj) {
   ps.s = s, ps.n = n, ps.gid = 0;   // (gid: the noise was drawn by another wave)
   pstate_load(ps_lds, pj, 32, ps, true);
   const float zr[3] = {s_z[pj], s_z[32 + pj], s_z[64 + pj]};
-  const bool zok = p.mode != MODE_EPS;
-  return step_epilogue<FROM>(p, ps, eps, step, t, zok ? zr : nullptr, zok ? s_z + 128 : nullptr);
+  const bool zok = KIND == CHAIN_PLAIN || p.mode != MODE_EPS;
+  return step_epilogue<KIND>(p, ps, eps, step, t, zok ? zr : nullptr, zok ? s_z + 128 : nullptr);
 }
 // ... and proj_in + pre_norm of the new state -> h's home (also before the first step)
 __device__ __forceinline__ void coop_enter_step(const PointState &ps, v4f *home, const unsigned char *cc, int lane) {
@@ -2049,7 +2116,7 @@ constexpr int CL_PS = CL_Z + 1024;                                 // per-point 
 constexpr int CL_TOTAL = CL_PS + 2048;
 static_assert(CL_TOTAL <= 160 * 1024, "LDS budget of the co-operative kernel");
 
-template <bool FROM>
+template <int KIND>
 __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams p) {
   constexpr int TSTRIDE = COOP_TSTRIDE, AREC = COOP_AREC;
   uint4 (*s_xn)[64] = reinterpret_cast<uint4 (*)[64]>(pipe_smem + CL_XN);
@@ -2068,7 +2135,7 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams 
   float *ps_lds = reinterpret_cast<float *>(pipe_smem + CL_PS);
   v4f *home = reinterpret_cast<v4f *>(pipe_smem + CL_HS) + lane;
   unsigned vmask = 0;
-  if (w0) coop_point_init<FROM>(p, ps_lds, s, n, pj, vmask);
+  if (w0) coop_point_init<KIND>(p, ps_lds, s, n, pj, vmask);
   const uint4 *asms_s = p.as_ms + (size_t)s * depth * AREC;
   coop_stage_consts(cc, p, s);   // (wave 0 reads them at every step boundary)
   __syncthreads();
@@ -2093,7 +2160,7 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams 
   }
   int seq = 0;
   for (int step = 0; step < p.nsteps; ++step) {
-    const int t = step_t(p, step, s);
+    const int t = step_t<KIND>(p, step, s);
     for (int b = 0; b < depth; ++b, ++seq) {
       const BlockPack bp = block_pack(p, b);
       float *s_bc = reinterpret_cast<float *>(pipe_smem + CL_BC + (seq & 1) * BCONST_BYTES);
@@ -2116,7 +2183,7 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams 
                          voff, lds0 + CL_W2 + k * 1024);
         }
         // the step's noise and posterior coefficients, ready for wave 0's epilogue
-        if (wave == COOP_NW - 1 && b == depth - 1 && p.mode != MODE_EPS) coop_draw_noise(p, s_z, step, t, s, n, lane);
+        if (wave == COOP_NW - 1 && b == depth - 1 && (KIND == CHAIN_PLAIN || p.mode != MODE_EPS)) coop_draw_noise<KIND>(p, s_z, step, t, s, n, lane);
       } else {           // ---- phase A: wave 0
         coop_phase_a(home, s_at, s_xn, lane, vmask);
       }
@@ -2174,7 +2241,7 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop(const KParams 
       coop_eps(eps, home, cc, p, lane);
       tr.stamp(18);
       PointState ps;
-      if (coop_posterior<FROM>(p, ps, eps, ps_lds, s_z, s, n, step, t, pj)) break;   // (the other waves leave through the loop bound: nsteps = 1 in these modes)
+      if (coop_posterior<KIND>(p, ps, eps, ps_lds, s_z, s, n, step, t, pj)) break;   // (the other waves leave through the loop bound: nsteps = 1 in these modes)
       tr.stamp(19);
       pstate_store(ps_lds, pj, 32, ps, false);
       if (step + 1 < p.nsteps) coop_enter_step(ps, home, cc, lane);
@@ -2205,7 +2272,7 @@ constexpr int C2_PS = C2_Z + 2 * 1024;                             // 2 tiles x 
 constexpr int C2_TOTAL = C2_PS + 2 * 2048;
 static_assert(C2_TOTAL <= 160 * 1024, "LDS budget of the two-tile co-operative kernel");
 
-template <bool FROM>
+template <int KIND>
 __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop2(const KParams p) {
   constexpr int AREC = COOP_AREC;
   uint4 *s_at = reinterpret_cast<uint4 *>(pipe_smem + C2_AT);
@@ -2226,7 +2293,7 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop2(const KParams
   float *ps_lds = reinterpret_cast<float *>(pipe_smem + C2_PS + (wave & 1) * 2048);   // (waves 0, 1)
   const int n_a = nbase + wave * 32 + pj;                                             // (waves 0, 1: this lane's point)
   unsigned vmask = 0;
-  if (arole) coop_point_init<FROM>(p, ps_lds, s, n_a, pj, vmask);
+  if (arole) coop_point_init<KIND>(p, ps_lds, s, n_a, pj, vmask);
   const uint4 *asms_s = p.as_ms + (size_t)s * depth * AREC;
   coop_stage_consts(cc, p, s);
   __syncthreads();
@@ -2244,9 +2311,9 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop2(const KParams
     coop_enter_step(ps, home(wave), cc, lane);
   }
   int seq = 0;
-  if (p.nsteps > 0) stage_block(0, step_t(p, 0, s), 0);
+  if (p.nsteps > 0) stage_block(0, step_t<KIND>(p, 0, s), 0);
   for (int step = 0; step < p.nsteps; ++step) {
-    const int t = step_t(p, step, s);
+    const int t = step_t<KIND>(p, step, s);
     for (int b = 0; b < depth; ++b, ++seq) {
       const BlockPack bp = block_pack(p, b);
       float *s_bc = reinterpret_cast<float *>(pipe_smem + C2_BC + (seq & 1) * BCONST_BYTES);
@@ -2255,9 +2322,9 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop2(const KParams
       __syncthreads();   // 0: attention record, c_t, block constants of this block are in LDS; h's homes hold the previous block's result
       if (arole) {       // ---- phase A: wave w on tile w
         coop_phase_a(home(wave), s_at, xn_base(wave), lane, vmask);
-      } else if (wave >= COOP_NW - 2 && b == depth - 1 && p.mode != MODE_EPS) {   // the step's noise and posterior coefficients: wave 6 for tile 0, wave 7 for tile 1
+      } else if (wave >= COOP_NW - 2 && b == depth - 1 && (KIND == CHAIN_PLAIN || p.mode != MODE_EPS)) {   // the step's noise and posterior coefficients: wave 6 for tile 0, wave 7 for tile 1
         const int tz = wave - (COOP_NW - 2);
-        coop_draw_noise(p, z_base(tz), step, t, s, nbase + tz * 32 + pj, lane);
+        coop_draw_noise<KIND>(p, z_base(tz), step, t, s, nbase + tz * 32 + pj, lane);
       }
       __syncthreads();   // 1: xn3 of both tiles and h are in LDS
       // ---- phase H: every wave, chunks `wave` and `wave + 8`, both tiles per fragment set
@@ -2282,7 +2349,7 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop2(const KParams
       // the next block's operands (next step's c_t row behind the last block)
       auto stage_next = [&] {
         if (b + 1 < depth) stage_block(b + 1, t, (seq + 1) & 1);
-        else if (step + 1 < p.nsteps) stage_block(0, step_t(p, step + 1, s), (seq + 1) & 1);
+        else if (step + 1 < p.nsteps) stage_block(0, step_t<KIND>(p, step + 1, s), (seq + 1) & 1);
       };
       // ---- phase G: wave (gt, ct) accumulates output tile ct of tile gt, chunk after chunk (the accumulation order of the pipelined kernel), + b2
       {
@@ -2316,7 +2383,7 @@ __global__ void __launch_bounds__(COOP_NW * 64, 2) k_denoise_coop2(const KParams
       float eps[3];
       coop_eps(eps, home(wave), cc, p, lane);
       PointState ps;
-      if (coop_posterior<FROM>(p, ps, eps, ps_lds, z_base(wave), s, n_a, step, t, pj)) break;   // (the other waves leave through the loop bound: nsteps = 1 in these modes)
+      if (coop_posterior<KIND>(p, ps, eps, ps_lds, z_base(wave), s, n_a, step, t, pj)) break;   // (the other waves leave through the loop bound: nsteps = 1 in these modes)
       pstate_store(ps_lds, pj, 32, ps, false);
       if (step + 1 < p.nsteps) coop_enter_step(ps, home(wave), cc, lane);
     }
@@ -2376,17 +2443,37 @@ struct VariantKernel {
 };
 const VariantKernel KERNELS[NUM_VARIANTS] = {
     {k_denoise_pipe<8>, PipeCfg<8>::L_TOTAL},     {k_denoise_pipe<4>, PipeCfg<4>::L_TOTAL},     {k_denoise_pipe<2>, PipeCfg<2>::L_TOTAL},
-    {k_denoise_coop<false>, CL_TOTAL},            {k_denoise_coop2<false>, C2_TOTAL},           {k_denoise_pipe_f32<8>, PipeCfg<8>::L_TOTAL},
+    {k_denoise_coop<CHAIN_GENERAL>, CL_TOTAL},    {k_denoise_coop2<CHAIN_GENERAL>, C2_TOTAL},   {k_denoise_pipe_f32<8>, PipeCfg<8>::L_TOTAL},
     {k_denoise_pipe_f32<4>, PipeCfg<4>::L_TOTAL}, {k_denoise_pipe_f32<2>, PipeCfg<2>::L_TOTAL}, {k_denoise<DFX_PREC_BF16, 4>, 0},
     {k_denoise<DFX_PREC_F32, 4>, 0},
 };
 // ... and their instantiations for partial chains (KParams::start != START_NOISE): the same plan, the same launch shape
 const VariantKernel KERNELS_FROM[NUM_VARIANTS] = {
-    {k_denoise_pipe<8, true>, PipeCfg<8>::L_TOTAL},     {k_denoise_pipe<4, true>, PipeCfg<4>::L_TOTAL},     {k_denoise_pipe<2, true>, PipeCfg<2>::L_TOTAL},
-    {k_denoise_coop<true>, CL_TOTAL},                   {k_denoise_coop2<true>, C2_TOTAL},                  {k_denoise_pipe_f32<8, true>, PipeCfg<8>::L_TOTAL},
+    {k_denoise_pipe<8, CHAIN_FROM>, PipeCfg<8>::L_TOTAL}, {k_denoise_pipe<4, CHAIN_FROM>, PipeCfg<4>::L_TOTAL}, {k_denoise_pipe<2, CHAIN_FROM>, PipeCfg<2>::L_TOTAL},
+    {k_denoise_coop<CHAIN_FROM>, CL_TOTAL},             {k_denoise_coop2<CHAIN_FROM>, C2_TOTAL},            {k_denoise_pipe_f32<8, true>, PipeCfg<8>::L_TOTAL},
     {k_denoise_pipe_f32<4, true>, PipeCfg<4>::L_TOTAL}, {k_denoise_pipe_f32<2, true>, PipeCfg<2>::L_TOTAL}, {k_denoise<DFX_PREC_BF16, 4, true>, 0},
     {k_denoise<DFX_PREC_F32, 4, true>, 0},
 };
+// ... and the plain-generation instantiations of the five bf16 chain kernels (ChainKind): the same plan, the same launch shape, the same name in
+// dfx_last_kernel_variant.  The other variants have none (nullptr): a plain launch that the planner gives to one of them takes its GENERAL form.
+const VariantKernel KERNELS_PLAIN[NUM_VARIANTS] = {
+    {k_denoise_pipe<8, CHAIN_PLAIN>, PipeCfg<8>::L_TOTAL}, {k_denoise_pipe<4, CHAIN_PLAIN>, PipeCfg<4>::L_TOTAL}, {k_denoise_pipe<2, CHAIN_PLAIN>, PipeCfg<2>::L_TOTAL},
+    {k_denoise_coop<CHAIN_PLAIN>, CL_TOTAL},               {k_denoise_coop2<CHAIN_PLAIN>, C2_TOTAL},              {nullptr, 0},
+    {nullptr, 0},                                          {nullptr, 0},                                          {nullptr, 0},
+    {nullptr, 0},
+};
+static_assert((int)Variant::Pipe8 == 0 && (int)Variant::Pipe4 == 1 && (int)Variant::Pipe2 == 2 && (int)Variant::Coop == 3 && (int)Variant::Coop2 == 4,
+              "KERNELS_PLAIN's rows against denoiser_plan.h's Variant");
+bool g_force_general = false;          // debug: dfx_debug_chain_general
+const char *g_last_chain_kind = "";    // "general" | "from" | "plain": the instantiation the last launch() took (dfx_debug_last_chain_kind)
+
+// Plain generation: everything that the PLAIN instantiations fix at compile time (ChainKind).  dfx_sample_chain without explicit noise and without
+// snapshots is such a launch — bench.py's timed call, AnchorDiffAE.decode when it asks for no trajectory.
+bool plain_launch(const KParams &p) {
+  return p.mode == MODE_CHAIN && p.start == START_NOISE && p.ddim_n == 0 && !p.t_shape && !p.noise && !p.xT_noise && !p.xstart && !p.traj && !p.x_in && !p.hold &&
+         p.nsteps == p.d.T && p.t0 == p.d.T - 1;
+}
+
 static_assert(info(Variant::Coop).threads == COOP_NW * 64 && info(Variant::Coop2).threads == COOP_NW * 64 && info(Variant::Pipe8).points == PipeCfg<8>::PTS,
               "denoiser_plan.h's table against the kernels' launch bounds");
 
@@ -2402,7 +2489,8 @@ int launch(const dfx_denoiser *d, const void *shape_ctx, KParams &p, hipStream_t
   // (the size check stays here, on the direct kernels' workgroup count as before; the planner itself takes any B, N)
   if (((long long)p.B * p.N / 32 + 3) / 4 > 0x7fffffffLL) return set_error(DFX_ERR_INVALID_ARG, "denoiser: B*N too large");
   const Plan plan = plan_launch({d->dev.prec, d->dev.w1_fold != 0, g_force_direct, force_from_code(g_force_nw), p.B, p.N, g_num_cus});
-  const VariantKernel &k = (p.start != START_NOISE ? KERNELS_FROM : KERNELS)[(int)plan.v];
+  const bool plain = !g_force_general && plain_launch(p) && KERNELS_PLAIN[(int)plan.v].kernel != nullptr;
+  const VariantKernel &k = (plain ? KERNELS_PLAIN : p.start != START_NOISE ? KERNELS_FROM : KERNELS)[(int)plan.v];
   if (k.lds > 0) {
     static PerDeviceOnce attrs;
     DFX_HIP_TRY(attrs.run([] {
@@ -2411,6 +2499,8 @@ int launch(const dfx_denoiser *d, const void *shape_ctx, KParams &p, hipStream_t
         if (e == hipSuccess && vk.lds > 0) e = set_max_lds(reinterpret_cast<const void *>(vk.kernel), vk.lds);
       for (const VariantKernel &vk : KERNELS_FROM)
         if (e == hipSuccess && vk.lds > 0) e = set_max_lds(reinterpret_cast<const void *>(vk.kernel), vk.lds);
+      for (const VariantKernel &vk : KERNELS_PLAIN)
+        if (e == hipSuccess && vk.lds > 0) e = set_max_lds(reinterpret_cast<const void *>(vk.kernel), vk.lds);
       return e;
     }));
   }
@@ -2418,6 +2508,7 @@ int launch(const dfx_denoiser *d, const void *shape_ctx, KParams &p, hipStream_t
   tm.begin(st);
   hipLaunchKernelGGL(k.kernel, dim3((unsigned)plan.grid), dim3(info(plan.v).threads), k.lds, st, p);
   g_last_variant = info(plan.v).name;
+  g_last_chain_kind = plain ? "plain" : p.start != START_NOISE ? "from" : "general";
   const int rc = check_launch("denoiser kernel");
   tm.end();
   return rc;
@@ -2545,6 +2636,8 @@ int dfx_masked_mse_f32(const float *target, const float *pred, const float *flag
 
 void dfx_debug_force_direct(int on) { g_force_direct = on != 0; }
 void dfx_debug_pipe_waves(int nw) { g_force_nw = nw; }
+void dfx_debug_chain_general(int on) { g_force_general = on != 0; }
+const char *dfx_debug_last_chain_kind(void) { return g_last_chain_kind; }
 const char *dfx_debug_plan_variant(int prec, int w1_fold, int force_direct, int pipe_waves_code, int B, int N, long long *grid_out) {
   const Plan plan = plan_launch({prec, w1_fold != 0, force_direct != 0, force_from_code(pipe_waves_code), B, N, g_num_cus});
   if (grid_out) *grid_out = plan.grid;

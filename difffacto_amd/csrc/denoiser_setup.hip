@@ -313,7 +313,9 @@ __global__ void __launch_bounds__(256) k_shape_ctx(const float *__restrict__ par
     const int hf = tid >> 4, r = tid & 15, R = rho(r, hf), head = R >> 2, j = R & 3;
     float acc = 0.f;
     for (int d = 0; d < DHEAD; ++d) acc = fmaf(s_wqb[head * DHEAD + d], s_k[head * DHEAD + d][j], acc);
-    sbias[tid] = acc * scale;
+    // bf16 records carry the key mask here (denoiser_internal.h, "key mask"): the rows of an absent part start the A_s MFMAs from -FLT_MAX and leave
+    // them as -FLT_MAX, the value the masked softmax used to select.  fp32 records keep the plain bias: the exact kernels select (softmax4<false>).
+    sbias[tid] = PREC == DFX_PREC_BF16 && valid[(size_t)s * 4 + j] == 0.f ? -3.402823466e38f : acc * scale;
   } else if (tid < 256) {
     sbias[tid] = 0.f;  // pad of the 1 KiB piece
   }

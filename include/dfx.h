@@ -163,7 +163,11 @@ int dfx_denoiser_get_tables(const dfx_denoiser *d, float *host_out);
  * K/V projections folded with to_q / to_out and the per-part proj_in constants.
  *   part_code (B,256,4)  mean (B,3,4)  var (B,3,4) = exp(logvar)   [ctx list of prepare_ctx,
  *   part_encoders.py:1317-1326]   valid (B,4) floats (mask of attention.py:192-197)
- * `ctx_out` is a caller-allocated device buffer of dfx_shape_ctx_bytes(d, B) bytes. */
+ * `ctx_out` is a caller-allocated device buffer of dfx_shape_ctx_bytes(d, B) bytes.
+ * The context is opaque: it is consumed by the library that prepared it, with the `valid` it was prepared with.  The context of a bf16
+ * engine carries the key mask inside its attention operands (the similarity bias of an absent part is -FLT_MAX) and its kernels no longer
+ * read `valid` for the softmax, so a context written by an earlier library version must be prepared again, and a change of `valid` means
+ * a new dfx_shape_ctx_prepare, as it always did.  The context of an fp32 engine is what it was. */
 size_t dfx_shape_ctx_bytes(const dfx_denoiser *d, int B);
 int dfx_shape_ctx_prepare(const dfx_denoiser *d, const float *part_code, const float *mean, const float *var,
                           const float *valid, void *ctx_out, int B, dfx_stream_t stream);

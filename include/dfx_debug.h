@@ -99,6 +99,13 @@ int dfx_debug_w1_fold_channel(const dfx_denoiser *d);
  * whatever the code.  All variants of one precision are bit-identical.
  * dfx_last_kernel_variant() (dfx.h) names the kernel a launch actually took. */
 void dfx_debug_pipe_waves(int nw);
+/* Debug / A-B switch: 1 makes a plain generation launch (dfx_sample_chain of a bf16 engine with in-kernel noise and no snapshots) take the
+ * GENERAL instantiation of its chain kernel, whose mode selects are tested at run time, where it would take the PLAIN one, which has them
+ * fixed at compile time (csrc/denoiser_kernel.hip: ChainKind); 0 = automatic (the default).  The two are bit-identical.
+ * dfx_debug_last_chain_kind: "plain", "general" or "from" (partial chains) for the instantiation the last denoiser launch took, "" before
+ * the first; dfx_last_kernel_variant() reports the same kernel name for all three. */
+void dfx_debug_chain_general(int on);
+const char *dfx_debug_last_chain_kind(void);
 /* Host-side run (no GPU) of the launcher's planner (csrc/denoiser_plan.h): the name dfx_last_kernel_variant() would report after a denoiser
  * launch of B shapes of N points on an engine of precision `prec` (DFX_PREC_*) with / without the W1 bias fold, under dfx_debug_force_direct(force_direct)
  * and dfx_debug_pipe_waves(pipe_waves_code); *grid_out (may be NULL) = its workgroups.  A pure function of its arguments: the process-global
