@@ -1981,7 +1981,8 @@ int bn_bwd(hipStream_t st, const BnScratch &w, const float *dy, const float *be,
 }
 int check_pn(const dfx_pointnet_v2_weights *wt, const void *ws, size_t ws_bytes, int B, int N, const char *what) {
   DFX_REQUIRE(wt && ws, "%s: null argument", what);
-  DFX_REQUIRE(wt->num_anchors == 4 && wt->zdim >= 4 && wt->zdim % 4 == 0, "%s: num_anchors 4 and zdim %% 4 == 0 required", what);
+  // (zdim is the K of the last head layer's input-gradient products, consumed eight at a time: mfma_linear.h)
+  DFX_REQUIRE(wt->num_anchors == 4 && wt->zdim >= 8 && wt->zdim % 8 == 0, "%s: num_anchors 4 and zdim %% 8 == 0 required", what);
   DFX_REQUIRE(B >= 2 && N >= 1, "%s: B >= 2 (BatchNorm over the batch in the heads) and N >= 1 required", what);
   DFX_REQUIRE((long long)B * N < (1ll << 31), "%s: B*N too large", what);
   PnWs t;
@@ -2076,10 +2077,11 @@ __global__ void k_smt_from_rows(const float *__restrict__ rows, float *__restric
     if (c0 + k < Cc && l0 + tx < L) xb[(size_t)(c0 + k) * L + l0 + tx] = tile[tx][k];
 }
 // max over the ns rows of a group (F.max_pool2d over nsample: the FIRST maximum wins, like torch's CPU / CUDA pooling kernels on ties): y (G ns, Cc) ->
-// out (B, Cc, M) with G = B M, arg (G, Cc) = the winning row of the group
+// out (B, Cc, M) with G = B M, arg (G, Cc) = the winning row of the group.  grid (G, ceil(Cc / 64)): the group count (65 536 for SA1 of PointNet2SSG at
+// B = 128) on the x axis, whose limit is 2^31 - 1; the y axis ends at 65 535
 __global__ void k_smt_pool_fwd(const float *__restrict__ y, float *__restrict__ out, int32_t *__restrict__ arg, int M, int ns, int Cc) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  const long long g = blockIdx.y;
+  const int c = blockIdx.y * blockDim.x + threadIdx.x;
+  const long long g = blockIdx.x;
   if (c >= Cc) return;
   const float *p = y + (size_t)g * ns * Cc + c;
   float best = p[0];
@@ -2094,8 +2096,8 @@ __global__ void k_smt_pool_fwd(const float *__restrict__ y, float *__restrict__ 
 }
 // dy (G ns, Cc) = d_out (B, Cc, M) at the group's winning row, zero elsewhere
 __global__ void k_smt_pool_bwd(const float *__restrict__ d_out, const int32_t *__restrict__ arg, float *__restrict__ dy, int M, int ns, int Cc) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  const long long g = blockIdx.y;
+  const int c = blockIdx.y * blockDim.x + threadIdx.x;
+  const long long g = blockIdx.x;
   if (c >= Cc) return;
   const long long b = g / M, m = g % M;
   const float v = d_out[((size_t)b * Cc + c) * M + m];
@@ -2155,7 +2157,8 @@ int check_smt(const dfx_shared_mlp_train *t, const void *ws, size_t ws_bytes, in
   DFX_REQUIRE(B >= 1 && M >= 1 && ns >= 1 && (long long)B * M * ns < (1ll << 31), "%s: bad sizes", what);
   DFX_REQUIRE(t->ch[0] >= 1, "%s: no input channels", what);
   for (int l = 0; l < t->layers; ++l) {
-    DFX_REQUIRE(t->ch[l + 1] >= 4 && t->ch[l + 1] % 4 == 0 && t->ch[l + 1] <= 1024, "%s: layer %d: %d output channels (multiple of 4, <= 1024)", what, l, t->ch[l + 1]);
+    // (every width is the K of two fp32 products — the next layer's forward and this layer's dX = dz W — and mfma_linear.h consumes K eight at a time)
+    DFX_REQUIRE(t->ch[l + 1] >= 8 && t->ch[l + 1] % 8 == 0 && t->ch[l + 1] <= 1024, "%s: layer %d: %d output channels (multiple of 8, <= 1024)", what, l, t->ch[l + 1]);
     DFX_REQUIRE(t->conv_w[l], "%s: layer %d: null weight", what, l);
     DFX_REQUIRE(t->bn_w[l] ? (t->bn_b[l] != nullptr) : true, "%s: layer %d: BatchNorm weight without bias", what, l);
   }
@@ -2860,7 +2863,7 @@ int dfx_shared_mlp_train_forward(const dfx_shared_mlp_train *t, void *workspace,
     in = act, K = co;
   }
   const int cl = t->ch[t->layers];
-  if (pool) k_smt_pool_fwd<<<dim3((cl + 63) / 64, (unsigned)G), 64, 0, st>>>(in, out, w.arg, M, ns, cl);
+  if (pool) k_smt_pool_fwd<<<dim3((unsigned)G, (cl + 63) / 64), 64, 0, st>>>(in, out, w.arg, M, ns, cl);
   else k_smt_from_rows<<<dim3((unsigned)((L + 31) / 32), (cl + 31) / 32, B), 256, 0, st>>>(in, out, cl, L, cl);
   return dfx::check_launch("shared_mlp_train_forward");
 }
@@ -2879,7 +2882,7 @@ int dfx_shared_mlp_train_backward(const dfx_shared_mlp_train *t, void *workspace
   carve_smt(w, workspace, t, R, G);
   const int cl = t->ch[t->layers];
   float *dy = w.dA, *other = w.dB;
-  if (pool) k_smt_pool_bwd<<<dim3((cl + 63) / 64, (unsigned)G), 64, 0, st>>>(d_out, w.arg, dy, M, ns, cl);
+  if (pool) k_smt_pool_bwd<<<dim3((unsigned)G, (cl + 63) / 64), 64, 0, st>>>(d_out, w.arg, dy, M, ns, cl);
   else k_smt_to_rows<<<dim3((unsigned)((L + 31) / 32), (cl + 31) / 32, B), 256, 0, st>>>(d_out, dy, cl, L, cl);
   for (int l = t->layers - 1; l >= 0; --l) {
     const int co = t->ch[l + 1], ci = l == 0 ? w.cp0 : t->ch[l], ci_valid = t->ch[l];

@@ -130,7 +130,7 @@ class PointNetV2(nn.Module):
                                                             B, N, _ffi.current_stream())
             _ffi.check(rc, "dfx_pointnet_v2_forward_f32")
             return m, v
-        if self.training and x.is_cuda and B >= 2 and A == 4 and self.zdim % 4 == 0:
+        if self.training and x.is_cuda and B >= 2 and A == 4 and self.zdim >= 8 and self.zdim % 8 == 0:
             # train() mode: batch-statistics BatchNorm forward (running statistics updated in place like nn.BatchNorm1d) and
             # the backward on libdfx's training kernels (difffacto_amd/training.py).  Exact fp32 unless the caller sets
             # `module.train_precision = "bf16"` (bf16 operands for the trunk's products: the max-pool's arg-max may flip under
@@ -155,7 +155,7 @@ class PointNetV2(nn.Module):
             _unsupported("PointNetV2 in eval() mode with a gradient required through it (an input or a parameter has requires_grad; "
                          "running-statistics BatchNorm has no native backward): freeze the module (requires_grad_(False)), wrap the "
                          "call in torch.no_grad(), or call .train() for the stage-1 training step")
-        _unsupported(f"PointNetV2.train() needs batch >= 2 (BatchNorm batch statistics), num_anchors == 4 and zdim % 4 == 0; "
+        _unsupported(f"PointNetV2.train() needs batch >= 2 (BatchNorm batch statistics), num_anchors == 4 and zdim % 8 == 0; "
                      f"got B={B}, num_anchors={A}, zdim={self.zdim}")
 
 
@@ -188,10 +188,17 @@ class PointNet2SSG(nn.Module):
 
     def _head(self, feat):
         """fc_layer on libdfx: (B, 1024) -> (B, zdim * num_anchors).  The rows of the training kernels are the B shapes (x as (1, C, B, 1))."""
-        from .pointnet2_ops.pointnet2_modules import mlp_train
+        from .pointnet2_ops.pointnet2_modules import mlp_train, train_widths_ok
         fc = self.fc_layer
         if fc[1].training != fc[4].training:
             _unsupported("PointNet2 head with its two BatchNorm1d layers in different modes")
+        # What the training kernels do not serve runs the module's own layers, like the SA / FP modules: a last width zdim * num_anchors that fails
+        # the width rule (not a multiple of 8, > 1024), anything but fp32 on the GPU.  One row under batch statistics has no variance: nn.BatchNorm1d
+        # raises there, and so does this (through the same layers) instead of updating the running statistics with it.
+        native = feat.is_cuda and feat.dtype == torch.float32 and all(p.is_cuda and p.dtype == torch.float32 for p in fc.parameters()) \
+            and train_widths_ok([fc[0].in_features, fc[0].out_features, fc[3].out_features]) and train_widths_ok([fc[7].in_features, fc[7].out_features])
+        if not native or (fc[1].training and feat.shape[0] == 1):
+            return fc(feat)
         x = feat.t().contiguous()[None, :, :, None]
         h = mlp_train([(fc[0], fc[1]), (fc[3], fc[4])], x, pool=False)                   # Linear + BatchNorm1d + ReLU, twice
         h = fc[6](h)                                                                       # nn.Dropout(0.5): identity in eval()

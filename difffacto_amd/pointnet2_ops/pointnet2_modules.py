@@ -10,8 +10,8 @@ shapes of PointNet2SSG); the module's torch parameters are only read (so checkpo
 In ``train()`` mode (round 6) the shared MLP with BATCH-statistics BatchNorm, its running-statistics update, the max
 and their gradients run in libdfx too (``dfx_shared_mlp_train_forward`` / ``_backward`` behind an autograd Function;
 the grouping / interpolation already had native gradient kernels); ``eval()`` with gradients enabled takes the same kernels
-with the running statistics.  Only stacks the training kernels do not serve (an output width that is not a multiple of 4)
-run the module's own torch layers.
+with the running statistics.  Only stacks the training kernels do not serve (an output width that is not a multiple of 8 or exceeds 1024:
+``train_widths_ok``) run the module's own torch layers.
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -107,17 +107,28 @@ def _inference(module: nn.Module) -> bool:
     return not module.training and not torch.is_grad_enabled()
 
 
+def train_widths_ok(channels) -> bool:
+    """The width rule of dfx_shared_mlp_train_* on a channel list [c_in, c_1, .., c_L]: 1 .. DFX_MLP_MAX_LAYERS layers, every OUTPUT width a multiple of 8 and
+    at most 1024.  Each output width is the K of two fp32 products (the next layer's forward, this layer's dX = dz W) and the MFMA kernels consume K eight
+    at a time; only the input width is free (libdfx pads it).  Pure: no tensors (check_smt in train_kernels.hip states the same rule)."""
+    channels = [int(c) for c in channels]
+    if not 1 <= len(channels) - 1 <= _ffi.DFX_MLP_MAX_LAYERS or channels[0] < 1:
+        return False
+    return all(8 <= c <= 1024 and c % 8 == 0 for c in channels[1:])
+
+
 def _train_native_ok(seq: nn.Sequential) -> bool:
-    """The training kernels (dfx_shared_mlp_train_*) serve build_shared_mlp stacks of <= 4 layers whose output widths are multiples of 4, fp32 on the
-    GPU, BatchNorm in train() mode (batch statistics) or in eval() mode under autograd (running statistics); anything else stays on the torch layers."""
+    """The training kernels (dfx_shared_mlp_train_*) serve build_shared_mlp stacks of <= 4 layers whose output widths pass ``train_widths_ok`` (multiples
+    of 8, <= 1024), fp32 on the GPU, BatchNorm in train() mode (batch statistics) or in eval() mode under autograd (running statistics); anything else
+    stays on the torch layers."""
     try:
         layers = _NativeMLP(seq).layers
     except NotImplementedError:
         return False
-    if not 1 <= len(layers) <= _ffi.DFX_MLP_MAX_LAYERS:
+    if not layers or not train_widths_ok([layers[0][0].in_channels] + [conv.out_channels for conv, _ in layers]):
         return False
     for conv, bn in layers:
-        if conv.out_channels % 4 or conv.out_channels > 1024 or conv.weight.dtype != torch.float32 or not conv.weight.is_cuda:
+        if conv.weight.dtype != torch.float32 or not conv.weight.is_cuda:
             return False
         if bn is not None and (not bn.affine or not bn.track_running_stats or bn.momentum is None):
             return False
@@ -289,7 +300,7 @@ class _PointnetSAModuleBase(nn.Module):
             elif xyz.is_cuda and _train_native_ok(mlp):
                 # train() / eval() under autograd: grouping (libdfx, with its gradient kernels) -> Conv2d 1x1 + BatchNorm2d (batch statistics) + ReLU -> max, natively (round 6)
                 pooled.append(shared_mlp_train(mlp, grouper(xyz, new_xyz, features), pool=True))
-            else:   # a stack the training kernels do not serve (an output width that is not a multiple of 4, mixed BatchNorm modes)
+            else:   # a stack the training kernels do not serve (train_widths_ok fails, mixed BatchNorm modes)
                 nbh = mlp(grouper(xyz, new_xyz, features))   # (B, mlp[-1], npoint, nsample)
                 pooled.append(nbh.amax(dim=3))               # max_pool2d over nsample, squeezed
         return new_xyz, torch.cat(pooled, dim=1)

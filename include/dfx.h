@@ -662,7 +662,8 @@ int dfx_fp_forward_f32(dfx_shared_mlp *h, const float *unknown, const float *kno
  * (pointnet2_ops_lib/pointnet2_ops/pointnet2_modules.py:9-19, :62-70; PointnetFPModule's mlp :170-209 with pool = 0), forward with saved
  * activations and backward — what autograd through nn.Conv2d / nn.BatchNorm2d / F.max_pool2d computes in the reference.  Exact fp32.
  *   x (B, ch[0], M, ns) = the grouper's output (QueryAndGroup / GroupAll through dfx_group_points, or the interpolated + skip features with
- *   ns = 1; a Linear + BatchNorm1d head over a batch of rows, e.g. PointNet2SSG.fc_layer (models/encoders/pointnet2.py:47-56): B = 1, M = rows, ns = 1); out (B, ch[layers], M) when pool != 0, else (B, ch[layers], M, ns).  ch[l] % 4 == 0 for l >= 1; layers <= DFX_MLP_MAX_LAYERS.
+ *   ns = 1; a Linear + BatchNorm1d head over a batch of rows, e.g. PointNet2SSG.fc_layer (models/encoders/pointnet2.py:47-56): B = 1, M = rows, ns = 1); out (B, ch[layers], M) when pool != 0, else (B, ch[layers], M, ns).  ch[l] % 8 == 0 and 8 <= ch[l] <= 1024 for l >= 1 (each is the K of
+ *   two fp32 MFMA products, consumed eight at a time; ch[0] is free: it is padded to a multiple of 8 internally); layers <= DFX_MLP_MAX_LAYERS.
  *   conv_b[l] == NULL when the layer has BatchNorm (bn_w[l] != NULL); bn_mean / bn_var: running statistics, updated IN PLACE by the forward
  *   when momentum >= 0.  grads: the same struct whose conv_w / conv_b / bn_w / bn_b name WRITABLE buffers of the parameters' shapes.
  *   batch_stats = 1: BatchNorm of train() mode; 0: eval() mode under autograd (the running statistics normalise, nothing is updated); the same value
@@ -710,7 +711,8 @@ int dfx_pointnet_v2_forward_f32(dfx_pointnet_v2 *h, const float *x, const float 
  * gradients of conv / BatchNorm / head weights and biases into `grads` (same struct, writable pointers; its running-statistics
  * pointers are ignored).  momentum >= 0 updates the running statistics in place like nn.BatchNorm1d (unbiased variance),
  * momentum < 0 leaves them alone.  workspace: dfx_pointnet_v2_train_workspace_bytes(B, N, 4, zdim), 256-byte aligned, shared
- * by the forward and the backward of one step.  num_anchors = 4, B >= 2.  precision as for the denoiser. */
+ * by the forward and the backward of one step.  num_anchors = 4, B >= 2, zdim % 8 == 0 (the K of the last head layer's input-gradient
+ * products; the eval handle has the same rule).  precision as for the denoiser. */
 size_t dfx_pointnet_v2_train_workspace_bytes(int B, int N, int num_anchors, int zdim);
 int dfx_pointnet_v2_train_forward(const dfx_pointnet_v2_weights *w, void *workspace, size_t workspace_bytes, const float *x,
                                   const float *attn, float *m, float *v, float momentum, int B, int N, int precision,
